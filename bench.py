@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: Q4_0 x Q8_1 W4A8 GEMV on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line: value, ms_per_step, gbps,
+us_per_gemv and roofline.achieved all come from the timed steps. Everything below marked (--full) takes
+runs of its own and is measured only with --full; without it those keys of the line are null or absent.
+--dump-outputs DIR writes what the last timed step computed, the [G, M, N] outputs a caller of the timed
+path receives, as float32 DIR/<name>.npy (rank 0; a fixed seeded sample where an array exceeds its share
+of 64 MB). The inputs are the seeded step4 recipe, so the same arguments give the same files.
 
 Workload:
   * N=1: BASELINE configs[1] — M=1, N=4096, K=4096, Q4_0 weights x Q8_1 activations.
@@ -15,22 +22,23 @@ Workload:
     replicated Q8_1 vector already in HBM. The step's G launches are captured in a hipGraph.
   * value = effective TFLOPS (2*M*N*K per GEMV, all ranks) over the timed steps; "gbps" is the
     matching algorithmic byte rate (tests/benchmark/benchmark_comparison.cu:138-140 formula).
+  * NMSE vs an fp64 product of the unquantized inputs (--full).
   * roofline.achieved = algorithmic bytes of ONE launch / its average duration, measured live with
     HIP events on the launch stream over the timed graph replays (so it includes each launch's
     dispatch boundary; rocprofv3's kernel-only durations are committed under profiles/).
-  * "batched": the same G GEMVs issued as ONE qg_gemm_w4a8_strided_batched launch per step;
+  * (--full) "batched": the same G GEMVs issued as ONE qg_gemm_w4a8_strided_batched launch per step;
     "grouped": the same through the pointer-array entry qg_gemm_w4a8_grouped (independent B / C
     pointers per item, what a decoder layer's Q / K / V or gate / up projections can use).
-  * roofline.floor_us / floor_frac: the single-launch floor under the same protocol (libqg_calib.so:
+  * (--full) roofline.floor_us / floor_frac: the single-launch floor under the same protocol (libqg_calib.so:
     an empty kernel with the GEMV's grid, and the best pure coalesced read of the same algorithmic
     bytes per launch over the same rotating copies) — what ONE isolated launch of this size can reach.
-  * N=1 side configs: BASELINE configs[2] and [3], and configs[4]'s full N=32000 GEMV on ONE GPU as
+  * (--full) N=1 side configs: BASELINE configs[2] and [3], and configs[4]'s full N=32000 GEMV on ONE GPU as
     single launches and as one grouped launch of G — the denominators of the strong-scaling ratios.
-  * N>1 "strong": the N=32000 GEMV split over the ranks (32000/N rows each), timed per step with
+  * (--full) N>1 "strong": the N=32000 GEMV split over the ranks (32000/N rows each), timed per step with
     the all-gather, as G single launches and as one grouped launch per step; the 1-GPU N=32000
     times measured in the same run on each rank's own GPU; strong_speedup_vs_1gpu_n32000 =
     1-GPU time per GEMV / N-GPU time per GEMV, per leg.
-  * cpu_baseline (rank 0, N=1): the oracle's restatement of gemm_w4a8_reference
+  * (--full) cpu_baseline (rank 0, N=1): the oracle's restatement of gemm_w4a8_reference
     (include/gemm_reference.h:175-222) on the step4 input recipe, 1 thread pinned, ~10 s sample;
     beside it the product's own host twin (libqg_host.so qg_gemm_w4a8_cpu_mt) at 1 pinned thread
     (cpu_baseline_twin) and row-partitioned over its persistent worker pool at 16 threads and at
@@ -53,6 +61,7 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(REPO, "llama.cpp-quant-gemm_amd"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -612,6 +621,26 @@ def strong_legs(world: int, rank: int, dev, G: int, steps: int, warmup: int, M: 
                         "ranks), like for like per leg; DESIGN.md §7"}}
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes over all files of one --dump-outputs
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """Write each tensor as float32 dirname/<name>.npy. An array larger than its equal share of DUMP_BUDGET is
+    cut to a fixed sample: the flat elements at sorted indices drawn without replacement by
+    numpy.random.default_rng(0), the same for every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1) // 4
+    written = {}
+    for name, t in arrays.items():
+        x = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if x.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=share, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), x)
+        written[name] = list(x.shape)
+    return written
+
+
 def compact_summary(out: dict) -> dict:
     """The bench line's figures in ~1.5 KB (the line's last key; see main)."""
     r = out.get("roofline") or {}
@@ -658,6 +687,12 @@ def main() -> None:
                     help="skip the side measurements of BASELINE configs[2], [3] and [4]-on-1-GPU (N = 1 only)")
     ap.add_argument("--no-floor", action="store_true", help="skip the single-launch floor (roofline.floor_us)")
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling N=32000 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: NMSE vs fp64, per-step distribution, batched / "
+                         "grouped launches, single-launch floor, hot point, gather and strong legs (N > 1), CPU baselines "
+                         "and the side configs (the --no-* switches trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -709,16 +744,19 @@ def main() -> None:
     mods = [RowShardedW4A8(wcopies[i], n_total, K, wtype) for i in range(R)]
 
     # accuracy of this run's data: NMSE vs an fp64 matmul of the unquantized inputs
-    c = qg.gemm_w4a8(aq, bq, M, local, K, wtype)
-    ref = a.double() @ b.double().T
-    num = torch.sum((c.double() - ref) ** 2)
-    den = torch.sum(ref ** 2)
-    if world > 1:
-        nd = torch.stack([num, den])
-        dist.all_reduce(nd)
-        num, den = nd[0], nd[1]
-    nmse = float(num / den)
-    del b, ref, c
+    nmse = None
+    if args.full:
+        c = qg.gemm_w4a8(aq, bq, M, local, K, wtype)
+        ref = a.double() @ b.double().T
+        num = torch.sum((c.double() - ref) ** 2)
+        den = torch.sum(ref ** 2)
+        if world > 1:
+            nd = torch.stack([num, den])
+            dist.all_reduce(nd)
+            num, den = nd[0], nd[1]
+        nmse = float(num / den)
+        del ref, c
+    del b
 
     lib = qg._lib.load()
     a_ptr = ctypes.c_void_p(aq.data_ptr())
@@ -794,10 +832,19 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- what the timed path computed in its last step
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % 2
+        arrays = {"c": outs[last][:, :, :local]}
+        if world > 1:
+            arrays["c_gathered"] = gathered[last]
+        dumped = dump_outputs(args.dump_outputs, arrays)
+
     # ---- per-step distribution (median, p10, p90), in its own pass after the
     #      timed region: HIP events around each step's launches on the launch stream
     step_pct = None
-    if graphs is not None:
+    if args.full and graphs is not None:
         torch.cuda.synchronize()
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(max(args.steps, 10))]
@@ -814,7 +861,7 @@ def main() -> None:
     # ---- the same G GEMVs as ONE strided-batched launch (qg_gemm_w4a8_strided_batched): the
     #      per-launch dispatch cost is paid once per step instead of once per GEMV
     batched_us = None
-    if R >= G:
+    if args.full and R >= G:
         fnb = lib.qg_gemm_w4a8_strided_batched
         bout = torch.empty((G, M, rows), dtype=torch.float32, device=dev)
         cs = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -843,7 +890,7 @@ def main() -> None:
     # ---- the same G GEMVs as ONE pointer-array grouped launch (qg_gemm_w4a8_grouped, through the
     #      shipped module's compute_local_group): independent weight / output pointers per item
     grouped_us = None
-    if graphs is not None and args.algo == 0:
+    if args.full and graphs is not None and args.algo == 0:
         gout = torch.zeros((G, M, rows), dtype=torch.float32, device=dev)
         grouped_us = graph_time_us(lambda: RowShardedW4A8.compute_local_group(mods[:G], aq, M, gout), 20, G)
         if not torch.equal(gout[:, :, :local], outs[0][:, :, :local]):
@@ -851,7 +898,7 @@ def main() -> None:
 
     # ---- the single-launch floor of this size under the same protocol (roofline.floor_us)
     floor = None
-    if graphs is not None and not args.no_floor:
+    if args.full and graphs is not None and not args.no_floor:
         rpb = 16  # the M = 1 GEMV's rows per 1024-thread workgroup (qg_gemv.hip)
         floor = measure_floor(dev, wcopies, G, algo_bytes(M, local, K, bb), (local + rpb - 1) // rpb, 1024,
                               unit_shape=(local, K) if (M == 1 and wtype == 2 and K <= 4096 and K % 64 == 0) else None)
@@ -859,7 +906,7 @@ def main() -> None:
     # ---- N > 1: the step's all-gather alone (same bytes, no GEMVs beside it), so the per-GPU kernel
     #      time and the gather latency are reported separately (SURVEY.md §7, 8-GPU hard part)
     gather_us = None
-    if world > 1:
+    if args.full and world > 1:
         for _ in range(3):
             dist.all_gather_into_tensor(gathered[0].view(-1), outs[0].view(-1))
         torch.cuda.synchronize()
@@ -873,7 +920,7 @@ def main() -> None:
 
     # ---- hot (Infinity-Cache resident) reference point: one copy, same launch count
     hot_us = None
-    if graphs is not None:
+    if args.full and graphs is not None:
         g_hot = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_hot):
             for j in range(G):
@@ -888,7 +935,7 @@ def main() -> None:
         hot_us = (time.perf_counter() - th) / (10 * G) * 1e6
 
     strong = None
-    if world > 1 and not args.no_strong and graphs is not None:
+    if args.full and world > 1 and not args.no_strong and graphs is not None:
         del mods, wcopies
         torch.cuda.empty_cache()
         strong = strong_legs(world, rank, dev, G, args.steps, args.warmup)
@@ -953,10 +1000,12 @@ def main() -> None:
             "gather": None if gather_us is None else {
                 "us_per_step": round(gather_us, 2), "bytes_per_rank": G * M * rows * 4,
                 "note": f"all_gather_into_tensor of one step's {G} output slices alone ({backend})"},
+            "full": args.full,
+            "outputs": None if dumped is None else {"dir": args.dump_outputs, "shapes": dumped},
             "hot_l3": None if hot_us is None else {"us_per_gemv": round(hot_us, 3),
                                                    "tflops": round(flops_per_gemv / world / hot_us / 1e6, 3)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             one, twin, mt = cpu_baseline(M, n_total, K, wtype, args.cpu_seconds)
             rnd = lambda d: {k: (round(v, 6) if isinstance(v, float) else v) for k, v in d.items()}
             out["cpu_baseline"] = rnd(one)
@@ -964,7 +1013,8 @@ def main() -> None:
             out["cpu_baseline_mt"] = [rnd(x) for x in mt]
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_configs and args.wtype == "q4_0" and args.n == 0 and args.m == 1 and args.k == 4096:
+        if (args.full and world == 1 and not args.no_configs and args.wtype == "q4_0" and args.n == 0 and args.m == 1
+                and args.k == 4096):
             # BASELINE configs[2] (the M=32 prefill) and configs[3] (all-quants GEMV), measured on the
             # same GPU in the same run (parity cases otherwise; not part of `value`)
             torch.cuda.empty_cache()

@@ -21,5 +21,5 @@ run() {  # name timeout cmd...
 rm -f $OUT/steps.log
 run pytest_gpu 1000 python -u -m pytest $TESTS -m gpu -q -rf --timeout 300 --timeout-method thread
 [ "${NOSMOKE:-0}" = 1 ] || run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[ "${NOBENCH:-0}" = 1 ] || run bench 400 python bench.py --steps 50 --warmup 10
+[ "${NOBENCH:-0}" = 1 ] || run bench 400 python bench.py --full --steps 50 --warmup 10
 echo done

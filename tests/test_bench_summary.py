@@ -1,5 +1,5 @@
 """bench.py's compact summary (the bench line's LAST key): built from every kind of row the
-line carries, short enough to survive the driver's tail of stdout. CPU only (no GPU, no measurement)."""
+line carries, short enough to survive the driver's tail of stdout; and the --dump-outputs writer. CPU only (no GPU, no measurement)."""
 import json
 import os
 import sys
@@ -30,3 +30,25 @@ def test_compact_summary_rows_and_size():
     assert sm["batched_us"] == 1.385 and sm["grouped_us"] == 1.505 and sm["cpu_16t_ms"] == 0.5
     # the driver keeps about 2 KB of the tail: the summary with its key must fit in well under that
     assert len(json.dumps({"summary": sm})) < 1400
+
+
+def test_dump_outputs_full_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array; an array over its share of the byte budget becomes the same
+    sorted seeded sample of its flat elements on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+    x = torch.arange(6000, dtype=torch.float32).reshape(6, 10, 100)
+    y = torch.arange(50, dtype=torch.float64)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"x": x, "y": y}) == {"x": [6, 10, 100], "y": [50]}
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), x.numpy())
+    assert np.load(tmp_path / "a" / "y.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4 * 1000)  # 1000 elements per array
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), {"x": x, "y": y}) == {"x": [1000], "y": [50]}
+    xs = np.load(tmp_path / "b" / "x.npy")
+    assert np.array_equal(xs, np.load(tmp_path / "c" / "x.npy"))
+    assert xs.dtype == np.float32 and (np.diff(xs) > 0).all() and xs.max() < 6000
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 2 * 4 * 1000 + 2 * 128  # the .npy headers beside the budgeted data

@@ -18,7 +18,7 @@ TAG=${1:?usage: gpu_step.sh TAG STEP...}; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs"
 for step in "$@"; do
   echo "== $step"
   case $step in
@@ -33,7 +33,7 @@ for step in "$@"; do
       timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1
       cat "$OUT/smoke.txt" ;;
     bench)
-      timeout -k 10 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
       tail -1 "$OUT/bench.json" | cut -c1-600 ;;
     trace)
       timeout -k 10 400 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --stats --output-format csv -d "$OUT/trace_ser" -o run -- $B > "$OUT/trace_ser.log" 2>&1
