@@ -12,6 +12,7 @@
  *   block_q4_1  20 B  compat/ggml_types.h:90-96
  *   block_q5_0  22 B  compat/ggml_types.h:111-117
  *   block_q5_1  24 B  compat/ggml_types.h:125-132
+ *   block_q4_K 144 B  ggml's K-quant (the reference defines only QK_K = 256 and the type id)
  *
  * Nibble packing (include/quantize.h:56-67): qs[j] low nibble = x[j], high nibble = x[j+16].
  * Q5 fifth bit (tests/framework/test_framework.cuh:309-325): bit i of the little-endian u32
@@ -61,7 +62,23 @@ typedef struct {
     int8_t qs[32];
 } qg_block_q8_1;
 
+/* ggml's block_q4_K: a super-block of 256 elements = 8 sub-blocks of 32.
+ *   scales[12]: eight 6-bit scales sc[0..7] and eight 6-bit mins m[0..7]:
+ *     j <  4: sc[j] = q[j] & 63                             m[j] = q[j+4] & 63
+ *     j >= 4: sc[j] = (q[j+4] & 15) | ((q[j-4] >> 6) << 4)  m[j] = (q[j+4] >> 4) | ((q[j] >> 6) << 4)
+ *   qs[128]: chunk i = 0..3 covers elements 64i .. 64i+63; for l = 0..31
+ *     element 64i + l = qs[32i + l] & 15 (sub-block 2i), element 64i + 32 + l = qs[32i + l] >> 4 (sub-block 2i+1)
+ *   value of element e of sub-block j = d * sc[j] * q_e - dmin * m[j] */
+#define QG_QK_K 256
+typedef struct {
+    uint16_t d;          /* fp16 scale of the sub-block scales */
+    uint16_t dmin;       /* fp16 scale of the sub-block mins */
+    uint8_t scales[12];
+    uint8_t qs[128];
+} qg_block_q4_K;
+
 #ifdef __cplusplus
+static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");
 static_assert(sizeof(qg_block_q4_1) == 20, "block_q4_1 must be 20 bytes");
 static_assert(sizeof(qg_block_q5_0) == 22, "block_q5_0 must be 22 bytes");
@@ -69,6 +86,7 @@ static_assert(sizeof(qg_block_q5_1) == 24, "block_q5_1 must be 24 bytes");
 static_assert(sizeof(qg_block_q8_0) == 34, "block_q8_0 must be 34 bytes");
 static_assert(sizeof(qg_block_q8_1) == 36, "block_q8_1 must be 36 bytes");
 #else
+_Static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 _Static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");
 _Static_assert(sizeof(qg_block_q4_1) == 20, "block_q4_1 must be 20 bytes");
 _Static_assert(sizeof(qg_block_q5_0) == 22, "block_q5_0 must be 22 bytes");

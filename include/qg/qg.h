@@ -38,7 +38,8 @@ typedef enum {
     QG_TYPE_Q5_0 = 6,
     QG_TYPE_Q5_1 = 7,
     QG_TYPE_Q8_0 = 8,
-    QG_TYPE_Q8_1 = 9
+    QG_TYPE_Q8_1 = 9,
+    QG_TYPE_Q4_K = 12  /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
 } qg_type;
 
 typedef enum {
@@ -73,6 +74,26 @@ int qg_gemm_w4a8_ex(const void* A_q8_1, const void* B, float* C, int M, int N, i
  * column slice of a wider buffer in the row-sharded multi-GPU path, quant_gemm/sharded.py). */
 int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int64_t ldc, int wtype,
                      int algo, qg_stream_t stream);
+
+/* ---- Q4_K weights (wtype == QG_TYPE_Q4_K) --------------------------------------------------
+ * B: block_q4_K[N][K/256], ggml's bytes (qg/blocks.h). Sub-block j of super-block sb meets activation
+ * block 8 sb + j:
+ *   C(m, n) = sum_sb [ d * sum_j d_a * float(sc_j * sumi_j)  -  dmin * sum_j float(m_j) * s_a ]
+ * with sumi the exact int32 dot of the 4-bit codes and the Q8_1 bytes, and s_a the Q8_1 block's stored sum
+ * (as the Q4_1 / Q5_1 min terms). The order of the fp32 operations is the kernel's; each output is within
+ * 2 * (K/32 + W + 2) * 2^-24 * sum(|terms|) of the exact value, W = 0 for the decode GEMV and 16 for the
+ * MFMA prefill, and two launches give identical bits.
+ * Taken by: qg_gemm_w4a8, qg_gemm_w4a8_ex, qg_gemm_w4a8_ldc, qg_debug_sumi (per-sub-block sumi[M][N][K/32]
+ * from the product's own instantiation), qg_debug_config, qg_select_algo, qg_dequantize,
+ * qg_gemm_w4a8_from_view (weights view: nb[0] = 144, ne[0] = K) and qg_gemm_w4a8_f32 with a workspace
+ * (quantize into it, then the product). QG_ALGO_AUTO: the decode GEMV ("q4k_gemv") for M <= 8, the MFMA
+ * prefill ("q4k_mmq") from M = 9 on; both may be forced (the GEMV only for M <= 8 and while its LDS
+ * records, 336 B per token and super-block, fit 160 KiB).
+ * Validation: K not a positive multiple of 256 -> QG_ERR_BAD_K; B not 16-B aligned or A not 4-B aligned ->
+ * QG_ERR_ALIGN; QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a
+ * workspace of qg_gemm_w4a8_f32_workspace_size(M, K) bytes -> QG_ERR_UNSUPPORTED.
+ * Every other entry that takes a wtype (tiled, repacked, prepacked, padded, grouped, strided-batched, _ws,
+ * qg_quantize) returns QG_ERR_UNSUPPORTED for it and launches nothing. */
 
 /* The Solution entry point of the definition gemm_q4_0_q8_1_w4a8
  * (schemas/definitions/gemm/gemm_q4_0_q8_1_w4a8.json:35-53: inputs A_q8_1[M][K/32], B_q4_0[N][K/32],
@@ -390,7 +411,8 @@ int qg_gguf_kv_string(const qg_gguf* file, int64_t index, const char** str, uint
 const char* qg_status_string(int status);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
-int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 0 if unknown */
+int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 0 if unknown */
+int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K, 0 if unknown */
 const char* qg_version(void);
 
 #ifdef __cplusplus

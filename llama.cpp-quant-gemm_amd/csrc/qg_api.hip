@@ -21,6 +21,7 @@
 
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
+#include "qg_q4k.hpp"
 
 using namespace qg;
 
@@ -140,6 +141,10 @@ bool is_weight_type(int t) {
     return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
 }
 
+// Q4_K (256-element super-blocks) has its own predicate and its own dispatch (run_q4k below): the entries
+// that take it test this first, every other entry keeps is_weight_type and so keeps refusing it.
+bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
+
 // Crossover from profiles/tools_archive/mmq_probe.hip (profiles/r01_tuning/mmq_probe_smallm.txt): the dot4 GEMV
 // wins up to M = 4 (its LDS activation reads grow with M), the MFMA kernel from M = 5 on.
 int select_algo(const GemmArgs& g) {
@@ -225,6 +230,30 @@ int run_gemm(GemmArgs& g, int algo, hipStream_t st) {
     return QG_OK;
 }
 
+// Q4_K products (qg_q4k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on. Interleaved A/B
+// against a build with the threshold at 4 | 5 (profiles/q4k/ab_q4k_variants.txt, N = K = 4096): M = 5 GEMV 5.82 us,
+// MFMA 7.43; M = 8 GEMV 7.31, MFMA 7.45 — the GEMV keeps M <= 8. The GEMV's LDS records bound M * K
+// (q4k_gemv_eligible); beyond that AUTO takes the MFMA kernel at any M.
+#ifndef QG_Q4K_GEMV_MAXM  // (A/B builds: the largest M AUTO sends to the decode GEMV)
+#define QG_Q4K_GEMV_MAXM 8
+#endif
+int select_algo_q4k(const GemmArgs& g) {
+    return g.M <= QG_Q4K_GEMV_MAXM && q4k_gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
+}
+
+int run_q4k(GemmArgs& g, int algo, hipStream_t st) {
+    if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
+    if (g.K <= 0 || g.K % 256 != 0) return QG_ERR_BAD_K;
+    if (g.M == 0 || g.N == 0) return QG_OK;
+    if (!g.A || !g.B || (!g.C && !g.sumi)) return QG_ERR_INVALID_ARG;
+    if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return QG_ERR_ALIGN;
+    if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_AUTO) algo = select_algo_q4k(g);
+    if (algo == QG_ALGO_GEMV) return q4k_gemv_eligible(g) ? hip_status(launch_q4k_gemv(g, st)) : QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_MFMA) return q4k_mmq_eligible(g) ? hip_status(launch_q4k_mmq(g, st)) : QG_ERR_UNSUPPORTED;
+    return QG_ERR_INVALID_ARG;
+}
+
 // The tiled weight layout (qg_tile_weights): the MFMA small-batch decode for M = 3..4 and M = 2 at K/32 > 256
 // (qg_gemvm.hip), the tiled decode GEMV for the rest of M <= 4 (qg_gemvt.hip, round 6), the
 // MFMA kernels beyond (LAY_TILED; odd K/32 through its activation windows). Shapes neither
@@ -255,9 +284,12 @@ int block_bytes(int t) {
         case QG_TYPE_Q5_1: return 24;
         case QG_TYPE_Q8_0: return 34;
         case QG_TYPE_Q8_1: return 36;
+        case QG_TYPE_Q4_K: return 144;
     }
     return 0;
 }
+
+int block_elems(int t) { return is_q4k_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
 
 int weight_major(int wtype, const void* W, const void* A, float* out, int M, int N, int K, qg_stream_t s) {
     // out[mw][nt] = sum_b dot(W[mw][b], A[nt][b]) -> activation-major (m = nt, n = mw) with
@@ -287,7 +319,8 @@ int run_w16(int wtype, const float* A, const void* B, float* C, int M, int N, in
 size_t row_bytes(int type, int64_t K) {
     if (type == QG_TYPE_F32) return (size_t)K * 4;
     if (type == QG_TYPE_F16) return (size_t)K * 2;
-    return (size_t)(K / 32) * (size_t)block_bytes(type);
+    const int be = block_elems(type);  // 256 for Q4_K
+    return be ? (size_t)(K / be) * (size_t)block_bytes(type) : 0;
 }
 
 int view_dims(const qg_tensor_view* act, const qg_tensor_view* w, const qg_tensor_view* out, int64_t& M, int64_t& N,
@@ -314,6 +347,22 @@ size_t fused_workspace_bytes(int M, int K) { return M > 0 && K > 0 ? (size_t)M *
 // the Q8_1 product (same bytes, so the same results); without a workspace, fused GEMV launches
 // over row chunks (the weights are streamed once per chunk).
 int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (is_q4k_type(g.wtype)) {
+        // Q4_K has no fused prologue: FP32 rows are quantized into the caller's workspace, then the Q8_1
+        // product runs on it (the same bytes, so the same results as the two calls)
+        if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
+        if (g.K <= 0 || g.K % 256 != 0) return QG_ERR_BAD_K;
+        if (g.M == 0 || g.N == 0) return QG_OK;
+        if (!g.A || !g.B || !g.C) return QG_ERR_INVALID_ARG;
+        if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return QG_ERR_ALIGN;
+        if (g.ain != AIN_F32 || !ws || ws_bytes < fused_workspace_bytes(g.M, g.K)) return QG_ERR_UNSUPPORTED;
+        if (((uintptr_t)ws & 3) != 0) return QG_ERR_ALIGN;
+        const hipError_t e = launch_quantize(QG_TYPE_Q8_1, 0, (const float*)g.A, ws, (int64_t)g.M * (g.K / 32), st);
+        if (e != hipSuccess) return hip_status(e);
+        g.ain = AIN_Q8_1;
+        g.A = ws;
+        return run_q4k(g, QG_ALGO_AUTO, st);
+    }
     if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
     if (g.K <= 0 || g.K % 32 != 0) return QG_ERR_BAD_K;
     if (!is_weight_type(g.wtype)) return QG_ERR_UNSUPPORTED;
@@ -424,6 +473,7 @@ int qg_gemm_w4a8_ex(const void* A, const void* B, float* C, int M, int N, int K,
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
     g.ldc_m = N; g.ldc_n = 1;
+    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
     return run_gemm(g, algo, (hipStream_t)stream);
 }
 
@@ -717,7 +767,7 @@ int qg_gemm_w8a8(const void* A, const void* B, float* C, int M, int N, int K, qg
 
 int qg_quantize(int type, int variant, const float* x, void* y, int64_t k, qg_stream_t stream) {
     if (k < 0 || k % 32 != 0) return QG_ERR_BAD_K;
-    if (block_bytes(type) == 0) return QG_ERR_UNSUPPORTED;
+    if (block_bytes(type) == 0 || is_q4k_type(type)) return QG_ERR_UNSUPPORTED;  // (no Q4_K quantizer)
     if (variant != 0 && !(variant == 1 && type == QG_TYPE_Q8_1) &&
         !(variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0)))
         return QG_ERR_UNSUPPORTED;
@@ -739,6 +789,13 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 }
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
+    if (is_q4k_type(type)) {
+        if (k < 0 || k % 256 != 0) return QG_ERR_BAD_K;
+        if (k == 0) return QG_OK;
+        if (!x || !y) return QG_ERR_INVALID_ARG;
+        if (((uintptr_t)y & 3) != 0 || ((uintptr_t)x & 1) != 0) return QG_ERR_ALIGN;
+        return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
+    }
     if (k < 0 || k % 32 != 0) return QG_ERR_BAD_K;
     if (block_bytes(type) == 0) return QG_ERR_UNSUPPORTED;
     if (k == 0) return QG_OK;
@@ -754,6 +811,7 @@ int qg_debug_sumi(const void* A, const void* B, int32_t* sumi, int M, int N, int
     GemmArgs g;
     g.A = A; g.B = B; g.sumi = sumi; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
     g.ldc_m = N; g.ldc_n = 1;
+    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
     return run_gemm(g, algo, (hipStream_t)stream);
 }
 
@@ -767,6 +825,7 @@ int qg_debug_config(int M, int N, int K, int wtype, int algo, int sumi, char* bu
     else g.C = (float*)256;
     g.ldc_m = N; g.ldc_n = 1;
     g.describe = buf; g.describe_len = len;
+    if (is_q4k_type(wtype)) return run_q4k(g, algo, nullptr);
     return run_gemm(g, algo, nullptr);
 }
 
@@ -776,6 +835,7 @@ int qg_gemm_w4a8_ldc(const void* A, const void* B, float* C, int M, int N, int K
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
     g.ldc_m = (long)ldc; g.ldc_n = 1;
+    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
     return run_gemm(g, algo, (hipStream_t)stream);
 }
 
@@ -794,9 +854,10 @@ int qg_gemm_w4a8_from_view(const qg_tensor_view* act, const qg_tensor_view* w, q
         else if (strcmp(kernel_type, "ragged") == 0) algo = QG_ALGO_RAGGED;
         else return QG_ERR_INVALID_ARG;
     }
-    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !is_weight_type(w->type)) return QG_ERR_UNSUPPORTED;
+    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !(is_weight_type(w->type) || is_q4k_type(w->type)))
+        return QG_ERR_UNSUPPORTED;
     int64_t M, N, K;
-    const int rc = view_dims(act, w, out, M, N, K);
+    const int rc = view_dims(act, w, out, M, N, K, block_elems(w->type));  // Q4_K: K % 256, 144-B super-blocks
     if (rc != QG_OK) return rc;
     return qg_gemm_w4a8_ex(act->data, w->data, (float*)out->data, (int)M, (int)N, (int)K, w->type, algo, stream);
 }
@@ -864,11 +925,14 @@ int qg_last_hip_error(void) { return g_last_hip; }
 int qg_select_algo(int M, int N, int K, int wtype) {
     GemmArgs g;
     g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
+    if (is_q4k_type(wtype)) return K > 0 && K % 256 == 0 ? select_algo_q4k(g) : -1;
     if (K <= 0 || K % 32 != 0 || !is_weight_type(wtype)) return -1;
     return select_algo(g);
 }
 
 int qg_block_bytes(int type) { return block_bytes(type); }
+
+int qg_block_elems(int type) { return block_elems(type); }
 
 const char* qg_version(void) { return "qg-mi355x 0.1.0 (gfx950)"; }
 

@@ -1,7 +1,7 @@
 // qg_gguf.hip — GGUF reader (host code): the weight-file side of the ggml-facing adapter
-// (SURVEY.md §8f-4). Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 tensors in GGUF files use the same block
+// (SURVEY.md §8f-4). Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 and Q4_K tensors in GGUF files use the same block
 // bytes as the kernels (qg/blocks.h), so a tensor's data is uploaded as-is and viewed as a
-// qg_tensor_view for qg_gemm_w4a8_from_view.
+// qg_tensor_view for qg_gemm_w4a8_from_view (Q4_K: nb[0] = 144, rows of ne[0] / 256 super-blocks).
 //
 // Format (GGUF v2/v3, little-endian): "GGUF", u32 version, u64 tensor count, u64 metadata count;
 // metadata key/value pairs (string = u64 length + bytes; typed values, arrays of values); tensor
@@ -115,9 +115,9 @@ uint64_t tensor_bytes(uint32_t t, const int64_t ne[4], uint32_t n_dims) {
         case QG_TYPE_F32: return n * 4;
         case QG_TYPE_F16: return n * 2;
     }
-    const int bb = qg_block_bytes((int)t);
-    if (bb == 0 || ne[0] % 32 != 0) return 0;
-    return n / 32 * (uint64_t)bb;
+    const int bb = qg_block_bytes((int)t), be = qg_block_elems((int)t);  // Q4_K: 144-B super-blocks of 256
+    if (bb == 0 || be == 0 || ne[0] % be != 0) return 0;
+    return n / (uint64_t)be * (uint64_t)bb;
 }
 
 int parse(qg_gguf* g) {
@@ -161,6 +161,8 @@ int parse(qg_gguf* g) {
         t.type = r.get<uint32_t>();
         t.offset = r.get<uint64_t>();
         t.nbytes = tensor_bytes(t.type, t.ne, t.n_dims);
+        // a Q4_K row is whole super-blocks: ggml cannot have written anything else
+        if (t.type == QG_TYPE_Q4_K && r.ok && t.ne[0] % 256 != 0) return QG_ERR_INVALID_ARG;
         g->tensors.push_back(std::move(t));
     }
     if (!r.ok) return QG_ERR_INVALID_ARG;
@@ -254,7 +256,7 @@ int qg_gguf_tensor_view(const qg_gguf* g, int64_t i, void* device_data, qg_tenso
     const int bb = qg_block_bytes((int)t.type);
     const size_t row = t.type == QG_TYPE_F32 ? (size_t)t.ne[0] * 4
                        : t.type == QG_TYPE_F16 ? (size_t)t.ne[0] * 2
-                                               : (size_t)(t.ne[0] / 32) * (size_t)bb;
+                                               : (size_t)(t.ne[0] / qg_block_elems((int)t.type)) * (size_t)bb;
     out->nb[0] = t.type == QG_TYPE_F32 ? 4 : t.type == QG_TYPE_F16 ? 2 : (size_t)bb;
     out->nb[1] = row;
     out->nb[2] = row * (size_t)t.ne[1];

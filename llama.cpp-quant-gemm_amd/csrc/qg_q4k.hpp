@@ -1,0 +1,53 @@
+// qg_q4k.hpp — Q4_K (ggml type 12) building blocks shared by the decode GEMV (qg_q4k_gemv.hip), the MFMA
+// prefill (qg_q4k_mmq.hip) and the dequantizer (qg_quantize.hip).
+//
+// block_q4_K (include/qg/blocks.h), 144 B = 36 dwords, 256 elements:
+//   dword 0      f16 d | f16 dmin << 16
+//   dwords 1..3  scales[12]: eight 6-bit scales sc[0..7] and eight 6-bit mins m[0..7]
+//   dwords 4..35 qs[128]: chunk i = 0..3 is dwords 4 + 8i .. 4 + 8i + 7; the low nibble of byte l of the chunk
+//                is element l of sub-block 2i, the high nibble element l of sub-block 2i + 1
+// Sub-block j of super-block sb meets activation block 8 sb + j. The product ("Q4_K"):
+//   C(m, n) = sum_sb [ d * sum_j d_a * float(sc_j * sumi_j)  -  dmin * sum_j float(m_j) * s_a ]
+// sc_j * sumi_j is below 2^24 in magnitude, so the int -> float conversion is exact.
+#pragma once
+#include "qg_common.hpp"
+#include "qg_kernels.hpp"
+
+namespace qg {
+
+constexpr int Q4K_BYTES = 144;
+constexpr int Q4K_DW = 36;
+
+// The eight scales and eight mins of one super-block, four bytes per dword:
+//   sc[0] = sc 0..3, sc[1] = sc 4..7, mn[0] = m 0..3, mn[1] = m 4..7.
+struct q4k_scales {
+    uint32_t sc[2], mn[2];
+};
+__host__ __device__ __forceinline__ q4k_scales q4k_unpack_scales(uint32_t u0, uint32_t u1, uint32_t u2) {
+    q4k_scales r;
+    r.sc[0] = u0 & 0x3F3F3F3Fu;
+    r.mn[0] = u1 & 0x3F3F3F3Fu;
+    r.sc[1] = (u2 & 0x0F0F0F0Fu) | ((u0 >> 2) & 0x30303030u);
+    r.mn[1] = ((u2 >> 4) & 0x0F0F0F0Fu) | ((u1 >> 2) & 0x30303030u);
+    return r;
+}
+// byte J (0..7) of a two-dword group
+template <int J> __host__ __device__ __forceinline__ int q4k_byte(const uint32_t (&v)[2]) {
+    return (int)((v[J / 4] >> (8 * (J % 4))) & 0xFFu);
+}
+
+// Decode GEMV (M <= 8): see qg_q4k_gemv.hip. LDS per (token, super-block): 64 qs dwords, 8 x (d_a, s_a) fp32,
+// 4 pad dwords (84 = 4 x odd: the 16-B reads of lanes on consecutive super-blocks hit distinct bank groups).
+constexpr int Q4K_REC_DW = 84;
+inline size_t q4k_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / SB_ELEMS) * Q4K_REC_DW * 4; }
+constexpr size_t Q4K_GEMV_LDS_MAX = 160 * 1024;
+
+// Shape / pointer rules of the two families (K % 256 == 0 and the alignments are checked by the C-ABI first).
+bool q4k_gemv_eligible(const GemmArgs& g);
+hipError_t launch_q4k_gemv(const GemmArgs& g, hipStream_t st);
+bool q4k_mmq_eligible(const GemmArgs& g);
+hipError_t launch_q4k_mmq(const GemmArgs& g, hipStream_t st);
+// nsb super-blocks -> 256 * nsb floats, y = (d * sc) * q - dmin * m (qg_quantize.hip)
+hipError_t launch_dequantize_q4k(const void* x, float* y, int64_t nsb, hipStream_t st);
+
+}  // namespace qg

@@ -16,6 +16,7 @@
 //     Q8_1 s = sum(x) in element order as variant 0 (the definition's torch.sum order is unspecified)
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_q4k.hpp"
 #include "qg_quant_block.hpp"
 
 namespace qg {
@@ -468,6 +469,44 @@ hipError_t launch_quantize_f16_fused(const void* x, void* y, int64_t nblocks, hi
     if (nblocks == 0) return hipSuccess;
     hipLaunchKernelGGL(quantize_f16_fused_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, st,
                        (const uint16_t*)x, (uint8_t*)y, nblocks);
+    return hipGetLastError();
+}
+
+// Q4_K (qg_q4k.hpp): one thread per 32-element sub-block, y = (d * sc_j) * q - dmin * m_j in exactly that
+// operation order (no contraction), so the result can be checked bit for bit. Byte loads: x needs only the
+// 2-B alignment of its fp16 fields.
+namespace {
+__global__ __launch_bounds__(256) void dequantize_q4k_kernel(const uint8_t* __restrict__ x, float* __restrict__ y,
+                                                             int64_t nsub) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nsub) return;
+    const uint8_t* b = x + (g >> 3) * Q4K_BYTES;
+    const int j = (int)(g & 7);
+    const float d = h2f((uint32_t)b[0] | ((uint32_t)b[1] << 8)), dmin = h2f((uint32_t)b[2] | ((uint32_t)b[3] << 8));
+    const uint8_t* q = b + 4;
+    int sc, mn;
+    if (j < 4) {
+        sc = q[j] & 63;
+        mn = q[j + 4] & 63;
+    } else {
+        sc = (q[j + 4] & 15) | ((q[j - 4] >> 6) << 4);
+        mn = (q[j + 4] >> 4) | ((q[j] >> 6) << 4);
+    }
+    const float ds = d * (float)sc, dm = dmin * (float)mn;
+    const uint8_t* qs = b + 16 + 32 * (j >> 1);
+    float* o = y + g * QK;
+    for (int l = 0; l < 32; ++l) {
+        const int v = (j & 1) ? qs[l] >> 4 : qs[l] & 15;
+        o[l] = ds * (float)v - dm;
+    }
+}
+}  // namespace
+
+hipError_t launch_dequantize_q4k(const void* x, float* y, int64_t nsb, hipStream_t st) {
+    if (nsb == 0) return hipSuccess;
+    const int64_t nsub = nsb * 8;
+    hipLaunchKernelGGL(dequantize_q4k_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
+                       nsub);
     return hipGetLastError();
 }
 

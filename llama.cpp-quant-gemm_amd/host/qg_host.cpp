@@ -117,6 +117,48 @@ template <class F> void gemm_rows(const uint8_t* A, const uint8_t* B, float* C, 
         }
 }
 
+// Q4_K (qg/blocks.h: 144-B super-blocks of 8 sub-blocks; sub-block j of super-block sb meets activation block
+// 8 sb + j). The product contract of qg.h, in the decode GEMV's operation order: per super-block one fp32 dot
+// accumulator and one min accumulator in sub-block order, d and dmin applied once, super-blocks summed in order.
+struct FmtQ4_K {
+    static constexpr int bytes = 144;
+    static void scale_min(const uint8_t* q, int j, int& sc, int& m) {
+        if (j < 4) {
+            sc = q[j] & 63;
+            m = q[j + 4] & 63;
+        } else {
+            sc = (q[j + 4] & 15) | ((q[j - 4] >> 6) << 4);
+            m = (q[j + 4] >> 4) | ((q[j] >> 6) << 4);
+        }
+    }
+};
+template <>
+void gemm_rows<FmtQ4_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int N, int K, int j0, int j1) {
+    const int nsb = K / 256;
+    const size_t arow = (size_t)(K / QK) * 36, wrow = (size_t)nsb * FmtQ4_K::bytes;
+    for (int i = 0; i < M; ++i)
+        for (int n = j0; n < j1; ++n) {
+            float sum = 0.0f;
+            for (int sb = 0; sb < nsb; ++sb) {
+                const uint8_t* w = B + n * wrow + (size_t)sb * FmtQ4_K::bytes;
+                const float d = half_to_float(w), dmin = half_to_float(w + 2);
+                float fd = 0.0f, fm = 0.0f;
+                for (int j = 0; j < 8; ++j) {
+                    const ActBlock a(A + i * arow + (size_t)(8 * sb + j) * 36);
+                    const uint8_t* qs = w + 16 + 32 * (j / 2);
+                    int32_t sumi = 0;
+                    for (int l = 0; l < 32; ++l) sumi += (int32_t)a.qs[l] * ((j & 1) ? qs[l] >> 4 : qs[l] & 15);
+                    int sc, m;
+                    FmtQ4_K::scale_min(w + 4, j, sc, m);
+                    fd += a.d * (float)(sc * sumi);
+                    fm += (float)m * a.s;
+                }
+                sum += d * fd - dmin * fm;
+            }
+            C[(size_t)i * N + n] = sum;
+        }
+}
+
 // Process-wide persistent worker pool: threads are started once (grown on demand) and parked on
 // a condition variable between jobs, so a multi-threaded call costs one wake-up per worker instead
 // of a thread start and join (which dominated a 1-9 ms GEMV at 256 threads). One job at a time
@@ -213,8 +255,10 @@ extern "C" {
 int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int threads) {
     const int rc = check_gemm(A, B, C, M, N, K);
     if (rc != QG_OK) return rc;
+    if (wtype == QG_TYPE_Q4_K && K % 256 != 0) return QG_ERR_BAD_K;
     if (M == 0 || N == 0) return QG_OK;
     switch (wtype) {
+        case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q5_0: gemm_threads<FmtQ5_0>(A, B, C, M, N, K, threads); return QG_OK;

@@ -11,7 +11,7 @@ Same names, argument meaning, tensor layouts and error behaviour as the referenc
 Differences, all deliberate: kernels run on torch's *current* HIP stream (the reference launches
 on the legacy default stream, gemm_ops.cu:250); validation errors raise RuntimeError like
 TORCH_CHECK does. Extra entry points expose the rest of the C-ABI: the activation-major
-``gemm_w4a8`` (include/gemm_reference.h convention), Q4_1/Q5_0/Q5_1 weights, every quantizer and
+``gemm_w4a8`` (include/gemm_reference.h convention), Q4_1/Q5_0/Q5_1 and Q4_K weights, every quantizer and
 the per-block ``debug_sumi`` parity hook. Every call goes to HIP kernels in ``libqg_hip.so``;
 there is no CPU path.
 """
@@ -32,9 +32,18 @@ BLOCK_Q8_1_BYTES = 36
 
 # ggml_type ids (compat/ggml_types.h:199-215)
 Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 2, 3, 6, 7, 8, 9
-BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36}
+Q4_K = 12  # 256-element super-blocks of 144 bytes (qg.h "Q4_K weights")
+BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144}
 ALGO_AUTO, ALGO_GEMV, ALGO_MFMA, ALGO_GENERIC, ALGO_RAGGED = 0, 1, 2, 3, 4
 WEIGHT_TYPES = (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0)
+# what gemm_w4a8 / gemm_w4a8_f32 / debug_sumi take; the layout entries (tiled, repacked, grouped, batched) keep
+# WEIGHT_TYPES
+GEMM_WEIGHT_TYPES = WEIGHT_TYPES + (Q4_K,)
+
+
+def block_elems(qtype: int) -> int:
+    """Elements per block of a type (qg_block_elems): 32, or 256 for Q4_K; 0 if unknown."""
+    return _lib.load().qg_block_elems(qtype)
 
 
 def _require(cond: bool, msg: str) -> None:
@@ -60,7 +69,7 @@ def quantize(x: torch.Tensor, qtype: int, variant: int = 0) -> torch.Tensor:
     _require(x.dim() >= 1, "Input must have at least 1 dimension")
     K = x.size(-1)
     _require(K % 32 == 0, f"Last dimension must be divisible by 32, got {K}")
-    _require(qtype in BLOCK_BYTES, f"unknown quant type {qtype}")
+    _require(qtype in BLOCK_BYTES and qtype != Q4_K, f"unknown quant type {qtype}")
     x = x.contiguous()
     out = torch.empty(tuple(x.shape[:-1]) + (K // 32, BLOCK_BYTES[qtype]), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
@@ -87,10 +96,11 @@ def dequantize(x_q: torch.Tensor, qtype: int) -> torch.Tensor:
     _require(x_q.numel() % bb == 0, f"Input size {x_q.numel()} is not a multiple of {bb}-byte blocks")
     x_q = x_q.contiguous()
     nblocks = x_q.numel() // bb
-    shape = tuple(x_q.shape[:-2]) + (x_q.shape[-2] * 32,) if x_q.dim() >= 2 else (nblocks * 32,)
+    be = block_elems(qtype)
+    shape = tuple(x_q.shape[:-2]) + (x_q.shape[-2] * be,) if x_q.dim() >= 2 else (nblocks * be,)
     out = torch.empty(shape, dtype=torch.float32, device=x_q.device)
     with torch.cuda.device(x_q.device):
-        _lib.check(_lib.load().qg_dequantize(qtype, _ptr(x_q), _ptr(out), nblocks * 32, _stream(x_q.device)),
+        _lib.check(_lib.load().qg_dequantize(qtype, _ptr(x_q), _ptr(out), nblocks * be, _stream(x_q.device)),
                    "dequantize")
     return out
 
@@ -105,10 +115,11 @@ def dequantize_q4_0(x_q: torch.Tensor, K: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------- GEMMs
-def _check_blocks(t: torch.Tensor, what: str, rows: int, K: int, bb: int) -> None:
+def _check_blocks(t: torch.Tensor, what: str, rows: int, K: int, bb: int, be: int = 32) -> None:
+    """rows x K elements in blocks of be elements and bb bytes (be = block_elems(type): 256 for Q4_K)."""
     _require(t.is_cuda, f"{what} must be a CUDA tensor")
     _require(t.dtype == torch.uint8, f"{what} must be uint8")
-    expect = rows * (K // 32) * bb
+    expect = rows * (K // be) * bb
     _require(t.numel() == expect, f"{what} shape mismatch: expected {expect} elements, got {t.numel()}")
 
 
@@ -130,10 +141,11 @@ def gemm_w4a8(activation_q: torch.Tensor, weight_q: torch.Tensor, M: int, N: int
     ``out``: optional float32 [M, N] destination; its rows may be strided (``out.stride(1) == 1``,
     ``out.stride(0) >= N``, e.g. a column slice of a wider buffer), written through
     ``qg_gemm_w4a8_ldc``."""
-    _require(K % 32 == 0, f"K must be divisible by 32, got {K}")
-    _require(wtype in WEIGHT_TYPES, f"unsupported weight type {wtype}")
+    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
+    be = block_elems(wtype)
+    _require(K % be == 0, f"K must be divisible by {be}, got {K}")
     _check_blocks(activation_q, "Activation", M, K, 36)
-    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype])
+    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype], be)
     a = activation_q.contiguous()
     w = weight_q.contiguous()
     if out is None:
@@ -403,10 +415,12 @@ def gemm_w4a8_f32(x: torch.Tensor, weight_q: torch.Tensor, wtype: int = Q4_0, wo
     _require(x.is_cuda, "Input must be a CUDA tensor")
     _require(x.dtype == torch.float32 and x.dim() == 2, "x must be float32 [M, K]")
     M, K = x.shape
-    _require(K % 32 == 0, f"K must be divisible by 32, got {K}")
-    _require(wtype in WEIGHT_TYPES, f"unsupported weight type {wtype}")
-    N = weight_q.numel() // ((K // 32) * BLOCK_BYTES[wtype]) if K else 0
-    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype])
+    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
+    be = block_elems(wtype)
+    _require(K % be == 0, f"K must be divisible by {be}, got {K}")
+    _require(wtype != Q4_K or workspace, "Q4_K weights need the Q8_1 workspace (workspace=True)")
+    N = weight_q.numel() // ((K // be) * BLOCK_BYTES[wtype]) if K else 0
+    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype], be)
     x = x.contiguous()
     w = weight_q.contiguous()
     if out is None:
@@ -498,8 +512,9 @@ def gemm_q4_0_fp32(weight_q: torch.Tensor, activation: torch.Tensor, M: int, N: 
 def debug_sumi(activation_q: torch.Tensor, weight_q: torch.Tensor, M: int, N: int, K: int,
                wtype: int = Q4_0, algo: int = ALGO_AUTO) -> torch.Tensor:
     """Per-block int32 dots [M, N, K/32] through the same decode path as ``algo``."""
+    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
     _check_blocks(activation_q, "Activation", M, K, 36)
-    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype])
+    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype], block_elems(wtype))
     out = torch.empty((M, N, K // 32), dtype=torch.int32, device=weight_q.device)
     with torch.cuda.device(weight_q.device):
         _lib.check(_lib.load().qg_debug_sumi(_ptr(activation_q.contiguous()), _ptr(weight_q.contiguous()),
@@ -576,5 +591,5 @@ __all__ = [
     "gemm_w4a16", "gemm_w8a16", "gemm_q4_0_fp32",
     "tile_weights", "gemm_w4a8_tiled", "debug_sumi_tiled", "debug_config_tiled",
     "quantize_q8_1_tiled", "tile_activations", "gemm_w4a8_tiled_act", "debug_sumi_tiled_act", "debug_config_tiled_act",
-    "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1",
+    "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "block_elems",
 ]

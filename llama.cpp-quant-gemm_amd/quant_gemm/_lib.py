@@ -104,6 +104,7 @@ SIGNATURES = {
     "qg_last_hip_error": ([], I),
     "qg_select_algo": ([I, I, I, I], I),
     "qg_block_bytes": ([I], I),
+    "qg_block_elems": ([I], I),
     "qg_version": ([], ctypes.c_char_p),
 }
 

@@ -19,7 +19,9 @@ import torch
 from . import _lib
 
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
-_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36}
+Q4_K = 12
+_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144}
+_BE = {Q4_K: 256}  # elements per block where it is not 32 (qg_block_elems)
 
 
 class TensorView(ctypes.Structure):
@@ -29,7 +31,7 @@ class TensorView(ctypes.Structure):
 
 def view_of(t: torch.Tensor, qtype: int, k: int) -> TensorView:
     """ggml-ordered view of a dense row-major tensor holding rows of K elements of ``qtype``."""
-    row = k * 4 if qtype == F32 else k * 2 if qtype == F16 else (k // 32) * _BB[qtype]
+    row = k * 4 if qtype == F32 else k * 2 if qtype == F16 else (k // _BE.get(qtype, 32)) * _BB[qtype]
     rows = t.numel() * t.element_size() // row
     v = TensorView()
     v.data, v.type = t.data_ptr(), qtype
@@ -70,12 +72,13 @@ class GGUFTensor:
 
     @property
     def shape(self) -> tuple:
-        """torch-order shape of the data: [.., rows, K/32, block bytes] (quantized) or [.., rows, K]."""
+        """torch-order shape of the data: [.., rows, K/32, block bytes] (quantized; Q4_K: [.., rows, K/256, 144])
+        or [.., rows, K]."""
         dims = [d for d in reversed(self.ne)]
         while len(dims) > 1 and dims[0] == 1:
             dims = dims[1:]
         if self.type in _BB:
-            return tuple(dims[:-1]) + (dims[-1] // 32, _BB[self.type])
+            return tuple(dims[:-1]) + (dims[-1] // _BE.get(self.type, 32), _BB[self.type])
         return tuple(dims)
 
     def __repr__(self) -> str:
