@@ -121,6 +121,89 @@ def build(d, dmin, sc, m, q) -> np.ndarray:
     return b
 
 
+# f16 scale values at the ends of the format: subnormals (2^-24 .. 1023 * 2^-24, 2^-15 among them), the smallest
+# normal (2^-14) and the largest finite value (65504)
+F16_SUBNORMALS = (2.0 ** -24, 3 * 2.0 ** -24, 2.0 ** -20, 2.0 ** -15, 1023 * 2.0 ** -24)
+F16_MIN_NORMAL = 2.0 ** -14
+F16_MAX = 65504.0
+EXTREME_ROWS = 16  # weight rows extremes() gives a class of their own; the rest are random_q4k rows
+
+
+def extremes(rng, m: int, n: int = 32, k: int = 512):
+    """Q8_1 [m, k/32, 36] and Q4_K [n, k/256, 144] at the ends of their scale formats, one class per weight row
+    (an output's tolerance follows its own magnitude, so no row's extreme hides another's). No Inf, no NaN; the
+    largest term, 65504 * 63 * 65504 * (15 * 127 * 32) = 1.6e16, is far inside fp32.
+
+    Weight rows: 0..3 d and dmin f16 subnormals of both signs; 4 the smallest normal; 5 d = dmin = 65504 with every
+    sc = m = 63 and every nibble 15; 6..8 the other sign pairs of +-65504; 9 sc = 0, m = 63; 10 sc = 63, m = 0;
+    11..14 sub-blocks 4..7 (whose sc and m keep their high two bits in another byte) at 16 / 32 / 48 / 63 in four
+    rotations, sub-blocks 0..3 at zero (11) or at the complement (12..14); 15 sc = m = 48 in sub-blocks 4..7 and 16 in
+    0..3.
+    Activation token 0: every d_a and s_a an f16 subnormal. Token 1: super-block 0 meets subnormal d_a with
+    s_a = -65504 .. -36832, the others d_a = 65504, qs = +127, s_a = -65504. Further tokens are random."""
+    assert m >= 2 and n >= EXTREME_ROWS and k % QK_K == 0
+    nsb = k // QK_K
+    bq = random_q4k(rng, n, k)
+    d, dmin, sc, mn, q = fields(bq)
+    sub = np.array(F16_SUBNORMALS)
+    alt = np.where(np.arange(nsb) % 2 == 0, 1.0, -1.0)  # the sign alternates along the super-blocks
+    for r in range(4):
+        d[r] = sub[(r + np.arange(nsb)) % 5] * alt * (1 if r % 2 == 0 else -1)
+        dmin[r] = sub[(2 * r + 1 + np.arange(nsb)) % 5] * alt * (1 if r < 2 else -1)
+    d[4], dmin[4] = F16_MIN_NORMAL * alt, -F16_MIN_NORMAL * alt
+    for r, (sd, sm) in zip(range(5, 9), ((1, 1), (-1, -1), (1, -1), (-1, 1))):
+        d[r], dmin[r] = sd * F16_MAX, sm * F16_MAX
+    sc[5], mn[5], q[5] = 63, 63, 15
+    sc[9], mn[9] = 0, 63
+    sc[10], mn[10] = 63, 0
+    hi = np.array([16, 32, 48, 63])
+    for i, r in enumerate(range(11, 15)):
+        sc[r, :, 4:], mn[r, :, 4:] = np.roll(hi, i), np.roll(hi[::-1], i)
+        sc[r, :, :4], mn[r, :, :4] = (0, 0) if i == 0 else (63 - sc[r, :, 4:], 63 - mn[r, :, 4:])
+    sc[15, :, 4:], mn[15, :, 4:], sc[15, :, :4], mn[15, :, :4] = 48, 48, 16, 16
+    bq = build(d, dmin, sc, mn, q)
+
+    aq = random_q8_1(rng, m, k)
+    nb = k // 32
+    j = np.arange(nb)
+    aq[0, :, 0:2] = _f16_bytes(sub[j % 5])
+    aq[0, :, 2:4] = _f16_bytes(sub[(j + 2) % 5] * np.where(j % 3 == 0, -1.0, 1.0))
+    aq[1, :, 0:2] = _f16_bytes(np.where(j < 8, sub[j % 5], F16_MAX))
+    aq[1, :, 2:4] = _f16_bytes(np.where(j < 8, -F16_MAX + 4096.0 * j, -F16_MAX))
+    aq[1, 8:, 4:36] = 127
+    return aq, bq
+
+
+W_OFFSETS = (16, 32, 48, 144)  # 16 mod 32, 32 mod 64, 48 mod 64, one whole super-block
+A_OFFSETS = (4, 8, 12, 36)     # 4 mod 16, 8 mod 16, 12 mod 16, one whole Q8_1 block
+
+
+def fuzz_cases(n_cases: int = 24, seed: int = 412):
+    """(i, m, n, k, weight byte offset, activation byte offset): the seeded Q4_K sweep of tests/test_gpu_q4k_paths.py.
+    M from the product sweep's list (tests/test_gpu_fuzz.py), N in 1..300, K = 256 * (1..20), the offsets from
+    the pointer contract's classes (weights 16 B, activations 4 B)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n_cases):
+        m = int(rng.choice([1, 2, 3, 4, 5, 7, 8, 9, 12, 16, 17, 24, 31, 32, 33, 48, 64, 65, 96]))
+        n = int(rng.integers(1, 301))
+        k = 256 * int(rng.integers(1, 21))
+        out.append((i, m, n, k, int(rng.choice(W_OFFSETS)), int(rng.choice(A_OFFSETS))))
+    return out
+
+
+def dev_at(x: np.ndarray, offset: int):
+    """x on the GPU as a contiguous slice of one flat uint8 buffer, starting `offset` bytes past a 256-B boundary."""
+    import torch
+    x = np.ascontiguousarray(x)
+    flat = torch.zeros(x.nbytes + 512 + offset, dtype=torch.uint8, device="cuda")
+    start = (-flat.data_ptr()) % 256 + offset
+    t = flat[start:start + x.nbytes]
+    t.copy_(torch.from_numpy(x.view(np.uint8).reshape(-1)))
+    assert (t.data_ptr() - offset) % 256 == 0 and t.is_contiguous()
+    return t.reshape(x.shape)
+
+
 def quantize(x: np.ndarray) -> np.ndarray:
     """A simple test-side Q4_K quantizer (for NMSE only; not ggml's): float [N, K] -> uint8 [N, K/256, 144].
     Per sub-block lo = min(0, min x), scale = (max(0, max x) - lo) / 15, mval = -lo; d = f16(max scale / 63),
