@@ -66,7 +66,19 @@ typedef enum {
  * (include/gemm_cuda_naive.cuh:285-292, gemm_cuda_tiled.cuh:293-300, gemm_cuda_dp4a.cuh:409-444)
  * and is the device twin of gemm_w4a8_reference (include/gemm_reference.h:175-222).
  * A: block_q8_1[M][K/32]; B: blocks of `wtype` (Q4_0/Q4_1/Q5_0/Q5_1, or Q8_0 = W8A8) [N][K/32];
- * C: float[M][N], overwritten. M == 0 or N == 0 is a no-op. */
+ * C: float[M][N], overwritten. M == 0 or N == 0 is a no-op.
+ *
+ * Under stream capture (hipStreamBeginCapture, torch.cuda.graph) consecutive independent GEMVs become ONE
+ * kernel node: a call with M <= 4 that AUTO (or QG_ALGO_GEMV) sends to the GEMV, whose only capture
+ * dependency is the GEMV node the calling thread's previous qg_gemm_w4a8 / _ex / _ldc call created in the
+ * same capture, with the same M, K and weight type, adds no node; that node is rewritten into the grouped
+ * launch of qg_gemm_w4a8_grouped over all of them (up to 64 per node). "Independent": the call's output
+ * overlaps no operand of the node's products and its inputs overlap none of their outputs (shared
+ * activations or weights are fine); anything else, e.g. a GEMV that reads the previous one's output, stays
+ * its own node, ordered as captured. Outputs are unchanged bit for bit, and a graph replays the same
+ * dependencies towards everything else captured. Merged where it measured faster (csrc/qg_api.hip,
+ * fuse_class_enabled): every M <= 4 in the loop-free form (K <= 4096), M = 1 beyond; see
+ * qg_set_capture_fusion. Eager (non-captured) calls are never merged. */
 int qg_gemm_w4a8(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream);
 int qg_gemm_w4a8_ex(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, int algo,
                     qg_stream_t stream);
@@ -409,6 +421,13 @@ int qg_gguf_kv_string(const qg_gguf* file, int64_t index, const char** str, uint
 
 /* ---- introspection ---- */
 const char* qg_status_string(int status);
+/* The capture-time GEMV merge (see qg_gemm_w4a8): 0 off, 1 on (the default; the environment variable
+ * QG_CAPTURE_FUSE=0, read once, makes off the default), 2 on for every shape class, measured or not (A/B
+ * runs). Process-wide; affects calls made after it. */
+void qg_set_capture_fusion(int on);
+/* Process-wide counters since load: captured GEMV calls merged into an existing node, and GEMV kernel
+ * nodes those calls started (calls eligible for the merge only). Either pointer may be NULL. */
+void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
 int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 0 if unknown */

@@ -663,8 +663,20 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
                     hipError_t e = hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                     if (e != hipSuccess) return e;
                 }
+                if (g.node_fill) g.node_fill->p = hipKernelNodeParams{};  // func == nullptr: nothing to launch
                 if (tiles == 0 || grp.count == 0) return hipSuccess;
                 grp.full = tiles == tmin ? 1 : 0;
+                if (GemvNodeFill* nf = g.node_fill) {  // capture-time merge: the same launch as a node's parameters
+                    nf->grp = grp;
+                    nf->argv[0] = &nf->grp;
+                    nf->one = one ? 1 : 0;
+                    nf->p.func = (void*)kg;
+                    nf->p.gridDim = dim3(tiles, grp.count);
+                    nf->p.blockDim = dim3(GW);
+                    nf->p.sharedMemBytes = (unsigned)lds;
+                    nf->p.kernelParams = nf->argv;
+                    return hipSuccess;
+                }
                 hipLaunchKernelGGL(kg, dim3(tiles, grp.count), dim3(GW), lds, st, grp);
                 return hipGetLastError();
             };

@@ -41,6 +41,8 @@ struct GemmArgs {
                                  // shared, N = the largest item's
     char* describe = nullptr;    // qg_debug_config: the leaf launcher writes the kernel it would
     size_t describe_len = 0;     // launch here (family + template parameters) and launches nothing
+    struct GemvNodeFill* node_fill = nullptr;  // with `group`: the grouped launcher fills this (kernel, grid,
+                                 // block, LDS, argument) and launches nothing — the capture-time merge
 };
 
 // Descriptor of a grouped GEMV launch (qg_gemm_w4a8_grouped), passed by value as the kernel argument.
@@ -55,6 +57,14 @@ struct GemvGroup {
     // full: every item has the launch's row-tile count (no workgroup exits early) — gemvg_kernel
     int count, M, K, full;
     GemvItemDesc it[GEMV_GROUP_MAX];
+};
+// What the grouped launcher would launch (GemmArgs::node_fill), as the parameters of a graph kernel
+// node: the capture-time merge (qg_api.hip) installs them with hipGraphKernelNodeSetParams.
+struct GemvNodeFill {
+    hipKernelNodeParams p;  // p.func == nullptr: nothing to launch; p.kernelParams = argv
+    GemvGroup grp;          // the kernel's argument, `full` set for the launch's grid
+    void* argv[1];
+    int one;                // the loop-free one-unit form (K/32 units fit the row's lanes)
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device): `done`

@@ -576,6 +576,19 @@ def select_algo(M: int, N: int, K: int, wtype: int = Q4_0) -> int:
     return _lib.load().qg_select_algo(M, N, K, wtype)
 
 
+def set_capture_fusion(on) -> None:
+    """The capture-time GEMV merge (qg.h at qg_gemm_w4a8): False / 0 off, True / 1 on (default), 2 on for
+    every shape class (A/B runs)."""
+    _lib.load().qg_set_capture_fusion(int(on))
+
+
+def capture_fusion_stats() -> "tuple[int, int]":
+    """(merged, nodes): captured GEMV calls merged into an existing graph node, and GEMV nodes started."""
+    merged, nodes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.load().qg_capture_fusion_stats(ctypes.byref(merged), ctypes.byref(nodes))
+    return int(merged.value), int(nodes.value)
+
+
 def version() -> str:
     return _lib.load().qg_version().decode()
 
@@ -592,4 +605,5 @@ __all__ = [
     "tile_weights", "gemm_w4a8_tiled", "debug_sumi_tiled", "debug_config_tiled",
     "quantize_q8_1_tiled", "tile_activations", "gemm_w4a8_tiled_act", "debug_sumi_tiled_act", "debug_config_tiled_act",
     "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "block_elems",
+    "set_capture_fusion", "capture_fusion_stats",
 ]

@@ -102,6 +102,8 @@ SIGNATURES = {
     "qg_gguf_kv_string": ([P, I64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)], I),
     "qg_status_string": ([I], ctypes.c_char_p),
     "qg_last_hip_error": ([], I),
+    "qg_set_capture_fusion": ([I], None),
+    "qg_capture_fusion_stats": ([ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)], None),
     "qg_select_algo": ([I, I, I, I], I),
     "qg_block_bytes": ([I], I),
     "qg_block_elems": ([I], I),
