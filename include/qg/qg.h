@@ -76,7 +76,7 @@ typedef enum {
  * overlaps no operand of the node's products and its inputs overlap none of their outputs (shared
  * activations or weights are fine); anything else, e.g. a GEMV that reads the previous one's output, stays
  * its own node, ordered as captured. Outputs are unchanged bit for bit, and a graph replays the same
- * dependencies towards everything else captured. Merged where it measured faster (csrc/qg_api.hip,
+ * dependencies towards everything else captured. Merged where it measured faster (csrc/qg_capture_fuse.hip,
  * fuse_class_enabled): every M <= 4 in the loop-free form (K <= 4096), M = 1 beyond; see
  * qg_set_capture_fusion. Eager (non-captured) calls are never merged. */
 int qg_gemm_w4a8(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream);

@@ -1,132 +1,31 @@
 // qg_api.hip — the C-ABI (include/qg/qg.h): validation, dispatch, error reporting.
 //
 // Every entry point validates, picks a kernel family and enqueues on the caller's stream, so
-// callers may capture it into a hipGraph. The library's only allocations are the per-(device,
-// stream) workspaces of stream_workspace below — slot 0 the W4A16 / W8A16 split-K partials, slot 1
-// the odd-K/32 prefill's padded copies — made outside capture, never handed to a captured call
-// (captured calls take the non-workspace kernels, or the caller's buffer through the _ws entry
-// points), and grown only: growing one synchronizes its stream once (the library's one host sync,
-// qg.h), qg_release_workspaces frees them.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
+// callers may capture it into a hipGraph. Validation is one ordered precheck (below) plus what is specific
+// to an entry; the quantized product has one entry, run_product. The library's workspaces live in
+// qg_workspace.hip, the capture-time merge of GEMVs in qg_capture_fuse.hip.
 #include <string.h>
 
-#include <algorithm>
-#include <atomic>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <tuple>
-#include <utility>
+#include <initializer_list>
 
 #include "../../include/qg/qg.h"
-#include "qg_capture_fuse.hpp"
 #include "qg_kernels.hpp"
 #include "qg_q4k.hpp"
 
 using namespace qg;
 
 namespace qg {
-namespace {
-std::mutex g_ws_mu;  // guards the map; each entry has its own lock for its buffer
-struct WsEntry {
-    void* p = nullptr;
-    size_t n = 0;
-    std::mutex mu;
-};
-// key: (device, stream, slot) — slot 0 the W4A16 split-K workspace (its counters must stay zero
-// between calls), slot 1 the padded-repack buffers of the odd-K/32 prefill (qg_repack.hip)
-std::map<std::tuple<int, hipStream_t, int>, std::unique_ptr<WsEntry>> g_ws;
-}  // namespace
-
-void* stream_workspace(hipStream_t st, size_t bytes, int slot, std::unique_lock<std::mutex>* hold) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    // Never hand the library's buffer to a stream capture: a graph would keep its raw pointer,
-    // and a later eager call that grows the buffer (or qg_release_workspaces) would free it under
-    // the graph. Captured calls run without it; graphs pass their own workspace
-    // through the _ws entry points.
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return nullptr;
+int block_bytes(int t) {
+    switch (t) {
+        case QG_TYPE_Q4_0: return 18;
+        case QG_TYPE_Q4_1: return 20;
+        case QG_TYPE_Q5_0: return 22;
+        case QG_TYPE_Q5_1: return 24;
+        case QG_TYPE_Q8_0: return 34;
+        case QG_TYPE_Q8_1: return 36;
+        case QG_TYPE_Q4_K: return 144;
     }
-    WsEntry* e;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto& up = g_ws[std::make_tuple(dev, st, slot)];
-        if (!up) up.reset(new WsEntry);
-        e = up.get();
-    }
-    // The entry's lock is held while the buffer grows and, with `hold`, until the caller has
-    // enqueued every kernel that uses it (two host threads on one stream must not
-    // interleave a multi-kernel sequence on one buffer).
-    std::unique_lock<std::mutex> lk(e->mu);
-    if (!e->p || e->n < bytes) {
-        const size_t sz = std::max(bytes, (size_t)4 << 20);
-        void* p = nullptr;
-        if (hipMalloc(&p, sz) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        if (hipMemsetAsync(p, 0, sz, st) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(p);
-            return nullptr;
-        }
-        if (e->p) {
-            // launches still queued on st may use the old block: the one host sync of the library,
-            // once per growth (documented in qg.h; the _ws entry points never reach it)
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(e->p);
-        }
-        e->p = p;
-        e->n = sz;
-    }
-    void* p = e->p;
-    if (hold) *hold = std::move(lk);
-    return p;
-}
-
-int device_cus() {
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 256;
-    }
-    int v = cached[dev].load(std::memory_order_relaxed);
-    if (v > 0) return v;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    cached[dev].store(cus, std::memory_order_relaxed);
-    return cus;
-}
-
-void describe_kernel(const GemmArgs& g, const char* fmt, ...) {
-    if (!g.describe || g.describe_len == 0) return;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g.describe, g.describe_len, fmt, ap);
-    va_end(ap);
-}
-
-void release_workspaces() {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    bool synced = false;
-    for (auto& kv : g_ws) {
-        std::lock_guard<std::mutex> le(kv.second->mu);
-        if (kv.second->p) {
-            if (!synced) (void)hipDeviceSynchronize();
-            synced = true;
-            (void)hipFree(kv.second->p);
-        }
-    }
-    g_ws.clear();
+    return 0;
 }
 }  // namespace qg
 
@@ -143,9 +42,68 @@ bool is_weight_type(int t) {
     return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
 }
 
-// Q4_K (256-element super-blocks) has its own predicate and its own dispatch (run_q4k below): the entries
-// that take it test this first, every other entry keeps is_weight_type and so keeps refusing it.
+// Q4_K (256-element super-blocks): taken by the entries that go through run_product with q4k_ok; every other
+// entry tests is_weight_type alone and so keeps refusing it.
 bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
+
+int block_elems(int t) { return is_q4k_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
+
+// ---- the one ordered precheck ------------------------------------------------------------------------------
+// The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
+// the granule is QG_ERR_BAD_K; a weight type the entry does not take is QG_ERR_UNSUPPORTED; an empty call (a
+// size of 0) is a no-op, whatever its pointers; a null required pointer is QG_ERR_INVALID_ARG; a pointer
+// below its alignment (mask: the low bits that must be zero) is QG_ERR_ALIGN. Nothing is enqueued on any of
+// these. QG_GO: go on with what is specific to the entry.
+constexpr int QG_GO = 1;  // no status: every qg_status is <= 0
+struct PtrReq { const void* p; uintptr_t mask; };
+
+int precheck(std::initializer_list<int64_t> sizes, int64_t K, int granule, bool type_ok,
+             std::initializer_list<PtrReq> ptrs) {
+    for (const int64_t s : sizes) if (s < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % granule != 0) return QG_ERR_BAD_K;
+    if (!type_ok) return QG_ERR_UNSUPPORTED;
+    for (const int64_t s : sizes) if (s == 0) return QG_OK;
+    for (const PtrReq& r : ptrs) if (!r.p) return QG_ERR_INVALID_ARG;
+    for (const PtrReq& r : ptrs) if (((uintptr_t)r.p & r.mask) != 0) return QG_ERR_ALIGN;
+    return QG_GO;
+}
+
+// The element-count entries (qg_quantize, qg_dequantize, qg_quantize_q8_1_f16_fused) keep their own order: a
+// negative count is QG_ERR_BAD_K, and a count of 0 is a no-op only after the type check.
+int precheck_count(int64_t k, int granule, bool type_ok, std::initializer_list<PtrReq> ptrs) {
+    if (k < 0 || k % granule != 0) return QG_ERR_BAD_K;
+    if (!type_ok) return QG_ERR_UNSUPPORTED;
+    if (k == 0) return QG_OK;
+    return precheck({}, k, granule, true, ptrs);
+}
+
+// the output of a product: C, or the debug hook's sumi
+const void* out_ptr(const GemmArgs& g) { return g.C ? (const void*)g.C : (const void*)g.sumi; }
+
+// ---- GemmArgs in one place ---------------------------------------------------------------------------------
+// The activation-major product C[M][N] = A[M][K] . B[N][K]^T with dense output rows.
+GemmArgs product_args(const void* A, const void* B, float* C, int M, int N, int K, int wtype) {
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
+    g.ldc_m = N; g.ldc_n = 1;
+    return g;
+}
+
+// The reference's weight-major form out[mw][nt] = sum_b dot(W[mw][b], A[nt][b]) (M weight rows, N tokens) ->
+// activation-major (m = nt, n = mw) with output strides ldc_m = 1, ldc_n = Ntok.
+GemmArgs weight_major_args(int wtype, const void* W, const void* A, float* out, int M, int N, int K) {
+    GemmArgs g = product_args(A, W, out, N, M, K, wtype);
+    g.ldc_m = 1; g.ldc_n = N;
+    return g;
+}
+
+// The shape alone (qg_debug_config*, qg_select_algo, qg_gemm_w4a8_workspace_size): 256-B aligned stand-in
+// pointers, so the shape decides, as for a real call on aligned buffers.
+GemmArgs query_args(int M, int N, int K, int wtype, int sumi = 0) {
+    GemmArgs g = product_args((const void*)256, (const void*)256, sumi ? nullptr : (float*)256, M, N, K, wtype);
+    if (sumi) g.sumi = (int32_t*)256;
+    return g;
+}
 
 // Crossover from profiles/tools_archive/mmq_probe.hip (profiles/r01_tuning/mmq_probe_smallm.txt): the dot4 GEMV
 // wins up to M = 4 (its LDS activation reads grow with M), the MFMA kernel from M = 5 on.
@@ -161,139 +119,8 @@ int select_algo(const GemmArgs& g) {
     return QG_ALGO_GENERIC;
 }
 
-// ---- capture-time merge of back-to-back GEMVs (qg.h at qg_gemm_w4a8; hazard test: qg_capture_fuse.hpp) ----
-// A GEMV enqueued on a capturing stream whose ONLY capture dependency is a GEMV node this thread created in
-// the same capture, and which is independent of that node's items, adds no node: the node is rewritten
-// (hipGraphKernelNodeSetParams) into one grouped launch over all of them — the gemvg_kernel, grid and LDS
-// qg_gemm_w4a8_grouped would launch for the same items, so every output keeps its bits. The merged node keeps
-// the first node's predecessors and the new GEMV's only predecessor was that node, so the only ordering
-// removed is between items of the group (independent by the hazard test); successors captured earlier
-// (forked streams) merely wait for one more item. Any error on the way is swallowed and the call takes the
-// plain launch: a call that succeeds unmerged never fails merged.
-static_assert(fuse::MAX_ITEMS == GEMV_GROUP_MAX, "qg_capture_fuse.hpp and qg_kernels.hpp disagree on the group size");
-std::atomic<int> g_fuse_mode{-1};  // 0 off, 1 on (the measured classes), 2 every class (A/B runs); -1: not read yet
-std::atomic<uint64_t> g_fuse_merged{0}, g_fuse_nodes{0};
-
-int fuse_mode() {
-    int m = g_fuse_mode.load(std::memory_order_relaxed);
-    if (m >= 0) return m;
-    const char* e = getenv("QG_CAPTURE_FUSE");  // read once: the default until qg_set_capture_fusion
-    m = e && e[0] == '0' && !e[1] ? 0 : e && e[0] == '2' && !e[1] ? 2 : 1;
-    int unset = -1;
-    g_fuse_mode.compare_exchange_strong(unset, m, std::memory_order_relaxed);
-    return g_fuse_mode.load(std::memory_order_relaxed);
-}
-
-// The node the calling thread's last captured GEMV created or merged into. Capture ids are unique, so a
-// stale record never matches a later capture.
-struct FuseRecord {
-    bool valid = false;
-    unsigned long long id = 0;
-    hipGraphNode_t node = nullptr;
-    int wtype = 0;
-    GemvGroup grp = {};
-    fuse::Group spans;
-};
-thread_local FuseRecord t_fuse;
-
-int block_bytes(int t);
-
-// exactly the calls gemv_launch has a grouped form for (qg_gemv_kernel.hpp)
-bool fuse_candidate(const GemmArgs& g) {
-    return g.batch == 1 && g.ldc_n == 1 && !g.sumi && !g.describe && !g.group && g.ain == AIN_Q8_1 && g.nbw == 0 &&
-           g.lay == LAY_ROWS && g.M <= 4 && g.ldc_m >= 0 && g.ldc_m <= INT32_MAX;
-}
-
-// Shape classes the merge is enabled for, by measurement: tools/ab_capture_fuse.py (64 GEMVs per step on
-// distinct weight copies, merge off vs on in one process, interleaved rounds; us per GEMV, unfused -> fused),
-// profiles/capture_fuse/ab_capture_fuse.txt. Enabled where fused beats unfused by more than the unfused
-// arm's run-to-run spread (0.1 .. 5.4 % of its median):
-//  * the loop-free one-unit form (nf.one; K <= 4096 and the short rows), any M <= 4, any row count. N = K =
-//    4096: Q4_0 M = 1 3.354 -> 1.513, M = 2 3.823 -> 1.661, M = 4 4.517 -> 2.545, Q4_1 3.585 -> 1.682, Q5_0
-//    3.878 -> 1.833, Q5_1 3.958 -> 2.006, Q8_0 4.611 -> 2.757; K = 2048 2.559 -> 0.771. More than one
-//    dispatch round: Q4_0 N = 11008 6.598 -> 4.032, N = 14336 7.627 -> 5.228 (M = 2 8.189 -> 6.055), N = 32000
-//    M = 1 12.491 -> 11.405, M = 2 15.000 -> 13.000, M = 4 24.757 -> 20.039, Q8_0 N = 32000 22.433 -> 21.238.
-//  * the unit loop (K > 4096, K = 3072) at M = 1 (the grouped kernel loops where the Q4_0 single launch is
-//    multi-unit): Q4_0 K = 3072 3.102 -> 1.156, K = 8192 4.891 -> 2.925, K = 11008 6.213 -> 3.953, K = 14336
-//    7.709 -> 5.147; K = 14336 Q4_1 8.122 -> 5.700, Q5_1 10.893 -> 6.979, Q8_0 12.470 -> 9.597.
-// Not merged: the unit loop at M >= 2. N = 4096, K = 14336: M = 2 8.720 -> 8.839, M = 3 10.111 -> 14.542,
-// M = 4 10.819 -> 28.244 (the grouped unit loop at M tiles of 4 spills); M = 2 wins at K = 8192 (5.823 ->
-// 3.815), K = 11008 (7.086 -> 6.021) and N = 8192, K = 14336 (15.654 -> 12.437), but the class is not a win
-// throughout, so it stays off. M = 3 is not measured in the one-unit form (it runs the M = 4 instantiation).
-bool fuse_class_enabled(const GemvNodeFill& nf, int M, int mode) {
-    if (mode == 2) return true;
-    return nf.one || M == 1;
-}
-
-hipError_t capture_gemv(const GemmArgs& g, hipStream_t st) {
-    FuseRecord& r = t_fuse;
-    unsigned long long id = 0;
-    const hipGraphNode_t* deps = nullptr;
-    size_t nd = 0;
-    auto capturing = [&]() {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        hipGraph_t graph = nullptr;
-        if (hipStreamGetCaptureInfo_v2(st, &cs, &id, &graph, &deps, &nd) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        return cs == hipStreamCaptureStatusActive;
-    };
-    if (!capturing()) {
-        r.valid = false;
-        return launch_gemv(g, st);
-    }
-    const int mode = fuse_mode();
-    const fuse::ItemSpans sp = fuse::item_spans(g.A, g.B, g.C, g.M, g.N, g.K, g.ldc_m, block_bytes(g.wtype));
-    if (mode && r.valid && r.id == id && nd == 1 && deps[0] == r.node && r.grp.M == g.M && r.grp.K == g.K &&
-        r.wtype == g.wtype && r.grp.count < GEMV_GROUP_MAX && fuse::can_join(r.spans, sp)) {
-        GemvGroup grp = r.grp;
-        grp.it[grp.count++] = GemvItemDesc{g.A, g.B, g.C, g.N, (int)g.ldc_m};
-        int maxn = 0;
-        for (int i = 0; i < grp.count; ++i) maxn = std::max(maxn, grp.it[i].N);
-        GemvNodeFill nf;
-        GemmArgs q = g;
-        q.A = grp.it[0].A; q.B = grp.it[0].B; q.C = grp.it[0].C; q.N = maxn; q.ldc_m = grp.it[0].ldc;
-        q.group = &grp;
-        q.node_fill = &nf;
-        nf.p = hipKernelNodeParams{};
-        hipError_t e = launch_gemv(q, st);  // launches nothing: the grouped launch's kernel, grid, block, LDS
-        if (e == hipSuccess && !(nf.p.func && fuse_class_enabled(nf, g.M, mode))) e = hipErrorNotSupported;
-        if (e == hipSuccess) e = hipGraphKernelNodeSetParams(r.node, &nf.p);
-        if (e == hipSuccess) {
-            r.grp = grp;
-            fuse::join(r.spans, sp);
-            g_fuse_merged.fetch_add(1, std::memory_order_relaxed);
-            return hipSuccess;
-        }
-        (void)hipGetLastError();
-    }
-    r.valid = false;
-    const hipError_t e = launch_gemv(g, st);
-    if (e != hipSuccess) return e;
-    g_fuse_nodes.fetch_add(1, std::memory_order_relaxed);
-    // exactly one dependency now: the node just created
-    if (capturing() && nd == 1) {
-        r.valid = true;
-        r.id = id;
-        r.node = deps[0];
-        r.wtype = g.wtype;
-        r.grp = GemvGroup{};
-        r.grp.count = 1; r.grp.M = g.M; r.grp.K = g.K;
-        r.grp.it[0] = GemvItemDesc{g.A, g.B, g.C, g.N, (int)g.ldc_m};
-        r.spans.count = 0;
-        fuse::join(r.spans, sp);
-    }
-    return hipSuccess;
-}
-
-int run_gemm(GemmArgs& g, int algo, hipStream_t st) {
-    if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
-    if (g.K <= 0 || g.K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(g.wtype)) return QG_ERR_UNSUPPORTED;
-    if (g.M == 0 || g.N == 0) return QG_OK;
-    if (!g.A || !g.B || (!g.C && !g.sumi)) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)g.B & 1) != 0) return QG_ERR_ALIGN;  // fp16 fields: 2-byte alignment is the floor
+// The 32-element families (Q4_0 .. Q8_0) after the precheck.
+int run_q32(GemmArgs& g, int algo, hipStream_t st) {
     if (g.batch < 0) return QG_ERR_INVALID_ARG;
     if (g.batch == 0) return QG_OK;
     if (g.batch > 1 && (((uintptr_t)g.sB & 1) != 0 || (g.sA & 3) != 0)) return QG_ERR_ALIGN;
@@ -305,8 +132,8 @@ int run_gemm(GemmArgs& g, int algo, hipStream_t st) {
             algo = QG_ALGO_GENERIC;  // batch strides break the vector-load alignment: per-item path
         } else {
             if (g.batch > 65535) return QG_ERR_INVALID_ARG;
-            // under stream capture, consecutive independent GEMVs become one grouped node (capture_gemv)
-            return hip_status(fuse_candidate(g) ? capture_gemv(g, st) : launch_gemv(g, st));
+            // under stream capture, consecutive independent GEMVs become one grouped node (qg_capture_fuse.hip)
+            return hip_status(launch_or_merge_gemv(g, st));
         }
     }
     // MFMA on a shape the kernel cannot address directly (odd K / 32, 2-B aligned weights): through
@@ -338,22 +165,11 @@ int run_gemm(GemmArgs& g, int algo, hipStream_t st) {
             algo = QG_ALGO_GENERIC;
         }
     }
+    const auto launch = algo == QG_ALGO_MFMA ? launch_mfma : algo == QG_ALGO_RAGGED ? launch_ragged
+                        : algo == QG_ALGO_GENERIC ? launch_generic : nullptr;
+    if (!launch) return QG_ERR_INVALID_ARG;
     for (int i = 0; i < g.batch; ++i) {
-        const GemmArgs gi = item(i);
-        int rc;
-        switch (algo) {
-            case QG_ALGO_MFMA:
-                rc = hip_status(launch_mfma(gi, st));
-                break;
-            case QG_ALGO_RAGGED:
-                rc = hip_status(launch_ragged(gi, st));
-                break;
-            case QG_ALGO_GENERIC:
-                rc = hip_status(launch_generic(gi, st));
-                break;
-            default:
-                return QG_ERR_INVALID_ARG;
-        }
+        const int rc = hip_status(launch(item(i), st));
         if (rc != QG_OK) return rc;
     }
     return QG_OK;
@@ -370,17 +186,32 @@ int select_algo_q4k(const GemmArgs& g) {
     return g.M <= QG_Q4K_GEMV_MAXM && q4k_gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
 }
 
+// Q4_K after the precheck.
 int run_q4k(GemmArgs& g, int algo, hipStream_t st) {
-    if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
-    if (g.K <= 0 || g.K % 256 != 0) return QG_ERR_BAD_K;
-    if (g.M == 0 || g.N == 0) return QG_OK;
-    if (!g.A || !g.B || (!g.C && !g.sumi)) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return QG_ERR_ALIGN;
     if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
     if (algo == QG_ALGO_AUTO) algo = select_algo_q4k(g);
     if (algo == QG_ALGO_GEMV) return q4k_gemv_eligible(g) ? hip_status(launch_q4k_gemv(g, st)) : QG_ERR_UNSUPPORTED;
     if (algo == QG_ALGO_MFMA) return q4k_mmq_eligible(g) ? hip_status(launch_q4k_mmq(g, st)) : QG_ERR_UNSUPPORTED;
     return QG_ERR_INVALID_ARG;
+}
+
+// The quantized product: one precheck, then the 32-element families or the Q4_K pair by the weight type's
+// block size. q4k_ok = false: the entries that refuse Q4_K (qg.h) -- it is then a type like any other they do
+// not take, checked at the 32-element granule.
+int run_product(GemmArgs& g, int algo, hipStream_t st, bool q4k_ok = true) {
+    const bool k4 = q4k_ok && is_q4k_type(g.wtype);
+    // 32-element families: fp16 fields, 2-byte alignment is the floor; Q4_K: 16-B super-blocks, 4-B records
+    const int rc = precheck({g.M, g.N}, g.K, k4 ? block_elems(g.wtype) : 32, k4 || is_weight_type(g.wtype),
+                            {{g.A, k4 ? 3u : 0u}, {g.B, k4 ? 15u : 1u}, {out_ptr(g), 0}});
+    if (rc != QG_GO) return rc;
+    return k4 ? run_q4k(g, algo, st) : run_q32(g, algo, st);
+}
+
+// what QG_ALGO_AUTO dispatches to (qg_select_algo): the same routing
+int select_product_algo(const GemmArgs& g) {
+    const bool k4 = is_q4k_type(g.wtype);
+    if (!(k4 || is_weight_type(g.wtype)) || g.K <= 0 || g.K % block_elems(g.wtype) != 0) return -1;
+    return k4 ? select_algo_q4k(g) : select_algo(g);
 }
 
 // The tiled weight layout (qg_tile_weights): the MFMA small-batch decode for M = 3..4 and M = 2 at K/32 > 256
@@ -390,12 +221,8 @@ int run_q4k(GemmArgs& g, int algo, hipStream_t st) {
 // M <= 4 where the MFMA kernel rejects the shape too) return QG_ERR_UNSUPPORTED: the tiled layout has no
 // generic kernel.
 int run_tiled(GemmArgs& g, hipStream_t st) {
-    if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
-    if (g.K <= 0 || g.K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(g.wtype)) return QG_ERR_UNSUPPORTED;
-    if (g.M == 0 || g.N == 0) return QG_OK;
-    if (!g.A || !g.B || (!g.C && !g.sumi)) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 15) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({g.M, g.N}, g.K, 32, is_weight_type(g.wtype), {{g.A, 15}, {g.B, 15}, {out_ptr(g), 0}});
+    if (rc != QG_GO) return rc;
 #ifndef QG_TILED_GEMVM  // (A/B builds: 0 = the round-6 tiled decode GEMV for every M <= 4)
 #define QG_TILED_GEMVM 1
 #endif
@@ -405,39 +232,45 @@ int run_tiled(GemmArgs& g, hipStream_t st) {
     return hip_status(launch_mfma(g, st));
 }
 
-int block_bytes(int t) {
-    switch (t) {
-        case QG_TYPE_Q4_0: return 18;
-        case QG_TYPE_Q4_1: return 20;
-        case QG_TYPE_Q5_0: return 22;
-        case QG_TYPE_Q5_1: return 24;
-        case QG_TYPE_Q8_0: return 34;
-        case QG_TYPE_Q8_1: return 36;
-        case QG_TYPE_Q4_K: return 144;
-    }
-    return 0;
+// The tiled entries (lay = LAY_TILED, LAY_TILED_ACT): the product with an output row stride, the sumi hook
+// and the configuration query.
+int tiled_product(int lay, const void* A, const void* B_tiled, float* C, int M, int N, int K, int64_t ldc, int wtype,
+                  qg_stream_t stream) {
+    if (ldc < N || (M > 1 && ldc <= 0)) return QG_ERR_INVALID_ARG;
+    GemmArgs g = product_args(A, B_tiled, C, M, N, K, wtype);
+    g.ldc_m = (long)ldc;
+    g.lay = lay;
+    return run_tiled(g, (hipStream_t)stream);
 }
 
-int block_elems(int t) { return is_q4k_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
+int tiled_sumi(int lay, const void* A, const void* B_tiled, int32_t* sumi, int M, int N, int K, int wtype,
+               qg_stream_t stream) {
+    GemmArgs g = product_args(A, B_tiled, nullptr, M, N, K, wtype);
+    g.sumi = sumi;
+    g.lay = lay;
+    return run_tiled(g, (hipStream_t)stream);
+}
+
+// qg_debug_config*: the leaf launcher names the kernel into buf and launches nothing
+int describe_product(int lay, int M, int N, int K, int wtype, int algo, int sumi, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    GemmArgs g = query_args(M, N, K, wtype, sumi);
+    g.lay = lay;
+    g.describe = buf; g.describe_len = len;
+    return lay == LAY_ROWS ? run_product(g, algo, nullptr) : run_tiled(g, nullptr);
+}
 
 int weight_major(int wtype, const void* W, const void* A, float* out, int M, int N, int K, qg_stream_t s) {
-    // out[mw][nt] = sum_b dot(W[mw][b], A[nt][b]) -> activation-major (m = nt, n = mw) with
-    // output strides ldc_m = 1, ldc_n = Ntok.
-    GemmArgs g;
-    g.A = A; g.B = W; g.C = out; g.M = N; g.N = M; g.K = K; g.wtype = wtype;
-    g.ldc_m = 1; g.ldc_n = N;
-    return run_gemm(g, QG_ALGO_AUTO, (hipStream_t)s);
+    GemmArgs g = weight_major_args(wtype, W, A, out, M, N, K);
+    return run_product(g, QG_ALGO_AUTO, (hipStream_t)s, false);
 }
+
 int run_w16(int wtype, const float* A, const void* B, float* C, int M, int N, int K, hipStream_t st,
             void* ws = nullptr, size_t ws_bytes = 0) {
-    if (M < 0 || N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (M == 0 || N == 0) return QG_OK;
-    if (!A || !B || !C) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)A & 3) != 0 || ((uintptr_t)B & 1) != 0) return QG_ERR_ALIGN;
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
+    const int rc = precheck({M, N}, K, 32, true, {{A, 3}, {B, 1}, {C, 0}});
+    if (rc != QG_GO) return rc;
+    GemmArgs g = product_args(A, B, C, M, N, K, wtype);
     g.ws = ws; g.ws_bytes = ws_bytes;
     return hip_status(launch_w16(g, st));
 }
@@ -469,6 +302,11 @@ int view_dims(const qg_tensor_view* act, const qg_tensor_view* w, const qg_tenso
     return QG_OK;
 }
 
+// kernel_type of the FP32-activation _from_view entries: NULL or one of the reference's names (all one kernel here)
+bool baseline_kernel_type(const char* kt) {
+    return !kt || strcmp(kt, "naive") == 0 || strcmp(kt, "tiled") == 0 || strcmp(kt, "auto") == 0;
+}
+
 size_t fused_workspace_bytes(int M, int K) { return M > 0 && K > 0 ? (size_t)M * (size_t)(K / 32) * 36 : 0; }
 
 // FP32 / FP16 activations (g.ain != AIN_Q8_1), dense rows of K elements. Small M: quantization
@@ -476,33 +314,17 @@ size_t fused_workspace_bytes(int M, int K) { return M > 0 && K > 0 ? (size_t)M *
 // the Q8_1 product (same bytes, so the same results); without a workspace, fused GEMV launches
 // over row chunks (the weights are streamed once per chunk).
 int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (is_q4k_type(g.wtype)) {
-        // Q4_K has no fused prologue: FP32 rows are quantized into the caller's workspace, then the Q8_1
-        // product runs on it (the same bytes, so the same results as the two calls)
-        if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
-        if (g.K <= 0 || g.K % 256 != 0) return QG_ERR_BAD_K;
-        if (g.M == 0 || g.N == 0) return QG_OK;
-        if (!g.A || !g.B || !g.C) return QG_ERR_INVALID_ARG;
-        if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return QG_ERR_ALIGN;
-        if (g.ain != AIN_F32 || !ws || ws_bytes < fused_workspace_bytes(g.M, g.K)) return QG_ERR_UNSUPPORTED;
-        if (((uintptr_t)ws & 3) != 0) return QG_ERR_ALIGN;
-        const hipError_t e = launch_quantize(QG_TYPE_Q8_1, 0, (const float*)g.A, ws, (int64_t)g.M * (g.K / 32), st);
-        if (e != hipSuccess) return hip_status(e);
-        g.ain = AIN_Q8_1;
-        g.A = ws;
-        return run_q4k(g, QG_ALGO_AUTO, st);
-    }
-    if (g.M < 0 || g.N < 0) return QG_ERR_INVALID_ARG;
-    if (g.K <= 0 || g.K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(g.wtype)) return QG_ERR_UNSUPPORTED;
-    if (g.M == 0 || g.N == 0) return QG_OK;
-    if (!g.A || !g.B || !g.C) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)g.B & 1) != 0) return QG_ERR_ALIGN;
+    const bool k4 = is_q4k_type(g.wtype);
     const size_t es = g.ain == AIN_F32 ? 4 : 2;
-    if (((uintptr_t)g.A & (es - 1)) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({g.M, g.N}, g.K, k4 ? block_elems(g.wtype) : 32, k4 || is_weight_type(g.wtype),
+                            {{g.A, k4 ? 3 : es - 1}, {g.B, k4 ? 15u : 1u}, {g.C, 0}});
+    if (rc != QG_GO) return rc;
     const bool vec_ok = ((uintptr_t)g.A & 15) == 0;
-    if (g.M <= 4 && vec_ok && gemv_eligible(g)) return hip_status(launch_gemv(g, st));
-    if (ws && ws_bytes >= fused_workspace_bytes(g.M, g.K)) {
+    const bool ws_ok = ws && ws_bytes >= fused_workspace_bytes(g.M, g.K);
+    // Q4_K has no fused prologue: only FP32 rows through the caller's workspace, then the Q8_1 product on it
+    if (k4 && (g.ain != AIN_F32 || !ws_ok)) return QG_ERR_UNSUPPORTED;
+    if (!k4 && g.M <= 4 && vec_ok && gemv_eligible(g)) return hip_status(launch_gemv(g, st));
+    if (ws_ok) {
         if (((uintptr_t)ws & 3) != 0) return QG_ERR_ALIGN;
         const int64_t nblocks = (int64_t)g.M * (g.K / 32);
         const hipError_t e = g.ain == AIN_F32 ? launch_quantize(QG_TYPE_Q8_1, 0, (const float*)g.A, ws, nblocks, st)
@@ -511,7 +333,7 @@ int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
         GemmArgs q = g;
         q.ain = AIN_Q8_1;
         q.A = ws;
-        return run_gemm(q, QG_ALGO_AUTO, st);
+        return run_product(q, QG_ALGO_AUTO, st);
     }
     if (!vec_ok) return QG_ERR_ALIGN;
     for (int rows : {8, 4, 2, 1}) {
@@ -570,18 +392,15 @@ int qg_gemm_q4_0_fp32(const void* weight_q4_0, const float* activation, float* o
 
 int qg_gemm_w4a8_f32(const float* X, const void* B, float* C, int M, int N, int K, int wtype, void* workspace,
                      size_t workspace_bytes, qg_stream_t stream) {
-    GemmArgs g;
-    g.A = X; g.ain = AIN_F32; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
+    GemmArgs g = product_args(X, B, C, M, N, K, wtype);
+    g.ain = AIN_F32;
     return run_fused(g, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int qg_gemm_q4_0_fp16_fused_ws(const void* W, const void* act_f16, float* out, int M, int N, int K, void* workspace,
                                size_t workspace_bytes, qg_stream_t stream) {
-    // Weight-major (M weight rows, N tokens) -> activation-major args, as weight_major().
-    GemmArgs g;
-    g.A = act_f16; g.ain = AIN_F16_FUSED; g.B = W; g.C = out; g.M = N; g.N = M; g.K = K; g.wtype = QG_TYPE_Q4_0;
-    g.ldc_m = 1; g.ldc_n = N;
+    GemmArgs g = weight_major_args(QG_TYPE_Q4_0, W, act_f16, out, M, N, K);
+    g.ain = AIN_F16_FUSED;
     return run_fused(g, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -590,45 +409,35 @@ int qg_gemm_q4_0_fp16_fused(const void* W, const void* act_f16, float* out, int 
 }
 
 int qg_quantize_q8_1_f16_fused(const void* x, void* y, int64_t k, qg_stream_t stream) {
-    if (k < 0 || k % 32 != 0) return QG_ERR_BAD_K;
-    if (k == 0) return QG_OK;
-    if (!x || !y) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)x & 1) != 0 || ((uintptr_t)y & 3) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck_count(k, 32, true, {{x, 1}, {y, 3}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_quantize_f16_fused(x, y, k / 32, (hipStream_t)stream));
 }
 
 int qg_gemm_w4a8_ex(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int algo,
                     qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
-    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
-    return run_gemm(g, algo, (hipStream_t)stream);
+    GemmArgs g = product_args(A, B, C, M, N, K, wtype);
+    return run_product(g, algo, (hipStream_t)stream);
 }
 
 int qg_gemm_w4a8_strided_batched(const void* A, int64_t strideA, const void* B, int64_t strideB, float* C,
                                  int64_t strideC, int batch, int M, int N, int K, int wtype, qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
+    GemmArgs g = product_args(A, B, C, M, N, K, wtype);
     g.batch = batch; g.sA = strideA; g.sB = strideB; g.sC = strideC;
-    return run_gemm(g, QG_ALGO_AUTO, (hipStream_t)stream);
+    return run_product(g, QG_ALGO_AUTO, (hipStream_t)stream, false);
 }
 
 size_t qg_gemm_w4a8_workspace_size(int M, int N, int K, int wtype) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || !is_weight_type(wtype)) return 0;
-    GemmArgs g;
-    g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
+    const GemmArgs g = query_args(M, N, K, wtype);
     return repack_eligible(g) ? repack_workspace_bytes(g) : 0;
 }
 
 int qg_gemm_w4a8_ws(const void* A, const void* B, float* C, int M, int N, int K, int wtype, void* workspace,
                     size_t workspace_bytes, qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
+    GemmArgs g = product_args(A, B, C, M, N, K, wtype);
     g.ws = workspace; g.ws_bytes = workspace_bytes;
-    return run_gemm(g, QG_ALGO_AUTO, (hipStream_t)stream);
+    return run_product(g, QG_ALGO_AUTO, (hipStream_t)stream, false);
 }
 
 size_t qg_repack_weights_bytes(int N, int K, int wtype) {
@@ -637,32 +446,24 @@ size_t qg_repack_weights_bytes(int N, int K, int wtype) {
 }
 
 int qg_repack_weights(const void* B, void* B_packed, int N, int K, int wtype, qg_stream_t stream) {
-    if (N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(wtype)) return QG_ERR_UNSUPPORTED;
-    if (N == 0) return QG_OK;
-    if (!B || !B_packed) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)B & 1) != 0 || ((uintptr_t)B_packed & 15) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({N}, K, 32, is_weight_type(wtype), {{B, 1}, {B_packed, 15}});
+    if (rc != QG_GO) return rc;
     const int bb = block_bytes(wtype);
     return hip_status(launch_pad_rows(B, B_packed, N, (K / 32) * bb, padded_blocks(K) * bb, (hipStream_t)stream));
 }
 
 int qg_quantize_q8_1_padded(const float* x, void* y, int M, int K, qg_stream_t stream) {
-    if (M < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (M == 0) return QG_OK;
-    if (!x || !y) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)x & 3) != 0 || ((uintptr_t)y & 3) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({M}, K, 32, true, {{x, 3}, {y, 3}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_quantize_q8_1_padded(x, y, M, K / 32, padded_blocks(K), (hipStream_t)stream));
 }
 
 int qg_gemm_w4a8_padded(const void* A_padded, const void* B_packed, float* C, int M, int N, int K, int wtype,
                         qg_stream_t stream) {
+    // by hand: the logical K is checked before anything (M = -1, K = 33 is BAD_K here), the product sees K'
     if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    GemmArgs g;
-    g.A = A_padded; g.B = B_packed; g.C = C; g.M = M; g.N = N; g.K = padded_blocks(K) * 32; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
-    return run_gemm(g, QG_ALGO_AUTO, (hipStream_t)stream);
+    GemmArgs g = product_args(A_padded, B_packed, C, M, N, padded_blocks(K) * 32, wtype);
+    return run_product(g, QG_ALGO_AUTO, (hipStream_t)stream, false);
 }
 
 size_t qg_gemm_w4a8_prepacked_workspace_size(int M, int K) {
@@ -672,16 +473,12 @@ size_t qg_gemm_w4a8_prepacked_workspace_size(int M, int K) {
 
 int qg_gemm_w4a8_prepacked(const void* A, const void* B_packed, float* C, int M, int N, int K, int wtype,
                            void* workspace, size_t workspace_bytes, qg_stream_t stream) {
-    if (M < 0 || N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(wtype)) return QG_ERR_UNSUPPORTED;
-    if (M == 0 || N == 0) return QG_OK;
-    if (!A || !B_packed || !C) return QG_ERR_INVALID_ARG;
+    // (alignment is left to the route taken below: the MFMA kernel's eligibility, the pad copy, run_product)
+    const int rc = precheck({M, N}, K, 32, is_weight_type(wtype), {{A, 0}, {B_packed, 0}, {C, 0}});
+    if (rc != QG_GO) return rc;
     const hipStream_t st = (hipStream_t)stream;
     const int nbp = padded_blocks(K);
-    GemmArgs g;
-    g.A = A; g.B = B_packed; g.C = C; g.M = M; g.N = N; g.K = nbp * 32; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
+    GemmArgs g = product_args(A, B_packed, C, M, N, nbp * 32, wtype);
     if (nbp != K / 32) {
         // round 5: where the MFMA kernel runs (M >= 5), it reads the plain activation rows itself
         // (activation windows against the padded weight rows, qg_mmq_kernel.hpp AW): one launch, no
@@ -697,7 +494,7 @@ int qg_gemm_w4a8_prepacked(const void* A, const void* B_packed, float* C, int M,
         if (e != hipSuccess) return hip_status(e);
         g.A = workspace;
     }
-    return run_gemm(g, QG_ALGO_AUTO, st);
+    return run_product(g, QG_ALGO_AUTO, st, false);
 }
 
 size_t qg_tile_weights_bytes(int N, int K, int wtype) {
@@ -706,23 +503,14 @@ size_t qg_tile_weights_bytes(int N, int K, int wtype) {
 }
 
 int qg_tile_weights(const void* B, void* B_tiled, int N, int K, int wtype, qg_stream_t stream) {
-    if (N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (!is_weight_type(wtype)) return QG_ERR_UNSUPPORTED;
-    if (N == 0) return QG_OK;
-    if (!B || !B_tiled) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)B & 1) != 0 || ((uintptr_t)B_tiled & 15) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({N}, K, 32, is_weight_type(wtype), {{B, 1}, {B_tiled, 15}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_tile_weights(B, B_tiled, N, K, wtype, (hipStream_t)stream));
 }
 
 int qg_gemm_w4a8_tiled_ldc(const void* A, const void* B_tiled, float* C, int M, int N, int K, int64_t ldc, int wtype,
                            qg_stream_t stream) {
-    if (ldc < N || (M > 1 && ldc <= 0)) return QG_ERR_INVALID_ARG;
-    GemmArgs g;
-    g.A = A; g.B = B_tiled; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = (long)ldc; g.ldc_n = 1;
-    g.lay = LAY_TILED;
-    return run_tiled(g, (hipStream_t)stream);
+    return tiled_product(LAY_TILED, A, B_tiled, C, M, N, K, ldc, wtype, stream);
 }
 
 int qg_gemm_w4a8_tiled(const void* A, const void* B_tiled, float* C, int M, int N, int K, int wtype, qg_stream_t stream) {
@@ -731,24 +519,11 @@ int qg_gemm_w4a8_tiled(const void* A, const void* B_tiled, float* C, int M, int 
 
 int qg_debug_sumi_tiled(const void* A, const void* B_tiled, int32_t* sumi, int M, int N, int K, int wtype,
                         qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A; g.B = B_tiled; g.sumi = sumi; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
-    g.lay = LAY_TILED;
-    return run_tiled(g, (hipStream_t)stream);
+    return tiled_sumi(LAY_TILED, A, B_tiled, sumi, M, N, K, wtype, stream);
 }
 
 int qg_debug_config_tiled(int M, int N, int K, int wtype, int sumi, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    GemmArgs g;
-    g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    if (sumi) g.sumi = (int32_t*)256;
-    else g.C = (float*)256;
-    g.ldc_m = N; g.ldc_n = 1;
-    g.lay = LAY_TILED;
-    g.describe = buf; g.describe_len = len;
-    return run_tiled(g, nullptr);
+    return describe_product(LAY_TILED, M, N, K, wtype, QG_ALGO_AUTO, sumi, buf, len);
 }
 
 // ---- round 5: tiled activations (LAY_TILED_ACT) -------------------------------------------------------
@@ -758,31 +533,20 @@ size_t qg_activations_tiled_bytes(int M, int K) {
 }
 
 int qg_quantize_q8_1_tiled(const float* x, void* A_tiled, int M, int K, qg_stream_t stream) {
-    if (M < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (M == 0) return QG_OK;
-    if (!x || !A_tiled) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)x & 15) != 0 || ((uintptr_t)A_tiled & 15) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({M}, K, 32, true, {{x, 15}, {A_tiled, 15}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_quantize_q8_1_tiled(x, A_tiled, M, K, (hipStream_t)stream));
 }
 
 int qg_tile_activations(const void* A_q8_1, void* A_tiled, int M, int K, qg_stream_t stream) {
-    if (M < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
-    if (M == 0) return QG_OK;
-    if (!A_q8_1 || !A_tiled) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)A_q8_1 & 3) != 0 || ((uintptr_t)A_tiled & 15) != 0) return QG_ERR_ALIGN;
+    const int rc = precheck({M}, K, 32, true, {{A_q8_1, 3}, {A_tiled, 15}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_tile_activations(A_q8_1, A_tiled, M, K, (hipStream_t)stream));
 }
 
 int qg_gemm_w4a8_tiled_act_ldc(const void* A_tiled, const void* B_tiled, float* C, int M, int N, int K, int64_t ldc, int wtype,
                                qg_stream_t stream) {
-    if (ldc < N || (M > 1 && ldc <= 0)) return QG_ERR_INVALID_ARG;
-    GemmArgs g;
-    g.A = A_tiled; g.B = B_tiled; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = (long)ldc; g.ldc_n = 1;
-    g.lay = LAY_TILED_ACT;
-    return run_tiled(g, (hipStream_t)stream);
+    return tiled_product(LAY_TILED_ACT, A_tiled, B_tiled, C, M, N, K, ldc, wtype, stream);
 }
 
 int qg_gemm_w4a8_tiled_act(const void* A_tiled, const void* B_tiled, float* C, int M, int N, int K, int wtype,
@@ -792,35 +556,23 @@ int qg_gemm_w4a8_tiled_act(const void* A_tiled, const void* B_tiled, float* C, i
 
 int qg_debug_sumi_tiled_act(const void* A_tiled, const void* B_tiled, int32_t* sumi, int M, int N, int K, int wtype,
                             qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A_tiled; g.B = B_tiled; g.sumi = sumi; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
-    g.lay = LAY_TILED_ACT;
-    return run_tiled(g, (hipStream_t)stream);
+    return tiled_sumi(LAY_TILED_ACT, A_tiled, B_tiled, sumi, M, N, K, wtype, stream);
 }
 
 int qg_debug_config_tiled_act(int M, int N, int K, int wtype, int sumi, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    GemmArgs g;
-    g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    if (sumi) g.sumi = (int32_t*)256;
-    else g.C = (float*)256;
-    g.ldc_m = N; g.ldc_n = 1;
-    g.lay = LAY_TILED_ACT;
-    g.describe = buf; g.describe_len = len;
-    return run_tiled(g, nullptr);
+    return describe_product(LAY_TILED_ACT, M, N, K, wtype, QG_ALGO_AUTO, sumi, buf, len);
 }
 
 int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, qg_stream_t stream) {
+    // by hand: the items pointer is checked with the sizes, and M == 0 is a no-op only after every item's sizes
+    // and pointers have been checked (below)
     if (count < 0 || M < 0 || (count > 0 && !items)) return QG_ERR_INVALID_ARG;
     if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
     if (!is_weight_type(wtype)) return QG_ERR_UNSUPPORTED;
     const hipStream_t st = (hipStream_t)stream;
     auto item_args = [&](const qg_gemv_item& it) {
-        GemmArgs g;
-        g.A = it.A_q8_1; g.B = it.B; g.C = it.C; g.M = M; g.N = it.N; g.K = K; g.wtype = wtype;
-        g.ldc_m = it.ldc ? it.ldc : it.N; g.ldc_n = 1;
+        GemmArgs g = product_args(it.A_q8_1, it.B, it.C, M, it.N, K, wtype);
+        if (it.ldc) g.ldc_m = it.ldc;
         return g;
     };
     // validate every item before anything is enqueued; one launch only if AUTO picks the GEMV for all
@@ -839,7 +591,7 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
         for (int i = 0; i < count; ++i) {
             if (items[i].N == 0) continue;
             GemmArgs g = item_args(items[i]);
-            const int rc = run_gemm(g, QG_ALGO_AUTO, st);
+            const int rc = run_product(g, QG_ALGO_AUTO, st, false);
             if (rc != QG_OK) return rc;
         }
         return QG_OK;
@@ -847,19 +599,13 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
     for (int i0 = 0; i0 < count;) {
         GemvGroup grp = {};
         grp.M = M; grp.K = K;
-        int maxn = 0;
         for (; i0 < count && grp.count < GEMV_GROUP_MAX; ++i0) {
             const qg_gemv_item& it = items[i0];
             if (it.N == 0) continue;
             grp.it[grp.count++] = GemvItemDesc{it.A_q8_1, it.B, it.C, it.N, it.ldc ? it.ldc : it.N};
-            maxn = std::max(maxn, it.N);
         }
         if (grp.count == 0) break;
-        GemmArgs g;
-        g.A = grp.it[0].A; g.B = grp.it[0].B; g.C = grp.it[0].C; g.M = M; g.N = maxn; g.K = K; g.wtype = wtype;
-        g.ldc_m = grp.it[0].ldc; g.ldc_n = 1;
-        g.group = &grp;
-        const int rc = hip_status(launch_gemv(g, st));
+        const int rc = hip_status(launch_gemv(group_args(grp, wtype), st));
         if (rc != QG_OK) return rc;
     }
     return QG_OK;
@@ -895,16 +641,11 @@ int qg_gemm_w8a8(const void* A, const void* B, float* C, int M, int N, int K, qg
 }
 
 int qg_quantize(int type, int variant, const float* x, void* y, int64_t k, qg_stream_t stream) {
-    if (k < 0 || k % 32 != 0) return QG_ERR_BAD_K;
-    if (block_bytes(type) == 0 || is_q4k_type(type)) return QG_ERR_UNSUPPORTED;  // (no Q4_K quantizer)
-    if (variant != 0 && !(variant == 1 && type == QG_TYPE_Q8_1) &&
-        !(variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0)))
-        return QG_ERR_UNSUPPORTED;
-    if (k == 0) return QG_OK;
-    if (!x || !y) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)x & 3) != 0) return QG_ERR_ALIGN;
-    const uintptr_t need = type == QG_TYPE_Q8_1 ? 3 : 1;
-    if (((uintptr_t)y & need) != 0) return QG_ERR_ALIGN;
+    const bool type_ok = block_bytes(type) != 0 && !is_q4k_type(type);  // (no Q4_K quantizer)
+    const bool variant_ok = variant == 0 || (variant == 1 && type == QG_TYPE_Q8_1) ||
+                            (variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0));
+    const int rc = precheck_count(k, 32, type_ok && variant_ok, {{x, 3}, {y, type == QG_TYPE_Q8_1 ? 3u : 1u}});
+    if (rc != QG_GO) return rc;
     return hip_status(launch_quantize(type, variant, x, y, k / 32, (hipStream_t)stream));
 }
 
@@ -918,18 +659,10 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 }
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
-    if (is_q4k_type(type)) {
-        if (k < 0 || k % 256 != 0) return QG_ERR_BAD_K;
-        if (k == 0) return QG_OK;
-        if (!x || !y) return QG_ERR_INVALID_ARG;
-        if (((uintptr_t)y & 3) != 0 || ((uintptr_t)x & 1) != 0) return QG_ERR_ALIGN;
-        return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
-    }
-    if (k < 0 || k % 32 != 0) return QG_ERR_BAD_K;
-    if (block_bytes(type) == 0) return QG_ERR_UNSUPPORTED;
-    if (k == 0) return QG_OK;
-    if (!x || !y) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)y & 3) != 0 || ((uintptr_t)x & 1) != 0) return QG_ERR_ALIGN;
+    const int be = is_q4k_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
+    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, 1}, {y, 3}});
+    if (rc != QG_GO) return rc;
+    if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));
 }
 
@@ -937,35 +670,21 @@ int qg_dequantize_q4_0(const void* x, float* y, int64_t k, qg_stream_t s) { retu
 
 int qg_debug_sumi(const void* A, const void* B, int32_t* sumi, int M, int N, int K, int wtype, int algo,
                   qg_stream_t stream) {
-    GemmArgs g;
-    g.A = A; g.B = B; g.sumi = sumi; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = N; g.ldc_n = 1;
-    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
-    return run_gemm(g, algo, (hipStream_t)stream);
+    GemmArgs g = product_args(A, B, nullptr, M, N, K, wtype);
+    g.sumi = sumi;
+    return run_product(g, algo, (hipStream_t)stream);
 }
 
 int qg_debug_config(int M, int N, int K, int wtype, int algo, int sumi, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    // 256-B aligned stand-in pointers: the shape decides, as for a real call on aligned buffers
-    GemmArgs g;
-    g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    if (sumi) g.sumi = (int32_t*)256;
-    else g.C = (float*)256;
-    g.ldc_m = N; g.ldc_n = 1;
-    g.describe = buf; g.describe_len = len;
-    if (is_q4k_type(wtype)) return run_q4k(g, algo, nullptr);
-    return run_gemm(g, algo, nullptr);
+    return describe_product(LAY_ROWS, M, N, K, wtype, algo, sumi, buf, len);
 }
 
 int qg_gemm_w4a8_ldc(const void* A, const void* B, float* C, int M, int N, int K, int64_t ldc, int wtype, int algo,
                      qg_stream_t stream) {
     if (ldc < N || (M > 1 && ldc <= 0)) return QG_ERR_INVALID_ARG;
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    g.ldc_m = (long)ldc; g.ldc_n = 1;
-    if (is_q4k_type(wtype)) return run_q4k(g, algo, (hipStream_t)stream);
-    return run_gemm(g, algo, (hipStream_t)stream);
+    GemmArgs g = product_args(A, B, C, M, N, K, wtype);
+    g.ldc_m = (long)ldc;
+    return run_product(g, algo, (hipStream_t)stream);
 }
 
 int qg_gemm_w4a8_from_view(const qg_tensor_view* act, const qg_tensor_view* w, qg_tensor_view* out,
@@ -994,9 +713,7 @@ int qg_gemm_w4a8_from_view(const qg_tensor_view* act, const qg_tensor_view* w, q
 int qg_gemm_w4a16_from_view(const qg_tensor_view* act, const qg_tensor_view* w, qg_tensor_view* out,
                             const char* kernel_type, qg_stream_t stream) {
     if (!act || !w || !out) return QG_ERR_INVALID_ARG;
-    if (kernel_type && strcmp(kernel_type, "naive") != 0 && strcmp(kernel_type, "tiled") != 0 &&
-        strcmp(kernel_type, "auto") != 0)
-        return QG_ERR_INVALID_ARG;
+    if (!baseline_kernel_type(kernel_type)) return QG_ERR_INVALID_ARG;
     if (act->type != QG_TYPE_F32 || out->type != QG_TYPE_F32 || (w->type != QG_TYPE_Q4_0 && w->type != QG_TYPE_Q8_0))
         return QG_ERR_UNSUPPORTED;
     int64_t M, N, K;
@@ -1009,9 +726,7 @@ int qg_gemm_w4a16_from_view(const qg_tensor_view* act, const qg_tensor_view* w, 
 int qg_gemm_fp32_from_view(const qg_tensor_view* act, const qg_tensor_view* w, qg_tensor_view* out,
                            const char* kernel_type, qg_stream_t stream) {
     if (!act || !w || !out) return QG_ERR_INVALID_ARG;
-    if (kernel_type && strcmp(kernel_type, "naive") != 0 && strcmp(kernel_type, "tiled") != 0 &&
-        strcmp(kernel_type, "auto") != 0)
-        return QG_ERR_INVALID_ARG;
+    if (!baseline_kernel_type(kernel_type)) return QG_ERR_INVALID_ARG;
     if (act->type != QG_TYPE_F32 || out->type != QG_TYPE_F32 || w->type != QG_TYPE_F32) return QG_ERR_UNSUPPORTED;
     int64_t M, N, K;
     const int rc = view_dims(act, w, out, M, N, K, 1);
@@ -1027,13 +742,11 @@ int qg_validate_view_types(const qg_tensor_view* act, const qg_tensor_view* w, c
 }
 
 int qg_gemm_fp32(const float* A, const float* B, float* C, int M, int N, int K, qg_stream_t stream) {
-    if (M < 0 || N < 0 || K < 0) return QG_ERR_INVALID_ARG;
-    if (M == 0 || N == 0) return QG_OK;
-    if (!A || !B || !C) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)A & 3) != 0 || ((uintptr_t)B & 3) != 0 || ((uintptr_t)C & 3) != 0) return QG_ERR_ALIGN;
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
-    g.ldc_m = N; g.ldc_n = 1;
+    // no K granule, and K = 0 is a product (of nothing), not an empty call: K is checked here, the rest as everywhere
+    if (K < 0) return QG_ERR_INVALID_ARG;
+    const int rc = precheck({M, N}, 1, 1, true, {{A, 3}, {B, 3}, {C, 3}});
+    if (rc != QG_GO) return rc;
+    GemmArgs g = product_args(A, B, C, M, N, K, 0);
     return hip_status(launch_fp32(g, (hipStream_t)stream));
 }
 
@@ -1051,19 +764,12 @@ const char* qg_status_string(int s) {
 
 int qg_last_hip_error(void) { return g_last_hip; }
 
-void qg_set_capture_fusion(int on) { g_fuse_mode.store(on == 2 ? 2 : on ? 1 : 0, std::memory_order_relaxed); }
+void qg_set_capture_fusion(int on) { set_capture_fusion(on); }
 
-void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes) {
-    if (merged) *merged = g_fuse_merged.load(std::memory_order_relaxed);
-    if (nodes) *nodes = g_fuse_nodes.load(std::memory_order_relaxed);
-}
+void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes) { capture_fusion_stats(merged, nodes); }
 
 int qg_select_algo(int M, int N, int K, int wtype) {
-    GemmArgs g;
-    g.A = (const void*)256; g.B = (const void*)256; g.M = M; g.N = N; g.K = K; g.wtype = wtype;
-    if (is_q4k_type(wtype)) return K > 0 && K % 256 == 0 ? select_algo_q4k(g) : -1;
-    if (K <= 0 || K % 32 != 0 || !is_weight_type(wtype)) return -1;
-    return select_algo(g);
+    return select_product_algo(query_args(M, N, K, wtype));
 }
 
 int qg_block_bytes(int type) { return block_bytes(type); }

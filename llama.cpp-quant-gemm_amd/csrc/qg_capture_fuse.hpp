@@ -1,4 +1,4 @@
-// qg_capture_fuse.hpp — the hazard test of the capture-time GEMV merge (qg_api.hip, capture_gemv).
+// qg_capture_fuse.hpp — the hazard test of the capture-time GEMV merge (qg_capture_fuse.hip, capture_gemv).
 //
 // Under stream capture, a GEMV whose only capture dependency is a GEMV node this library created is
 // merged into that node (one grouped launch, gemvg_kernel) when it is independent of the node's items.
@@ -20,7 +20,7 @@
 namespace qg {
 namespace fuse {
 
-constexpr int MAX_ITEMS = 64;  // == GEMV_GROUP_MAX (qg_kernels.hpp; static_assert in qg_api.hip)
+constexpr int MAX_ITEMS = 64;  // == GEMV_GROUP_MAX (qg_kernels.hpp; static_assert in qg_capture_fuse.hip)
 
 struct Span {
     uintptr_t lo, hi;  // [lo, hi)

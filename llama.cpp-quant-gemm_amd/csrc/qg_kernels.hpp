@@ -1,4 +1,5 @@
-// qg_kernels.hpp — host-side view of the kernel families behind the C-ABI (qg_api.hip).
+// qg_kernels.hpp — host-side view of the kernel families behind the C-ABI (qg_api.hip), and of what they share
+// (qg_workspace.hip, qg_capture_fuse.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,8 +59,18 @@ struct GemvGroup {
     int count, M, K, full;
     GemvItemDesc it[GEMV_GROUP_MAX];
 };
+// The grouped launch's arguments (qg_gemm_w4a8_grouped and the capture-time merge): the first item's pointers,
+// N = the largest item's, `group` pointing at grp (which must outlive the launch call).
+inline GemmArgs group_args(const GemvGroup& grp, int wtype) {
+    GemmArgs g;
+    g.A = grp.it[0].A; g.B = grp.it[0].B; g.C = grp.it[0].C; g.M = grp.M; g.K = grp.K; g.wtype = wtype;
+    for (int i = 0; i < grp.count; ++i) g.N = grp.it[i].N > g.N ? grp.it[i].N : g.N;
+    g.ldc_m = grp.it[0].ldc; g.ldc_n = 1;
+    g.group = &grp;
+    return g;
+}
 // What the grouped launcher would launch (GemmArgs::node_fill), as the parameters of a graph kernel
-// node: the capture-time merge (qg_api.hip) installs them with hipGraphKernelNodeSetParams.
+// node: the capture-time merge (qg_capture_fuse.hip) installs them with hipGraphKernelNodeSetParams.
 struct GemvNodeFill {
     hipKernelNodeParams p;  // p.func == nullptr: nothing to launch; p.kernelParams = argv
     GemvGroup grp;          // the kernel's argument, `full` set for the launch's grid
@@ -93,6 +104,12 @@ void describe_kernel(const GemmArgs& g, const char* fmt, ...);
 // register-resident weight units, activation records staged in LDS.
 bool gemv_eligible(const GemmArgs& g);
 hipError_t launch_gemv(const GemmArgs& g, hipStream_t st);
+
+// The capture-time merge of back-to-back GEMVs (qg_capture_fuse.hip; qg.h at qg_gemm_w4a8): launch_gemv, or,
+// on a capturing stream, the call merged into the grouped node of the GEMVs captured just before it.
+hipError_t launch_or_merge_gemv(const GemmArgs& g, hipStream_t st);
+void set_capture_fusion(int on);                                // qg_set_capture_fusion
+void capture_fusion_stats(uint64_t* merged, uint64_t* nodes);   // qg_capture_fusion_stats
 
 // The decode GEMV (M <= 4) on the tiled layout (qg_gemvt.hip, round 6): waves of 16 rows x 4 stages reading
 // whole 256-B plane runs, the row kernel's dot and per-block terms (bit-identical per block to the
@@ -155,6 +172,10 @@ hipError_t launch_fp32(const GemmArgs& g, hipStream_t st);
 // kernel without a workspace.
 // hold: keep the buffer's lock until the caller has enqueued everything that uses it.
 void* stream_workspace(hipStream_t st, size_t bytes, int slot = 0, std::unique_lock<std::mutex>* hold = nullptr);
+void release_workspaces();  // qg_release_workspaces
+
+// Bytes per block of a quantization type (qg_block_bytes; 0: not a block type).
+int block_bytes(int type);
 
 // Quantizers / dequantizers (one thread per 32-element block, reference rounding semantics).
 hipError_t launch_quantize(int type, int variant, const float* x, void* y, int64_t nblocks, hipStream_t st);

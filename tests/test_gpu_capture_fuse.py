@@ -1,4 +1,4 @@
-"""Capture-time merge of back-to-back GEMVs (csrc/qg_api.hip capture_gemv; qg.h at qg_gemm_w4a8).
+"""Capture-time merge of back-to-back GEMVs (csrc/qg_capture_fuse.hip capture_gemv; qg.h at qg_gemm_w4a8).
 
 Under stream capture, consecutive independent qg_gemm_w4a8 GEMVs of one M, K and weight type become ONE
 grouped kernel node. Bar: every output of the graph replay equals the eager calls on the same inputs bit for
@@ -122,7 +122,7 @@ def test_independent_gemvs_merge(torch_, qg, calls, t, m, n, k):
                                           (4, 2048, 2, True)])
 def test_gate_by_shape_class(torch_, qg, m, k, t, merges):
     """The unit-loop form (more units per row than its lanes: K > 4096, K = 3072) merges at M = 1 only — M >= 2
-    measured slower merged (csrc/qg_api.hip fuse_class_enabled) — and with the gate lifted (mode 2) everything
+    measured slower merged (csrc/qg_capture_fuse.hip fuse_class_enabled) — and with the gate lifted (mode 2) everything
     merges; the bits are the eager calls' in all three graphs."""
     torch = torch_
     n, calls = 48, 3

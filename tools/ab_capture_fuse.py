@@ -3,7 +3,7 @@
 per shape, G qg_gemm_w4a8 calls on distinct resident weight copies (> 600 MB, so every launch streams from
 HBM) are captured twice into a hipGraph — merge off (G kernel nodes) and merge on for every shape class
 (mode 2: ceil(G / 64) grouped nodes) — and replayed in interleaved rounds, HIP events on the launch stream.
-Outputs must agree bit for bit between the arms. The gate in csrc/qg_api.hip (fuse_class_enabled) enables
+Outputs must agree bit for bit between the arms. The gate in csrc/qg_capture_fuse.hip (fuse_class_enabled) enables
 the classes where "fused" beats "unfused" by more than the unfused arm's own spread.
 
   python tools/ab_capture_fuse.py [--shapes 1x4096x4096:2,...] [--rounds 7] [--reps 20] [--out table.txt]
