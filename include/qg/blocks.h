@@ -13,6 +13,7 @@
  *   block_q5_0  22 B  compat/ggml_types.h:111-117
  *   block_q5_1  24 B  compat/ggml_types.h:125-132
  *   block_q4_K 144 B  ggml's K-quant (the reference defines only QK_K = 256 and the type id)
+ *   block_q6_K 210 B  ggml's K-quant (likewise)
  *
  * Nibble packing (include/quantize.h:56-67): qs[j] low nibble = x[j], high nibble = x[j+16].
  * Q5 fifth bit (tests/framework/test_framework.cuh:309-325): bit i of the little-endian u32
@@ -77,8 +78,21 @@ typedef struct {
     uint8_t qs[128];
 } qg_block_q4_K;
 
+/* ggml's block_q6_K: a super-block of 256 elements = 16 groups of 16 with signed 8-bit scales, 6-bit codes split
+ * over a nibble plane and a 2-bit plane, no min term. For element e: h = e / 128, p = e % 128, c = p / 32, l = p % 32,
+ *   lo = (ql[64h + 32(c & 1) + l] >> (4 (c >> 1))) & 15,  hi = (qh[32h + l] >> (2c)) & 3,  q = (lo | hi << 4) - 32
+ *   value = d * scales[8h + 2c + l / 16] * q
+ * 210 bytes: a multiple of 2, not of 4 -- consecutive super-blocks alternate between 0 and 2 bytes off a dword. */
+typedef struct {
+    uint8_t ql[128];     /* low 4 bits of the codes */
+    uint8_t qh[64];      /* high 2 bits of the codes */
+    int8_t scales[16];   /* one per 16 elements */
+    uint16_t d;          /* fp16 scale of the group scales */
+} qg_block_q6_K;
+
 #ifdef __cplusplus
 static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
+static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");
 static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");
 static_assert(sizeof(qg_block_q4_1) == 20, "block_q4_1 must be 20 bytes");
 static_assert(sizeof(qg_block_q5_0) == 22, "block_q5_0 must be 22 bytes");
@@ -87,6 +101,7 @@ static_assert(sizeof(qg_block_q8_0) == 34, "block_q8_0 must be 34 bytes");
 static_assert(sizeof(qg_block_q8_1) == 36, "block_q8_1 must be 36 bytes");
 #else
 _Static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
+_Static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");
 _Static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");
 _Static_assert(sizeof(qg_block_q4_1) == 20, "block_q4_1 must be 20 bytes");
 _Static_assert(sizeof(qg_block_q5_0) == 22, "block_q5_0 must be 22 bytes");

@@ -39,7 +39,8 @@ typedef enum {
     QG_TYPE_Q5_1 = 7,
     QG_TYPE_Q8_0 = 8,
     QG_TYPE_Q8_1 = 9,
-    QG_TYPE_Q4_K = 12  /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
+    QG_TYPE_Q4_K = 12, /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
+    QG_TYPE_Q6_K = 14  /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
 } qg_type;
 
 typedef enum {
@@ -106,6 +107,29 @@ int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, 
  * workspace of qg_gemm_w4a8_f32_workspace_size(M, K) bytes -> QG_ERR_UNSUPPORTED.
  * Every other entry that takes a wtype (tiled, repacked, prepacked, padded, grouped, strided-batched, _ws,
  * qg_quantize) returns QG_ERR_UNSUPPORTED for it and launches nothing. */
+
+/* ---- Q6_K weights (wtype == QG_TYPE_Q6_K) --------------------------------------------------
+ * B: block_q6_K[N][K/256], ggml's bytes (qg/blocks.h), rows dense. Q8_1 block b (0..7) of super-block sb is
+ * activation block 8 sb + b; it covers elements 32b .. 32b + 31, exactly the scale groups 2b (first 16
+ * elements) and 2b + 1 (last 16). With s0, s1 the exact int32 dots of the signed codes q (-32..31) with the
+ * Q8_1 bytes over those two halves:
+ *   isum(m, n, 8 sb + b) = scales[2b] * s0 + scales[2b + 1] * s1          (int32, exact; |isum| <= 2^24)
+ *   C(m, n) = sum_sb d * sum_b d_a(8 sb + b) * float(isum)
+ * The Q8_1 block's stored sum s_a is not used (the -32 is in the signed codes). The order of the fp32
+ * operations is the kernel's; each output is within 2 * (K/32 + W + 2) * 2^-24 * sum(|d d_a isum|) of the
+ * exact value, W = 0 for the decode GEMV and 8 for the MFMA prefill, and two launches give identical bits.
+ * Taken by the same entries as Q4_K: qg_gemm_w4a8, qg_gemm_w4a8_ex, qg_gemm_w4a8_ldc, qg_debug_sumi
+ * (isum[M][N][K/32] from the product's own instantiation), qg_debug_config, qg_select_algo, qg_dequantize
+ * ((d * float(scale)) * float(q), each product rounded to fp32), qg_gemm_w4a8_from_view (weights view:
+ * nb[0] = 210, ne[0] = K, dense rows) and qg_gemm_w4a8_f32 with a workspace. QG_ALGO_AUTO: the decode GEMV
+ * ("q6k_gemv") for M <= 8, the MFMA prefill ("q6k_mmq") from M = 9 on; both may be forced (the GEMV only for
+ * M <= 8 and while its LDS records, 304 B per token and super-block, fit 160 KiB). A Q6_K GEMV captured into
+ * a graph is a plain kernel node: the capture-time merge never considers it.
+ * Validation: K not a positive multiple of 256 -> QG_ERR_BAD_K; A not 4-B aligned or B not 2-B aligned ->
+ * QG_ERR_ALIGN (a 210-B super-block guarantees no more than 2 B inside a row, so the kernels take both
+ * parities); QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace ->
+ * QG_ERR_UNSUPPORTED. Every other entry that takes a wtype returns QG_ERR_UNSUPPORTED for it, as for Q4_K,
+ * and qg_tile_weights_bytes / qg_repack_weights_bytes return 0. */
 
 /* The Solution entry point of the definition gemm_q4_0_q8_1_w4a8
  * (schemas/definitions/gemm/gemm_q4_0_q8_1_w4a8.json:35-53: inputs A_q8_1[M][K/32], B_q4_0[N][K/32],
@@ -430,8 +454,8 @@ void qg_set_capture_fusion(int on);
 void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
-int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 0 if unknown */
-int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K, 0 if unknown */
+int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 0 if unknown */
+int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K / Q6_K, 0 if unknown */
 const char* qg_version(void);
 
 #ifdef __cplusplus

@@ -40,7 +40,10 @@ int qg_gemm_w8a8_cpu(const void* A_q8_1, const void* B_q8_0, float* C, int M, in
 /* Every weight format of qg_gemm_w4a8 (qg_type ids Q4_0/Q4_1/Q5_0/Q5_1/Q8_0), the same
  * per-block formulas as the GPU library (qg_common.hpp header), rows over `threads` threads
  * (<= 0: one). Also QG_TYPE_Q4_K (K % 256 == 0, else QG_ERR_BAD_K): the Q4_K product contract of qg.h,
- * one dot and one min accumulator per super-block in sub-block order, super-blocks summed in order. */
+ * one dot and one min accumulator per super-block in sub-block order, super-blocks summed in order.
+ * And QG_TYPE_Q6_K (K % 256 == 0, else QG_ERR_BAD_K): the Q6_K product contract of qg.h, isum in int32, one
+ * fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order. Bits are
+ * identical for every thread count (threads split the weight rows only). */
 int qg_gemm_w4a8_cpu_mt(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, int threads);
 
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */

@@ -11,6 +11,7 @@
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
 #include "qg_q4k.hpp"
+#include "qg_q6k.hpp"
 
 using namespace qg;
 
@@ -24,6 +25,7 @@ int block_bytes(int t) {
         case QG_TYPE_Q8_0: return 34;
         case QG_TYPE_Q8_1: return 36;
         case QG_TYPE_Q4_K: return 144;
+        case QG_TYPE_Q6_K: return 210;
     }
     return 0;
 }
@@ -42,11 +44,17 @@ bool is_weight_type(int t) {
     return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
 }
 
-// Q4_K (256-element super-blocks): taken by the entries that go through run_product with q4k_ok; every other
-// entry tests is_weight_type alone and so keeps refusing it.
+// The super-block types (256 elements: Q4_K, Q6_K): taken by the entries that go through run_product with
+// sb_ok; every other entry tests is_weight_type alone and so keeps refusing them.
 bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
+bool is_q6k_type(int t) { return t == QG_TYPE_Q6_K; }
+bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t); }
 
-int block_elems(int t) { return is_q4k_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
+int block_elems(int t) { return is_sb_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
+
+// Weight pointer alignment of a super-block type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
+// super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load.
+uintptr_t sb_weight_mask(int t) { return is_q6k_type(t) ? 1u : 15u; }
 
 // ---- the one ordered precheck ------------------------------------------------------------------------------
 // The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
@@ -195,23 +203,45 @@ int run_q4k(GemmArgs& g, int algo, hipStream_t st) {
     return QG_ERR_INVALID_ARG;
 }
 
-// The quantized product: one precheck, then the 32-element families or the Q4_K pair by the weight type's
-// block size. q4k_ok = false: the entries that refuse Q4_K (qg.h) -- it is then a type like any other they do
-// not take, checked at the 32-element granule.
-int run_product(GemmArgs& g, int algo, hipStream_t st, bool q4k_ok = true) {
-    const bool k4 = q4k_ok && is_q4k_type(g.wtype);
-    // 32-element families: fp16 fields, 2-byte alignment is the floor; Q4_K: 16-B super-blocks, 4-B records
-    const int rc = precheck({g.M, g.N}, g.K, k4 ? block_elems(g.wtype) : 32, k4 || is_weight_type(g.wtype),
-                            {{g.A, k4 ? 3u : 0u}, {g.B, k4 ? 15u : 1u}, {out_ptr(g), 0}});
+// Q6_K products (qg_q6k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on, Q4_K's threshold
+// ("Q6_K"). The GEMV's LDS records bound M * K (q6k_gemv_eligible); beyond that AUTO takes the MFMA
+// kernel at any M. Never through launch_or_merge_gemv: a captured Q6_K GEMV is a plain kernel node.
+#ifndef QG_Q6K_GEMV_MAXM  // (A/B builds: the largest M AUTO sends to the decode GEMV)
+#define QG_Q6K_GEMV_MAXM 8
+#endif
+int select_algo_q6k(const GemmArgs& g) {
+    return g.M <= QG_Q6K_GEMV_MAXM && q6k_gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
+}
+
+// Q6_K after the precheck.
+int run_q6k(GemmArgs& g, int algo, hipStream_t st) {
+    if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_AUTO) algo = select_algo_q6k(g);
+    if (algo == QG_ALGO_GEMV) return q6k_gemv_eligible(g) ? hip_status(launch_q6k_gemv(g, st)) : QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_MFMA) return q6k_mmq_eligible(g) ? hip_status(launch_q6k_mmq(g, st)) : QG_ERR_UNSUPPORTED;
+    return QG_ERR_INVALID_ARG;
+}
+
+// The quantized product: one precheck, then the 32-element families or a super-block type's pair by the weight
+// type's block size. sb_ok = false: the entries that refuse the super-block types (qg.h) -- such a type is then
+// one like any other they do not take, checked at the 32-element granule.
+int run_product(GemmArgs& g, int algo, hipStream_t st, bool sb_ok = true) {
+    const bool ksb = sb_ok && is_sb_type(g.wtype);
+    // 32-element families: fp16 fields, 2-byte alignment is the floor; super-block types: 4-B activation records,
+    // weights by the type (sb_weight_mask)
+    const int rc = precheck({g.M, g.N}, g.K, ksb ? block_elems(g.wtype) : 32, ksb || is_weight_type(g.wtype),
+                            {{g.A, ksb ? 3u : 0u}, {g.B, ksb ? sb_weight_mask(g.wtype) : 1u}, {out_ptr(g), 0}});
     if (rc != QG_GO) return rc;
-    return k4 ? run_q4k(g, algo, st) : run_q32(g, algo, st);
+    if (!ksb) return run_q32(g, algo, st);
+    return is_q6k_type(g.wtype) ? run_q6k(g, algo, st) : run_q4k(g, algo, st);
 }
 
 // what QG_ALGO_AUTO dispatches to (qg_select_algo): the same routing
 int select_product_algo(const GemmArgs& g) {
-    const bool k4 = is_q4k_type(g.wtype);
-    if (!(k4 || is_weight_type(g.wtype)) || g.K <= 0 || g.K % block_elems(g.wtype) != 0) return -1;
-    return k4 ? select_algo_q4k(g) : select_algo(g);
+    const bool ksb = is_sb_type(g.wtype);
+    if (!(ksb || is_weight_type(g.wtype)) || g.K <= 0 || g.K % block_elems(g.wtype) != 0) return -1;
+    if (!ksb) return select_algo(g);
+    return is_q6k_type(g.wtype) ? select_algo_q6k(g) : select_algo_q4k(g);
 }
 
 // The tiled weight layout (qg_tile_weights): the MFMA small-batch decode for M = 3..4 and M = 2 at K/32 > 256
@@ -281,7 +311,7 @@ int run_w16(int wtype, const float* A, const void* B, float* C, int M, int N, in
 size_t row_bytes(int type, int64_t K) {
     if (type == QG_TYPE_F32) return (size_t)K * 4;
     if (type == QG_TYPE_F16) return (size_t)K * 2;
-    const int be = block_elems(type);  // 256 for Q4_K
+    const int be = block_elems(type);  // 256 for the super-block types
     return be ? (size_t)(K / be) * (size_t)block_bytes(type) : 0;
 }
 
@@ -314,16 +344,16 @@ size_t fused_workspace_bytes(int M, int K) { return M > 0 && K > 0 ? (size_t)M *
 // the Q8_1 product (same bytes, so the same results); without a workspace, fused GEMV launches
 // over row chunks (the weights are streamed once per chunk).
 int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
-    const bool k4 = is_q4k_type(g.wtype);
+    const bool ksb = is_sb_type(g.wtype);
     const size_t es = g.ain == AIN_F32 ? 4 : 2;
-    const int rc = precheck({g.M, g.N}, g.K, k4 ? block_elems(g.wtype) : 32, k4 || is_weight_type(g.wtype),
-                            {{g.A, k4 ? 3 : es - 1}, {g.B, k4 ? 15u : 1u}, {g.C, 0}});
+    const int rc = precheck({g.M, g.N}, g.K, ksb ? block_elems(g.wtype) : 32, ksb || is_weight_type(g.wtype),
+                            {{g.A, ksb ? 3 : es - 1}, {g.B, ksb ? sb_weight_mask(g.wtype) : 1u}, {g.C, 0}});
     if (rc != QG_GO) return rc;
     const bool vec_ok = ((uintptr_t)g.A & 15) == 0;
     const bool ws_ok = ws && ws_bytes >= fused_workspace_bytes(g.M, g.K);
-    // Q4_K has no fused prologue: only FP32 rows through the caller's workspace, then the Q8_1 product on it
-    if (k4 && (g.ain != AIN_F32 || !ws_ok)) return QG_ERR_UNSUPPORTED;
-    if (!k4 && g.M <= 4 && vec_ok && gemv_eligible(g)) return hip_status(launch_gemv(g, st));
+    // the super-block types have no fused prologue: only FP32 rows through the caller's workspace, then the Q8_1 product on it
+    if (ksb && (g.ain != AIN_F32 || !ws_ok)) return QG_ERR_UNSUPPORTED;
+    if (!ksb && g.M <= 4 && vec_ok && gemv_eligible(g)) return hip_status(launch_gemv(g, st));
     if (ws_ok) {
         if (((uintptr_t)ws & 3) != 0) return QG_ERR_ALIGN;
         const int64_t nblocks = (int64_t)g.M * (g.K / 32);
@@ -641,7 +671,7 @@ int qg_gemm_w8a8(const void* A, const void* B, float* C, int M, int N, int K, qg
 }
 
 int qg_quantize(int type, int variant, const float* x, void* y, int64_t k, qg_stream_t stream) {
-    const bool type_ok = block_bytes(type) != 0 && !is_q4k_type(type);  // (no Q4_K quantizer)
+    const bool type_ok = block_bytes(type) != 0 && !is_sb_type(type);  // (no Q4_K / Q6_K quantizer)
     const bool variant_ok = variant == 0 || (variant == 1 && type == QG_TYPE_Q8_1) ||
                             (variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0));
     const int rc = precheck_count(k, 32, type_ok && variant_ok, {{x, 3}, {y, type == QG_TYPE_Q8_1 ? 3u : 1u}});
@@ -659,9 +689,10 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 }
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
-    const int be = is_q4k_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
+    const int be = is_sb_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
     const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, 1}, {y, 3}});
     if (rc != QG_GO) return rc;
+    if (is_q6k_type(type)) return hip_status(launch_dequantize_q6k(x, y, k / 256, (hipStream_t)stream));
     if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));
 }
@@ -702,10 +733,10 @@ int qg_gemm_w4a8_from_view(const qg_tensor_view* act, const qg_tensor_view* w, q
         else if (strcmp(kernel_type, "ragged") == 0) algo = QG_ALGO_RAGGED;
         else return QG_ERR_INVALID_ARG;
     }
-    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !(is_weight_type(w->type) || is_q4k_type(w->type)))
+    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !(is_weight_type(w->type) || is_sb_type(w->type)))
         return QG_ERR_UNSUPPORTED;
     int64_t M, N, K;
-    const int rc = view_dims(act, w, out, M, N, K, block_elems(w->type));  // Q4_K: K % 256, 144-B super-blocks
+    const int rc = view_dims(act, w, out, M, N, K, block_elems(w->type));  // super-block types: K % 256
     if (rc != QG_OK) return rc;
     return qg_gemm_w4a8_ex(act->data, w->data, (float*)out->data, (int)M, (int)N, (int)K, w->type, algo, stream);
 }

@@ -115,7 +115,15 @@ uint64_t tensor_bytes(uint32_t t, const int64_t ne[4], uint32_t n_dims) {
         case QG_TYPE_F32: return n * 4;
         case QG_TYPE_F16: return n * 2;
     }
-    const int bb = qg_block_bytes((int)t), be = qg_block_elems((int)t);  // Q4_K: 144-B super-blocks of 256
+    // the types this reader serves: the 32-element blocks and Q4_K (144-B super-blocks of 256). The reader's own
+    // list, not every type qg_block_bytes knows: a Q6_K tensor stays listed with nbytes == 0 and is not readable
+    // (lifting that is a follow-up of its own, DESIGN.md "Q6_K")
+    switch (t) {
+        case QG_TYPE_Q4_0: case QG_TYPE_Q4_1: case QG_TYPE_Q5_0: case QG_TYPE_Q5_1: case QG_TYPE_Q8_0: case QG_TYPE_Q8_1:
+        case QG_TYPE_Q4_K: break;
+        default: return 0;
+    }
+    const int bb = qg_block_bytes((int)t), be = qg_block_elems((int)t);
     if (bb == 0 || be == 0 || ne[0] % be != 0) return 0;
     return n / (uint64_t)be * (uint64_t)bb;
 }

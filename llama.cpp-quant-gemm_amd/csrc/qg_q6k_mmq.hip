@@ -1,0 +1,262 @@
+// qg_q6k_mmq.hip — the Q6_K MFMA prefill (M >= 9 activation rows, and any M the GEMV cannot take), family "q6k_mmq".
+//
+// C[m * ldc + n] = sum_sb sum_b (d * d_a) * float(scales[2b] * s0 + scales[2b + 1] * s1)   (qg_q6k.hpp)
+//
+// Work decomposition ("Q6_K"); the workgroup shapes, the activation staging and the K-slice reduction
+// are those of qg_q4k_mmq.hip:
+//  * A workgroup of 8 waves = RG row groups x KS = 8 / RG K slices owns 16 * RG weight rows x 16 * TT tokens and
+//    all of K. Wave (rg, ks) takes rows 16 rg .. 16 rg + 15 and super-blocks ks, ks + KS, ...; the KS partial tiles
+//    of a row group are summed through LDS in slice order, so two launches give identical bits.
+//  * v_mfma_i32_16x16x32_i8, the weights as the A operand: MFMA lane (r, q) holds k = 8q .. 8q + 7 of Q8_1 block
+//    b = 4h + c of row r, i.e. 8 bytes of ql at 64h + 32(c & 1) + 8q and 8 bytes of qh at 32h + 8q. Per
+//    super-block a lane reads four ql pieces and two qh pieces of 8 bytes and builds the 8 blocks' signed codes
+//    from them (q6k_codes), no cross-lane movement, straight from global memory.
+//  * A Q8_1 block spans two scale groups, and the lanes q < 2 hold exactly the first one: two MFMAs per block and
+//    token tile, the A operand zeroed in lanes q >= 2 for s0 and in lanes q < 2 for s1 (the matrix pipe is far
+//    from busy in the sibling kernels). isum = scales[2b] * s0 + scales[2b + 1] * s1 in int32.
+//  * Loads (qg_q6k.hpp, q6k_load): every piece is 0 or 2 bytes off a dword depending on the lane's row and the
+//    super-block; each is read as the dword-aligned span that covers it plus one dword and realigned with
+//    v_alignbyte. The extra dword of a ql / qh piece ends before byte 196 of the super-block; the result lane's
+//    header piece is scales[16] and d as one 18-byte stream (5 dwords: bytes 192..211 at parity 0, 190..209 at
+//    parity 2). No load at an address that is not a multiple of 4, none of a dword without a byte of the tensor;
+//    only the last super-block's final dword at parity 0 is half outside it, in the same page. By construction;
+//    no test probes it.
+//  * The activations are the B operand, staged through LDS per (K slice, 16-token tile) as in q4k_mmq: a token's
+//    8 blocks of one super-block are 288 contiguous bytes; one barrier per step; double buffered with RG > 1.
+//  * The result lane (c, q) holds token c x rows 4q .. 4q + 3, reads those rows' headers itself and applies
+//    acc = fma(d * d_a, float(isum), acc) per block.
+//  * Tolerance: W = 8. An output is the sum of KS <= 8 slice partials, each an fma chain over the slice's blocks:
+//    K/32 terms of two roundings each plus at most 8 chained partial sums.
+//  * SUMI: the same instantiation stores isum in place of the epilogue.
+#include "qg_q6k.hpp"
+
+namespace qg {
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int Q6K_MMQ_WAVES = 8;
+constexpr int Q6K_MMQ_WGS = 64 * Q6K_MMQ_WAVES;
+constexpr int Q6K_TOK_DW = 72;               // one token's 8 blocks of a super-block: 288 B
+constexpr int Q6K_TILE_DW = 16 * Q6K_TOK_DW;  // a 16-token tile: 1152 dwords
+
+// byte J (0..15) of a 16-byte group held in four dwords, sign extended
+template <int J> __device__ __forceinline__ int q6k_scale(const uint32_t (&v)[4]) {
+    return (int)(int8_t)(v[J / 4] >> (8 * (J % 4)));
+}
+
+template <int TT, int RG, bool SUMI>
+__global__ __launch_bounds__(Q6K_MMQ_WGS) void q6k_mmq_kernel(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B,
+                                                             int M, int N, int K, void* __restrict__ out, long ldc) {
+    static_assert(RG == 1 || RG == 4, "row groups per workgroup");
+    constexpr int W = Q6K_MMQ_WAVES, KS = W / RG;
+    constexpr int NBUF = RG > 1 ? 2 : 1;
+    constexpr int NR = 16 / RG;             // token loads (dwords 0..63 of a token) per wave and tile
+    constexpr int NT = RG == 1 ? 2 : 1;     // tail loads (dwords 64..71 of 8 tokens) per wave (RG = 4: waves 0, 1)
+    constexpr int STAGE_DW = KS * NBUF * Q6K_TILE_DW, PART_DW = SUMI ? 0 : W * TT * 256;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
+    const int nb = K / QK, nsb = K / SB_ELEMS;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int rg = wave % RG, ks = wave / RG;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int n0 = tile * (16 * RG) + 16 * rg, m0 = blockIdx.y * (16 * TT);
+    const long wrow = (long)nsb * Q6K_BYTES;
+    const long arow = (long)nb * 9;  // dwords per activation row
+    // rows / tokens past the end are clamped to the last one: loaded and multiplied, never stored
+    const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * wrow;  // the operand row of MFMA lane (r16, q)
+    const uint8_t* wh[4];                                       // the result lane's rows 4q .. 4q + 3
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wh[e] = B + (long)min(n0 + 4 * q + e, N - 1) * wrow;
+    uint32_t* stage = smem + ks * (NBUF * Q6K_TILE_DW);
+
+    // this wave's share of a 16-token tile of super-block sb: token loads r take dwords 0..63 of token NR rg + r (the
+    // token's row is wave-uniform, so its address lives in SGPRs), a tail load dwords 64..71 of 8 tokens
+    const bool tail = RG == 1 || rg < 2;
+    auto load_tile = [&](uint32_t (&dst)[NR + NT], int sb, int t) {
+        const uint32_t* a = A + (long)sb * Q6K_TOK_DW;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) dst[r] = a[(long)min(m0 + 16 * t + NR * rg + r, M - 1) * arow + lane];
+        if (tail) {
+#pragma unroll
+            for (int b = 0; b < NT; ++b) {
+                const int tk = 8 * (RG == 1 ? b : rg) + (lane >> 3);
+                dst[NR + b] = a[(long)min(m0 + 16 * t + tk, M - 1) * arow + 64 + (lane & 7)];
+            }
+        }
+    };
+    auto store_tile = [&](const uint32_t (&src)[NR + NT], uint32_t* buf) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) buf[(NR * rg + r) * Q6K_TOK_DW + lane] = src[r];
+        if (tail) {
+#pragma unroll
+            for (int b = 0; b < NT; ++b)
+                buf[(8 * (RG == 1 ? b : rg) + (lane >> 3)) * Q6K_TOK_DW + 64 + (lane & 7)] = src[NR + b];
+        }
+    };
+    struct wregs {
+        uint32_t ql[4][3];  // 8 bytes at 32 i + 8q of ql (+ the realignment dword)
+        uint32_t qh[2][3];  // 8 bytes at 32 h + 8q of qh
+        uint32_t hd[4][5];  // scales[16] and d of the result lane's four rows
+    };
+    auto load_weights = [&](wregs& w, int sb) {
+        const uint8_t* sbp = wq + (long)sb * Q6K_BYTES + 8 * q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q6k_load<2>(sbp + 32 * i, w.ql[i]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) q6k_load<2>(sbp + Q6K_QH + 32 * h, w.qh[h]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q6k_load<4>(wh[e] + (long)sb * Q6K_BYTES + Q6K_SC, w.hd[e]);
+    };
+
+    float acc[TT][4];
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0f;
+    const v4i zero = {0, 0, 0, 0};
+    // the A operand of the s0 MFMA keeps lanes q < 2 (elements 0..15 of the block), that of the s1 MFMA the others
+    const uint32_t keep0 = q < 2 ? 0xFFFFFFFFu : 0u, keep1 = ~keep0;
+
+    const int iters = (nsb + KS - 1) / KS;  // the same for every wave
+    uint32_t tl[NR + NT];
+    wregs wc;
+    {
+        const int sb0 = min(ks, nsb - 1);
+        load_tile(tl, sb0, 0);
+        load_weights(wc, sb0);
+    }
+    for (int it = 0; it < iters; ++it) {
+        const int sb = it * KS + ks;
+        const bool valid = sb < nsb;  // wave-uniform
+        const int sbl = min(sb, nsb - 1);  // the super-block wc holds
+        const int sbn = min(sb + KS, nsb - 1);
+        // realign by the parity of each row's super-block address (every piece sits at a multiple of 4 past it)
+        uint32_t cl[8][2];  // the signed codes of blocks 0..7, this lane's 8 elements
+        {
+            const uint32_t sh = (uint32_t)((uintptr_t)(wq + (long)sbl * Q6K_BYTES) & 3);
+            uint32_t l[4][2], hq[2][2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) q6k_realign<2>(wc.ql[i], sh, l[i]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) q6k_realign<2>(wc.qh[h], sh, hq[h]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    cl[4 * h + 0][x] = q6k_codes<0>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 1][x] = q6k_codes<1>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 2][x] = q6k_codes<2>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 3][x] = q6k_codes<3>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                }
+        }
+        uint32_t sc[4][4];
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t sh = (uint32_t)((uintptr_t)(wh[e] + (long)sbl * Q6K_BYTES) & 3);
+            q6k_realign<4>(wc.hd[e], sh, sc[e]);
+            d[e] = h2f((wc.hd[e][4] >> (8 * sh)) & 0xFFFFu);
+        }
+        static_for<TT>([&](auto T) {
+            constexpr int t = decltype(T)::value;
+            // this tile into the slice's LDS buffer (step parity: TT is 1 or even, so the parity is t's, or it's at
+            // TT = 1), the next one (and after the last, the next super-block's weights) in flight, then the barrier
+            // between the writes and the operand reads
+            uint32_t* buf = stage + (NBUF > 1 ? ((TT == 1 ? it : t) & 1) * Q6K_TILE_DW : 0);
+            store_tile(tl, buf);
+            if constexpr (t + 1 < TT) {
+                load_tile(tl, min(sb, nsb - 1), t + 1);
+            } else {
+                if (it + 1 < iters) {
+                    load_tile(tl, sbn, 0);
+                    load_weights(wc, sbn);
+                }
+            }
+            __syncthreads();
+            if (valid) {
+                const uint32_t* tok = buf + r16 * Q6K_TOK_DW;
+                static_for<8>([&](auto J) {
+                    constexpr int j = decltype(J)::value;
+                    const uint32_t b0 = tok[9 * j + 1 + 2 * q], b1 = tok[9 * j + 2 + 2 * q];
+                    const long bfr = (long)(((unsigned long)b1 << 32) | b0);
+                    const long a0 = (long)(((unsigned long)(cl[j][1] & keep0) << 32) | (cl[j][0] & keep0));
+                    const long a1 = (long)(((unsigned long)(cl[j][1] & keep1) << 32) | (cl[j][0] & keep1));
+                    const v4i c0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a0, bfr, zero, 0, 0, 0);
+                    const v4i c1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a1, bfr, zero, 0, 0, 0);
+                    float da = 0.0f;
+                    if constexpr (!SUMI) da = h2f(tok[9 * j] & 0xFFFFu);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int isum = q6k_scale<2 * j>(sc[e]) * c0[e] + q6k_scale<2 * j + 1>(sc[e]) * c1[e];
+                        if constexpr (SUMI) {
+                            const int m = m0 + 16 * t + r16, n = n0 + 4 * q + e;
+                            if (m < M && n < N) static_cast<int32_t*>(out)[((long)m * N + n) * nb + 8 * sb + j] = isum;
+                        } else {
+                            acc[t][e] = __builtin_fmaf(d[e] * da, (float)isum, acc[t][e]);
+                        }
+                    }
+                    // a block's two MFMAs and their epilogue stay together: scheduled freely, hipcc issues the
+                    // tile's MFMAs first and holds all their results
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+        });
+    }
+    if constexpr (!SUMI) {
+        // partial tiles as [slice][row group][token][row] (over the staging buffers, once every wave has read its
+        // last tile): lane (c, q) writes rows 4q .. 4q + 3 of token c (one 16-B store)
+        constexpr int PT = TT * 256;  // outputs per (slice, row group)
+        __syncthreads();
+        float* part = reinterpret_cast<float*>(smem);
+#pragma unroll
+        for (int t = 0; t < TT; ++t)
+            *reinterpret_cast<float4*>(&part[(ks * RG + rg) * PT + (16 * t + r16) * 16 + 4 * q]) =
+                make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+        __syncthreads();
+        float* C = static_cast<float*>(out);
+        for (int idx = threadIdx.x; idx < RG * PT; idx += Q6K_MMQ_WGS) {
+            float sum = part[idx];
+#pragma unroll
+            for (int k = 1; k < KS; ++k) sum += part[k * (RG * PT) + idx];
+            const int g = idx / PT, o = idx - g * PT;
+            const int m = m0 + (o >> 4), n = tile * (16 * RG) + 16 * g + (o & 15);
+            if (m < M && n < N) C[m * ldc + n] = sum;
+        }
+    }
+}
+
+template <int TT, int RG, bool SUMI> hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
+    const int gx = (g.N + 16 * RG - 1) / (16 * RG), gy = (g.M + 16 * TT - 1) / (16 * TT);
+    if (g.describe) {
+        describe_kernel(g, "q6k_mmq TT=%d RG=%d KS=%d grid=%dx%d", TT, RG, Q6K_MMQ_WAVES / RG, gx, gy);
+        return hipSuccess;
+    }
+    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
+    hipLaunchKernelGGL((q6k_mmq_kernel<TT, RG, SUMI>), dim3(gx, gy), dim3(Q6K_MMQ_WGS), 0, st, (const uint32_t*)g.A,
+                       (const uint8_t*)g.B, g.M, g.N, g.K, out, g.ldc_m);
+    return hipGetLastError();
+}
+
+template <bool SUMI> hipError_t launch_t(const GemmArgs& g, hipStream_t st) {
+    if (g.M <= 16) return launch_cfg<1, 1, SUMI>(g, st);
+    if (g.M <= 32) return launch_cfg<2, 1, SUMI>(g, st);
+    // 64 x 64 tiles once they fill the CUs (M = 256 at N = 4096 on a whole MI355X)
+    if ((long)((g.N + 63) / 64) * ((g.M + 63) / 64) >= device_cus()) return launch_cfg<4, 4, SUMI>(g, st);
+    return launch_cfg<4, 1, SUMI>(g, st);
+}
+
+}  // namespace
+
+bool q6k_mmq_eligible(const GemmArgs& g) {
+    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
+    if (((uintptr_t)g.B & 1) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
+    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
+    return (g.M + 63) / 64 <= 65535;
+}
+
+hipError_t launch_q6k_mmq(const GemmArgs& g, hipStream_t st) {
+    return g.sumi ? launch_t<true>(g, st) : launch_t<false>(g, st);
+}
+
+}  // namespace qg

@@ -17,6 +17,7 @@
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
 #include "qg_q4k.hpp"
+#include "qg_q6k.hpp"
 #include "qg_quant_block.hpp"
 
 namespace qg {
@@ -507,6 +508,37 @@ hipError_t launch_dequantize_q4k(const void* x, float* y, int64_t nsb, hipStream
     const int64_t nsub = nsb * 8;
     hipLaunchKernelGGL(dequantize_q4k_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
                        nsub);
+    return hipGetLastError();
+}
+
+// Q6_K (qg_q6k.hpp): one thread per 16-element scale group, y = (d * float(scale)) * float(q) in exactly that
+// operation order (no contraction), so the result can be checked bit for bit. Byte loads: x needs only the 2-B
+// alignment of its fp16 field.
+namespace {
+__global__ __launch_bounds__(256) void dequantize_q6k_kernel(const uint8_t* __restrict__ x, float* __restrict__ y,
+                                                             int64_t ngrp) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngrp) return;
+    const uint8_t* b = x + (g >> 4) * Q6K_BYTES;
+    const int gi = (int)(g & 15);  // scale group 8h + 2c + t: elements 128h + 32c + 16t ..+15
+    const int h = gi >> 3, c = (gi >> 1) & 3, t = gi & 1;
+    const float d = h2f((uint32_t)b[Q6K_D] | ((uint32_t)b[Q6K_D + 1] << 8));
+    const float ds = d * (float)(int8_t)b[Q6K_SC + gi];
+    const uint8_t* ql = b + 64 * h + 32 * (c & 1) + 16 * t;
+    const uint8_t* qh = b + Q6K_QH + 32 * h + 16 * t;
+    float* o = y + (g >> 4) * SB_ELEMS + 128 * h + 32 * c + 16 * t;
+    for (int l = 0; l < 16; ++l) {
+        const int q = (((ql[l] >> (4 * (c >> 1))) & 15) | (((qh[l] >> (2 * c)) & 3) << 4)) - 32;
+        o[l] = ds * (float)q;
+    }
+}
+}  // namespace
+
+hipError_t launch_dequantize_q6k(const void* x, float* y, int64_t nsb, hipStream_t st) {
+    if (nsb == 0) return hipSuccess;
+    const int64_t ngrp = nsb * 16;
+    hipLaunchKernelGGL(dequantize_q6k_kernel, dim3((unsigned)((ngrp + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
+                       ngrp);
     return hipGetLastError();
 }
 

@@ -159,6 +159,46 @@ void gemm_rows<FmtQ4_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int
         }
 }
 
+// Q6_K (qg/blocks.h: 210-B super-blocks; Q8_1 block b of super-block sb is activation block 8 sb + b and meets the
+// scale groups 2b and 2b + 1). The product contract of qg.h: isum = scales[2b] * s0 + scales[2b + 1] * s1 in int32,
+// one fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order.
+struct FmtQ6_K {
+    static constexpr int bytes = 210;
+    // the signed code of element 32b + l of a super-block (b = 4h + c)
+    static int value(const uint8_t* w, int b, int l) {
+        const int h = b >> 2, c = b & 3;
+        const int lo = (w[64 * h + 32 * (c & 1) + l] >> (4 * (c >> 1))) & 15;
+        const int hi = (w[128 + 32 * h + l] >> (2 * c)) & 3;
+        return (lo | (hi << 4)) - 32;
+    }
+};
+template <>
+void gemm_rows<FmtQ6_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int N, int K, int j0, int j1) {
+    const int nsb = K / 256;
+    const size_t arow = (size_t)(K / QK) * 36, wrow = (size_t)nsb * FmtQ6_K::bytes;
+    for (int i = 0; i < M; ++i)
+        for (int n = j0; n < j1; ++n) {
+            float sum = 0.0f;
+            for (int sb = 0; sb < nsb; ++sb) {
+                const uint8_t* w = B + n * wrow + (size_t)sb * FmtQ6_K::bytes;
+                const int8_t* sc = reinterpret_cast<const int8_t*>(w + 192);
+                const float d = half_to_float(w + 208);
+                float fd = 0.0f;
+                for (int b = 0; b < 8; ++b) {
+                    const ActBlock a(A + i * arow + (size_t)(8 * sb + b) * 36);
+                    int32_t s0 = 0, s1 = 0;
+                    for (int l = 0; l < 16; ++l) {
+                        s0 += (int32_t)a.qs[l] * FmtQ6_K::value(w, b, l);
+                        s1 += (int32_t)a.qs[l + 16] * FmtQ6_K::value(w, b, l + 16);
+                    }
+                    fd += a.d * (float)((int32_t)sc[2 * b] * s0 + (int32_t)sc[2 * b + 1] * s1);
+                }
+                sum += d * fd;
+            }
+            C[(size_t)i * N + n] = sum;
+        }
+}
+
 // Process-wide persistent worker pool: threads are started once (grown on demand) and parked on
 // a condition variable between jobs, so a multi-threaded call costs one wake-up per worker instead
 // of a thread start and join (which dominated a 1-9 ms GEMV at 256 threads). One job at a time
@@ -255,10 +295,11 @@ extern "C" {
 int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int threads) {
     const int rc = check_gemm(A, B, C, M, N, K);
     if (rc != QG_OK) return rc;
-    if (wtype == QG_TYPE_Q4_K && K % 256 != 0) return QG_ERR_BAD_K;
+    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K) && K % 256 != 0) return QG_ERR_BAD_K;
     if (M == 0 || N == 0) return QG_OK;
     switch (wtype) {
         case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
+        case QG_TYPE_Q6_K: gemm_threads<FmtQ6_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q5_0: gemm_threads<FmtQ5_0>(A, B, C, M, N, K, threads); return QG_OK;

@@ -19,9 +19,12 @@ import torch
 from . import _lib
 
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
-Q4_K = 12
-_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144}
-_BE = {Q4_K: 256}  # elements per block where it is not 32 (qg_block_elems)
+Q4_K, Q6_K = 12, 14
+_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210}
+_BE = {Q4_K: 256, Q6_K: 256}  # elements per block where it is not 32 (qg_block_elems)
+# the block types the GGUF reader serves (its own list: a Q6_K tensor is listed, not readable); views of bytes the
+# caller loaded (view_of) take every type of _BB
+_GGUF_BB = {t: bb for t, bb in _BB.items() if t != Q6_K}
 
 
 class TensorView(ctypes.Structure):
@@ -77,8 +80,8 @@ class GGUFTensor:
         dims = [d for d in reversed(self.ne)]
         while len(dims) > 1 and dims[0] == 1:
             dims = dims[1:]
-        if self.type in _BB:
-            return tuple(dims[:-1]) + (dims[-1] // _BE.get(self.type, 32), _BB[self.type])
+        if self.type in _GGUF_BB:
+            return tuple(dims[:-1]) + (dims[-1] // _BE.get(self.type, 32), _GGUF_BB[self.type])
         return tuple(dims)
 
     def __repr__(self) -> str:
@@ -155,14 +158,14 @@ class GGUFFile:
         t = self._t(name)
         p = self._lib.qg_gguf_tensor_data(self._h, t.index)
         raw = np.frombuffer(ctypes.string_at(p, t.nbytes), np.uint8)
-        if t.type in _BB:
+        if t.type in _GGUF_BB:
             return raw.reshape(t.shape)
         return raw.view(np.float32 if t.type == F32 else np.float16).reshape(t.shape)
 
     def to_device(self, name: str, device: str | torch.device = "cuda") -> torch.Tensor:
         """Upload the tensor (uint8 [.., rows, K/32, bb] for quantized types, float32/float16 otherwise)."""
         t = self._t(name)
-        dtype = torch.uint8 if t.type in _BB else torch.float32 if t.type == F32 else torch.float16
+        dtype = torch.uint8 if t.type in _GGUF_BB else torch.float32 if t.type == F32 else torch.float16
         out = torch.empty(t.shape, dtype=dtype, device=device)
         with torch.cuda.device(out.device):
             st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)

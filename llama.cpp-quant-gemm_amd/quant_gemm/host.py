@@ -24,7 +24,8 @@ SIGNATURES = {
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
     "qg_fill_step4_cpu": ([ctypes.c_uint, I, I, I, I, I, P, P], I),
 }
-BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144}  # 12: Q4_K, 256-element super-blocks
+# 12: Q4_K, 14: Q6_K, 256-element super-blocks
+BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210}
 _lib = None
 
 
