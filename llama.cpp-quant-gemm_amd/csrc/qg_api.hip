@@ -183,46 +183,47 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
     return QG_OK;
 }
 
-// Q4_K products (qg_q4k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on. Interleaved A/B
-// against a build with the threshold at 4 | 5 (profiles/q4k/ab_q4k_variants.txt, N = K = 4096): M = 5 GEMV 5.82 us,
-// MFMA 7.43; M = 8 GEMV 7.31, MFMA 7.45 — the GEMV keeps M <= 8. The GEMV's LDS records bound M * K
-// (q4k_gemv_eligible); beyond that AUTO takes the MFMA kernel at any M.
+// The super-block products (qg_q4k.hpp, qg_q6k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on.
+// Interleaved A/B of Q4_K against a build with the threshold at 4 | 5 (profiles/q4k/ab_q4k_variants.txt,
+// N = K = 4096): M = 5 GEMV 5.82 us, MFMA 7.43; M = 8 GEMV 7.31, MFMA 7.45 — the GEMV keeps M <= 8; Q6_K keeps the
+// threshold ("Q6_K", 3b). The GEMV's LDS records bound M * K (gemv_eligible); beyond that AUTO takes the
+// MFMA kernel at any M. Never through launch_or_merge_gemv: a captured super-block GEMV is a plain kernel node.
 #ifndef QG_Q4K_GEMV_MAXM  // (A/B builds: the largest M AUTO sends to the decode GEMV)
 #define QG_Q4K_GEMV_MAXM 8
 #endif
-int select_algo_q4k(const GemmArgs& g) {
-    return g.M <= QG_Q4K_GEMV_MAXM && q4k_gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
-}
-
-// Q4_K after the precheck.
-int run_q4k(GemmArgs& g, int algo, hipStream_t st) {
-    if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
-    if (algo == QG_ALGO_AUTO) algo = select_algo_q4k(g);
-    if (algo == QG_ALGO_GEMV) return q4k_gemv_eligible(g) ? hip_status(launch_q4k_gemv(g, st)) : QG_ERR_UNSUPPORTED;
-    if (algo == QG_ALGO_MFMA) return q4k_mmq_eligible(g) ? hip_status(launch_q4k_mmq(g, st)) : QG_ERR_UNSUPPORTED;
-    return QG_ERR_INVALID_ARG;
-}
-
-// Q6_K products (qg_q6k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on, Q4_K's threshold
-// ("Q6_K"). The GEMV's LDS records bound M * K (q6k_gemv_eligible); beyond that AUTO takes the MFMA
-// kernel at any M. Never through launch_or_merge_gemv: a captured Q6_K GEMV is a plain kernel node.
-#ifndef QG_Q6K_GEMV_MAXM  // (A/B builds: the largest M AUTO sends to the decode GEMV)
+#ifndef QG_Q6K_GEMV_MAXM
 #define QG_Q6K_GEMV_MAXM 8
 #endif
-int select_algo_q6k(const GemmArgs& g) {
-    return g.M <= QG_Q6K_GEMV_MAXM && q6k_gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
+struct SbRoute {
+    bool (*gemv_eligible)(const GemmArgs&);
+    hipError_t (*launch_gemv)(const GemmArgs&, hipStream_t);
+    bool (*mmq_eligible)(const GemmArgs&);
+    hipError_t (*launch_mmq)(const GemmArgs&, hipStream_t);
+    int maxm;
+};
+constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K
+    {q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, QG_Q4K_GEMV_MAXM},
+    {q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, QG_Q6K_GEMV_MAXM},
+};
+// the route of a super-block type (is_sb_type holds)
+const SbRoute& sb_route(int t) { return SB_ROUTES[is_q6k_type(t) ? 1 : 0]; }
+
+int select_algo_sb(const GemmArgs& g) {
+    const SbRoute& r = sb_route(g.wtype);
+    return g.M <= r.maxm && r.gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
 }
 
-// Q6_K after the precheck.
-int run_q6k(GemmArgs& g, int algo, hipStream_t st) {
+// A super-block type after the precheck.
+int run_sb(GemmArgs& g, int algo, hipStream_t st) {
+    const SbRoute& r = sb_route(g.wtype);
     if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
-    if (algo == QG_ALGO_AUTO) algo = select_algo_q6k(g);
-    if (algo == QG_ALGO_GEMV) return q6k_gemv_eligible(g) ? hip_status(launch_q6k_gemv(g, st)) : QG_ERR_UNSUPPORTED;
-    if (algo == QG_ALGO_MFMA) return q6k_mmq_eligible(g) ? hip_status(launch_q6k_mmq(g, st)) : QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_AUTO) algo = select_algo_sb(g);
+    if (algo == QG_ALGO_GEMV) return r.gemv_eligible(g) ? hip_status(r.launch_gemv(g, st)) : QG_ERR_UNSUPPORTED;
+    if (algo == QG_ALGO_MFMA) return r.mmq_eligible(g) ? hip_status(r.launch_mmq(g, st)) : QG_ERR_UNSUPPORTED;
     return QG_ERR_INVALID_ARG;
 }
 
-// The quantized product: one precheck, then the 32-element families or a super-block type's pair by the weight
+// The quantized product: one precheck, then the 32-element families or the super-block route by the weight
 // type's block size. sb_ok = false: the entries that refuse the super-block types (qg.h) -- such a type is then
 // one like any other they do not take, checked at the 32-element granule.
 int run_product(GemmArgs& g, int algo, hipStream_t st, bool sb_ok = true) {
@@ -233,7 +234,7 @@ int run_product(GemmArgs& g, int algo, hipStream_t st, bool sb_ok = true) {
                             {{g.A, ksb ? 3u : 0u}, {g.B, ksb ? sb_weight_mask(g.wtype) : 1u}, {out_ptr(g), 0}});
     if (rc != QG_GO) return rc;
     if (!ksb) return run_q32(g, algo, st);
-    return is_q6k_type(g.wtype) ? run_q6k(g, algo, st) : run_q4k(g, algo, st);
+    return run_sb(g, algo, st);
 }
 
 // what QG_ALGO_AUTO dispatches to (qg_select_algo): the same routing
@@ -241,7 +242,7 @@ int select_product_algo(const GemmArgs& g) {
     const bool ksb = is_sb_type(g.wtype);
     if (!(ksb || is_weight_type(g.wtype)) || g.K <= 0 || g.K % block_elems(g.wtype) != 0) return -1;
     if (!ksb) return select_algo(g);
-    return is_q6k_type(g.wtype) ? select_algo_q6k(g) : select_algo_q4k(g);
+    return select_algo_sb(g);
 }
 
 // The tiled weight layout (qg_tile_weights): the MFMA small-batch decode for M = 3..4 and M = 2 at K/32 > 256

@@ -1,0 +1,101 @@
+// qg_kq_launch.hpp — the host side the super-block (Q4_K, Q6_K) kernels share: instantiation choice, launch and
+// eligibility of the decode GEMV (qg_q4k_gemv.hip, qg_q6k_gemv.hip) and of the MFMA prefill (qg_q4k_mmq.hip,
+// qg_q6k_mmq.hip). The kernels themselves stay one per type ("Q4_K": what was tried to share them).
+//
+// A type's file passes a struct F of constants and static functions:
+//   GEMV:  REC_DW, LDS_MAX (dwords of an LDS record per (token, super-block), the bound on all of them), WMASK (the
+//          low bits of the weights pointer that must be 0), kernel<MT, LPR, WGS, SUMI, ONE>() and
+//          describe(g, MT, LPR, WGS, one, grid, lds), the qg_debug_config line
+//   MMQ:   NAME (the family, for the qg_debug_config line), WAVES, WMASK, kernel<TT, RG, SUMI>()
+#pragma once
+#include "qg_common.hpp"
+#include "qg_kernels.hpp"
+
+namespace qg {
+
+// ---- decode GEMV (M <= 8) ------------------------------------------------------------------------------------
+template <class F> inline size_t kq_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / SB_ELEMS) * F::REC_DW * 4; }
+
+template <class F, int MT, int LPR, int WGS, bool SUMI> hipError_t kq_gemv_launch_cfg(const GemmArgs& g, hipStream_t st) {
+    constexpr int RPB = (WGS / 64) * (64 / LPR);
+    const size_t lds = kq_gemv_lds_bytes<F>(g.M, g.K);
+    const int grid = (g.N + RPB - 1) / RPB;
+    const bool one = g.K / 64 <= LPR;
+    if (g.describe) {
+        F::describe(g, MT, LPR, WGS, (int)one, grid, lds);
+        return hipSuccess;
+    }
+    auto k = one ? F::template kernel<MT, LPR, WGS, SUMI, true>() : F::template kernel<MT, LPR, WGS, SUMI, false>();
+    if (lds > 64 * 1024) {
+        static std::atomic<unsigned long long> done[2];
+        const hipError_t e = set_max_lds_once((const void*)k, (int)F::LDS_MAX, done[one]);
+        if (e != hipSuccess) return e;
+    }
+    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, out,
+                       g.ldc_m);
+    return hipGetLastError();
+}
+
+// Lanes per row: the largest of 4 / 16 / 64 that the row's K / 64 units fill. K >= 4096: a wave per row, 16
+// rows per 1024-thread workgroup (256 workgroups at N = 4096, as the row GEMV); K >= 1024: 16 lanes, 32 rows per
+// 512-thread workgroup; below: 4 lanes, 64 rows per 256-thread workgroup.
+template <class F, int MT, bool SUMI> hipError_t kq_gemv_launch_lpr(const GemmArgs& g, hipStream_t st) {
+    const int U = g.K / 64;
+    if (U >= 64) return kq_gemv_launch_cfg<F, MT, 64, 1024, SUMI>(g, st);
+    if (U >= 16) return kq_gemv_launch_cfg<F, MT, 16, 512, SUMI>(g, st);
+    return kq_gemv_launch_cfg<F, MT, 4, 256, SUMI>(g, st);
+}
+
+template <class F, bool SUMI> hipError_t kq_gemv_launch_m(const GemmArgs& g, hipStream_t st) {
+    if (g.M <= 1) return kq_gemv_launch_lpr<F, 1, SUMI>(g, st);
+    if (g.M <= 2) return kq_gemv_launch_lpr<F, 2, SUMI>(g, st);
+    if (g.M <= 4) return kq_gemv_launch_lpr<F, 4, SUMI>(g, st);
+    return kq_gemv_launch_lpr<F, 8, SUMI>(g, st);
+}
+
+template <class F> hipError_t kq_gemv_launch(const GemmArgs& g, hipStream_t st) {
+    // the sumi hook runs the instantiation the product picks for this shape (same MT and LPR)
+    return g.sumi ? kq_gemv_launch_m<F, true>(g, st) : kq_gemv_launch_m<F, false>(g, st);
+}
+
+template <class F> bool kq_gemv_eligible(const GemmArgs& g) {
+    if (g.M < 1 || g.M > 8 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
+    if (((uintptr_t)g.B & F::WMASK) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
+    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
+    return kq_gemv_lds_bytes<F>(g.M, g.K) <= F::LDS_MAX;
+}
+
+// ---- MFMA prefill ----------------------------------------------------------------------------------------------
+template <class F, int TT, int RG, bool SUMI> hipError_t kq_mmq_launch_cfg(const GemmArgs& g, hipStream_t st) {
+    const int gx = (g.N + 16 * RG - 1) / (16 * RG), gy = (g.M + 16 * TT - 1) / (16 * TT);
+    if (g.describe) {
+        describe_kernel(g, "%s TT=%d RG=%d KS=%d grid=%dx%d", F::NAME, TT, RG, F::WAVES / RG, gx, gy);
+        return hipSuccess;
+    }
+    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
+    hipLaunchKernelGGL((F::template kernel<TT, RG, SUMI>()), dim3(gx, gy), dim3(64 * F::WAVES), 0, st, (const uint32_t*)g.A,
+                       (const uint8_t*)g.B, g.M, g.N, g.K, out, g.ldc_m);
+    return hipGetLastError();
+}
+
+template <class F, bool SUMI> hipError_t kq_mmq_launch_t(const GemmArgs& g, hipStream_t st) {
+    if (g.M <= 16) return kq_mmq_launch_cfg<F, 1, 1, SUMI>(g, st);
+    if (g.M <= 32) return kq_mmq_launch_cfg<F, 2, 1, SUMI>(g, st);
+    // 64 x 64 tiles once they fill the CUs (M = 256 at N = 4096 on a whole MI355X)
+    if ((long)((g.N + 63) / 64) * ((g.M + 63) / 64) >= device_cus()) return kq_mmq_launch_cfg<F, 4, 4, SUMI>(g, st);
+    return kq_mmq_launch_cfg<F, 4, 1, SUMI>(g, st);
+}
+
+template <class F> hipError_t kq_mmq_launch(const GemmArgs& g, hipStream_t st) {
+    return g.sumi ? kq_mmq_launch_t<F, true>(g, st) : kq_mmq_launch_t<F, false>(g, st);
+}
+
+template <class F> bool kq_mmq_eligible(const GemmArgs& g) {
+    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
+    if (((uintptr_t)g.B & F::WMASK) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
+    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
+    return (g.M + 63) / 64 <= 65535;
+}
+
+}  // namespace qg

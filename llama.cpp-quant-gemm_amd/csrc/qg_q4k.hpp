@@ -1,5 +1,5 @@
 // qg_q4k.hpp — Q4_K (ggml type 12) building blocks shared by the decode GEMV (qg_q4k_gemv.hip), the MFMA
-// prefill (qg_q4k_mmq.hip) and the dequantizer (qg_quantize.hip).
+// prefill (qg_q4k_mmq.hip) and the dequantizer (qg_quantize.hip). Launch and eligibility: qg_kq_launch.hpp.
 //
 // block_q4_K (include/qg/blocks.h), 144 B = 36 dwords, 256 elements:
 //   dword 0      f16 d | f16 dmin << 16
@@ -39,8 +39,6 @@ template <int J> __host__ __device__ __forceinline__ int q4k_byte(const uint32_t
 // Decode GEMV (M <= 8): see qg_q4k_gemv.hip. LDS per (token, super-block): 64 qs dwords, 8 x (d_a, s_a) fp32,
 // 4 pad dwords (84 = 4 x odd: the 16-B reads of lanes on consecutive super-blocks hit distinct bank groups).
 constexpr int Q4K_REC_DW = 84;
-inline size_t q4k_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / SB_ELEMS) * Q4K_REC_DW * 4; }
-constexpr size_t Q4K_GEMV_LDS_MAX = 160 * 1024;
 
 // Shape / pointer rules of the two families (K % 256 == 0 and the alignments are checked by the C-ABI first).
 bool q4k_gemv_eligible(const GemmArgs& g);

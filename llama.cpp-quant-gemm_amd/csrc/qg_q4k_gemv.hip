@@ -24,6 +24,7 @@
 //  * XCD-aware tile order on grids of one dispatch round (xcd_tile), as the row GEMV.
 //  * SUMI: the same instantiation stores each sub-block's int32 dot in place of the epilogue.
 // Argument order: everything (11 dwords) is preloaded into SGPRs by the dispatch (csrc/Makefile).
+#include "qg_kq_launch.hpp"
 #include "qg_q4k.hpp"
 
 namespace qg {
@@ -172,57 +173,23 @@ __global__ __launch_bounds__(WGS) void q4k_gemv_kernel(const uint32_t* __restric
     }
 }
 
-template <int MT, int LPR, int WGS, bool SUMI> hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
-    constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const size_t lds = q4k_gemv_lds_bytes(g.M, g.K);
-    const int grid = (g.N + RPB - 1) / RPB;
-    const bool one = g.K / 64 <= LPR;
-    if (g.describe) {
-        describe_kernel(g, "q4k_gemv MT=%d LPR=%d WGS=%d ONE=%d NT=%d grid=%d lds=%zu", MT, LPR, WGS, (int)one, QG_Q4K_NT,
-                        grid, lds);
-        return hipSuccess;
+// instantiation choice, launch and eligibility: qg_kq_launch.hpp
+struct q4k_gemv_fmt {
+    static constexpr int REC_DW = Q4K_REC_DW;
+    static constexpr size_t LDS_MAX = 160 * 1024;
+    static constexpr uintptr_t WMASK = 15;  // the 16-B loads
+    template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
+        return q4k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
     }
-    auto k = one ? q4k_gemv_kernel<MT, LPR, WGS, SUMI, true> : q4k_gemv_kernel<MT, LPR, WGS, SUMI, false>;
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> done[2];
-        const hipError_t e = set_max_lds_once((const void*)k, (int)Q4K_GEMV_LDS_MAX, done[one]);
-        if (e != hipSuccess) return e;
+    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
+        describe_kernel(g, "q4k_gemv MT=%d LPR=%d WGS=%d ONE=%d NT=%d grid=%d lds=%zu", MT, LPR, WGS, one, QG_Q4K_NT, grid,
+                        lds);
     }
-    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, out,
-                       g.ldc_m);
-    return hipGetLastError();
-}
-
-// Lanes per row: the largest of 4 / 16 / 64 that the row's K / 64 units fill. K >= 4096: a wave per row, 16
-// rows per 1024-thread workgroup (256 workgroups at N = 4096, as the row GEMV); K >= 1024: 16 lanes, 32 rows per
-// 512-thread workgroup; below: 4 lanes, 64 rows per 256-thread workgroup.
-template <int MT, bool SUMI> hipError_t launch_lpr(const GemmArgs& g, hipStream_t st) {
-    const int U = g.K / 64;
-    if (U >= 64) return launch_cfg<MT, 64, 1024, SUMI>(g, st);
-    if (U >= 16) return launch_cfg<MT, 16, 512, SUMI>(g, st);
-    return launch_cfg<MT, 4, 256, SUMI>(g, st);
-}
-
-template <bool SUMI> hipError_t launch_m(const GemmArgs& g, hipStream_t st) {
-    if (g.M <= 1) return launch_lpr<1, SUMI>(g, st);
-    if (g.M <= 2) return launch_lpr<2, SUMI>(g, st);
-    if (g.M <= 4) return launch_lpr<4, SUMI>(g, st);
-    return launch_lpr<8, SUMI>(g, st);
-}
+};
 
 }  // namespace
 
-bool q4k_gemv_eligible(const GemmArgs& g) {
-    if (g.M < 1 || g.M > 8 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
-    if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
-    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
-    return q4k_gemv_lds_bytes(g.M, g.K) <= Q4K_GEMV_LDS_MAX;
-}
-
-hipError_t launch_q4k_gemv(const GemmArgs& g, hipStream_t st) {
-    // the sumi hook runs the instantiation the product picks for this shape (same MT and LPR)
-    return g.sumi ? launch_m<true>(g, st) : launch_m<false>(g, st);
-}
+bool q4k_gemv_eligible(const GemmArgs& g) { return kq_gemv_eligible<q4k_gemv_fmt>(g); }
+hipError_t launch_q4k_gemv(const GemmArgs& g, hipStream_t st) { return kq_gemv_launch<q4k_gemv_fmt>(g, st); }
 
 }  // namespace qg

@@ -29,6 +29,7 @@
 //    two fma per output: acc = fma((d * sc_j) * d_a, float(sumi), acc); acc = fma(-(dmin * m_j), s_a, acc).
 //  * hipcc pads the MFMA results' 8 wait states (tests/test_isa_hazards.py scans this kernel too).
 //  * SUMI: the same instantiation stores each sub-block's int32 dot in place of the epilogue.
+#include "qg_kq_launch.hpp"
 #include "qg_q4k.hpp"
 
 namespace qg {
@@ -208,37 +209,17 @@ __global__ __launch_bounds__(Q4K_MMQ_WGS) void q4k_mmq_kernel(const uint32_t* __
     }
 }
 
-template <int TT, int RG, bool SUMI> hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
-    const int gx = (g.N + 16 * RG - 1) / (16 * RG), gy = (g.M + 16 * TT - 1) / (16 * TT);
-    if (g.describe) {
-        describe_kernel(g, "q4k_mmq TT=%d RG=%d KS=%d grid=%dx%d", TT, RG, Q4K_MMQ_WAVES / RG, gx, gy);
-        return hipSuccess;
-    }
-    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
-    hipLaunchKernelGGL((q4k_mmq_kernel<TT, RG, SUMI>), dim3(gx, gy), dim3(Q4K_MMQ_WGS), 0, st, (const uint32_t*)g.A,
-                       (const uint8_t*)g.B, g.M, g.N, g.K, out, g.ldc_m);
-    return hipGetLastError();
-}
-
-template <bool SUMI> hipError_t launch_t(const GemmArgs& g, hipStream_t st) {
-    if (g.M <= 16) return launch_cfg<1, 1, SUMI>(g, st);
-    if (g.M <= 32) return launch_cfg<2, 1, SUMI>(g, st);
-    // 64 x 64 tiles once they fill the CUs (M = 256 at N = 4096 on a whole MI355X)
-    if ((long)((g.N + 63) / 64) * ((g.M + 63) / 64) >= device_cus()) return launch_cfg<4, 4, SUMI>(g, st);
-    return launch_cfg<4, 1, SUMI>(g, st);
-}
+// instantiation choice, launch and eligibility: qg_kq_launch.hpp
+struct q4k_mmq_fmt {
+    static constexpr const char* NAME = "q4k_mmq";
+    static constexpr int WAVES = Q4K_MMQ_WAVES;
+    static constexpr uintptr_t WMASK = 15;  // the 16-B header loads
+    template <int TT, int RG, bool SUMI> static auto kernel() { return q4k_mmq_kernel<TT, RG, SUMI>; }
+};
 
 }  // namespace
 
-bool q4k_mmq_eligible(const GemmArgs& g) {
-    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
-    if (((uintptr_t)g.B & 15) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
-    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
-    return (g.M + 63) / 64 <= 65535;
-}
-
-hipError_t launch_q4k_mmq(const GemmArgs& g, hipStream_t st) {
-    return g.sumi ? launch_t<true>(g, st) : launch_t<false>(g, st);
-}
+bool q4k_mmq_eligible(const GemmArgs& g) { return kq_mmq_eligible<q4k_mmq_fmt>(g); }
+hipError_t launch_q4k_mmq(const GemmArgs& g, hipStream_t st) { return kq_mmq_launch<q4k_mmq_fmt>(g, st); }
 
 }  // namespace qg

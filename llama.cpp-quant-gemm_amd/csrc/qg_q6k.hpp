@@ -1,5 +1,5 @@
 // qg_q6k.hpp — Q6_K (ggml type 14) building blocks shared by the decode GEMV (qg_q6k_gemv.hip), the MFMA
-// prefill (qg_q6k_mmq.hip) and the dequantizer (qg_quantize.hip).
+// prefill (qg_q6k_mmq.hip) and the dequantizer (qg_quantize.hip). Launch and eligibility: qg_kq_launch.hpp.
 //
 // block_q6_K (include/qg/blocks.h), 210 B, 256 elements:
 //   bytes   0..127  ql[128]    low 4 bits of the codes
@@ -65,8 +65,6 @@ __device__ __forceinline__ uint32_t q6k_signed(uint32_t u) { return QG_Q6K_ASUM 
 // as fp32 (8), with QG_Q6K_ASUM the 16 half-block sums x 32 (16), 4 pad dwords (76 / 92 = 4 x odd: the 16-B reads
 // of lanes on consecutive super-blocks hit distinct bank groups).
 constexpr int Q6K_REC_DW = QG_Q6K_ASUM ? 92 : 76;
-inline size_t q6k_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / SB_ELEMS) * Q6K_REC_DW * 4; }
-constexpr size_t Q6K_GEMV_LDS_MAX = 160 * 1024;
 
 // Shape / pointer rules of the two families (K % 256 == 0 and the alignments are checked by the C-ABI first).
 bool q6k_gemv_eligible(const GemmArgs& g);

@@ -28,6 +28,7 @@
 //  * Tolerance: W = 8. An output is the sum of KS <= 8 slice partials, each an fma chain over the slice's blocks:
 //    K/32 terms of two roundings each plus at most 8 chained partial sums.
 //  * SUMI: the same instantiation stores isum in place of the epilogue.
+#include "qg_kq_launch.hpp"
 #include "qg_q6k.hpp"
 
 namespace qg {
@@ -226,37 +227,17 @@ __global__ __launch_bounds__(Q6K_MMQ_WGS) void q6k_mmq_kernel(const uint32_t* __
     }
 }
 
-template <int TT, int RG, bool SUMI> hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
-    const int gx = (g.N + 16 * RG - 1) / (16 * RG), gy = (g.M + 16 * TT - 1) / (16 * TT);
-    if (g.describe) {
-        describe_kernel(g, "q6k_mmq TT=%d RG=%d KS=%d grid=%dx%d", TT, RG, Q6K_MMQ_WAVES / RG, gx, gy);
-        return hipSuccess;
-    }
-    void* out = SUMI ? (void*)g.sumi : (void*)g.C;
-    hipLaunchKernelGGL((q6k_mmq_kernel<TT, RG, SUMI>), dim3(gx, gy), dim3(Q6K_MMQ_WGS), 0, st, (const uint32_t*)g.A,
-                       (const uint8_t*)g.B, g.M, g.N, g.K, out, g.ldc_m);
-    return hipGetLastError();
-}
-
-template <bool SUMI> hipError_t launch_t(const GemmArgs& g, hipStream_t st) {
-    if (g.M <= 16) return launch_cfg<1, 1, SUMI>(g, st);
-    if (g.M <= 32) return launch_cfg<2, 1, SUMI>(g, st);
-    // 64 x 64 tiles once they fill the CUs (M = 256 at N = 4096 on a whole MI355X)
-    if ((long)((g.N + 63) / 64) * ((g.M + 63) / 64) >= device_cus()) return launch_cfg<4, 4, SUMI>(g, st);
-    return launch_cfg<4, 1, SUMI>(g, st);
-}
+// instantiation choice, launch and eligibility: qg_kq_launch.hpp
+struct q6k_mmq_fmt {
+    static constexpr const char* NAME = "q6k_mmq";
+    static constexpr int WAVES = Q6K_MMQ_WAVES;
+    static constexpr uintptr_t WMASK = 1;  // every load is realigned
+    template <int TT, int RG, bool SUMI> static auto kernel() { return q6k_mmq_kernel<TT, RG, SUMI>; }
+};
 
 }  // namespace
 
-bool q6k_mmq_eligible(const GemmArgs& g) {
-    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % SB_ELEMS != 0) return false;
-    if (((uintptr_t)g.B & 1) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
-    if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
-    return (g.M + 63) / 64 <= 65535;
-}
-
-hipError_t launch_q6k_mmq(const GemmArgs& g, hipStream_t st) {
-    return g.sumi ? launch_t<true>(g, st) : launch_t<false>(g, st);
-}
+bool q6k_mmq_eligible(const GemmArgs& g) { return kq_mmq_eligible<q6k_mmq_fmt>(g); }
+hipError_t launch_q6k_mmq(const GemmArgs& g, hipStream_t st) { return kq_mmq_launch<q6k_mmq_fmt>(g, st); }
 
 }  // namespace qg

@@ -88,11 +88,14 @@ def gemm(aq: np.ndarray, bq: np.ndarray):
 
 
 def tol(mag: np.ndarray, k: int, w: int) -> np.ndarray:
-    """|c - C64| bound: twice the fp32 bound for K/32 + w terms; w = 0 for q4k_gemv, 16 for q4k_mmq."""
+    """|c - C64| bound of the contract: 2 (K/32 + w + 2) 2^-24 mag, twice the fp32 bound for K/32 + w terms. w = the
+    extra partial sums the kernel's reduction chains per output: 0 for q4k_gemv, q6k_gemv and the host twin (lane-serial /
+    one chain of K/32 terms), 16 for q4k_mmq, 8 for q6k_mmq (an output is the sum of at most 8 K-slice partials)."""
     return 2.0 * (k // 32 + w + 2) * 2.0 ** -24 * mag + 1e-30
 
 
 def _f16_bytes(x: np.ndarray) -> np.ndarray:
+    x = np.asarray(x)
     return np.ascontiguousarray(x.astype(np.float16)).view(np.uint8).reshape(x.shape + (2,))
 
 

@@ -12,6 +12,9 @@ from __future__ import annotations
 
 import numpy as np
 
+# shared with the Q4_K reference; re-exported: the tests take them from either module
+from kquant_ref import F16_MAX, F16_MIN_NORMAL, F16_SUBNORMALS, _f16_bytes, dev_at, tol  # noqa: F401
+
 QK_K = 256
 BYTES = 210
 Q6_K = 14
@@ -25,11 +28,6 @@ def _index_maps():
 
 
 _QL_IDX, _QL_SH, _QH_IDX, _QH_SH, _GROUP = _index_maps()
-
-
-def _f16_bytes(x: np.ndarray) -> np.ndarray:
-    x = np.asarray(x)
-    return np.ascontiguousarray(x.astype(np.float16)).view(np.uint8).reshape(x.shape + (2,))
 
 
 def fields(b: np.ndarray):
@@ -95,13 +93,6 @@ def gemm(aq: np.ndarray, bq: np.ndarray):
     return t.sum(-1), isum, np.abs(t).sum(-1)
 
 
-def tol(mag: np.ndarray, k: int, w: int) -> np.ndarray:
-    """|c - C64| bound of the contract: 2 (K/32 + w + 2) 2^-24 mag. w = the extra partial sums the kernel's reduction
-    chains per output: 0 for q6k_gemv and the host twin (lane-serial / one chain of K/32 terms), 8 for q6k_mmq (an
-    output is the sum of at most 8 K-slice partials)."""
-    return 2.0 * (k // 32 + w + 2) * 2.0 ** -24 * mag + 1e-30
-
-
 def random_q6k(rng, n: int, k: int) -> np.ndarray:
     """[n, k/256, 210]: every ql / qh / scales byte uniform in 0..255, d in +-0.01 (f16, both signs)."""
     b = rng.integers(0, 256, (n, k // QK_K, BYTES), dtype=np.uint8)
@@ -118,9 +109,6 @@ def random_q8_1(rng, m: int, k: int) -> np.ndarray:
 
 
 # f16 scale values at the ends of the format
-F16_SUBNORMALS = (2.0 ** -24, 3 * 2.0 ** -24, 2.0 ** -20, 2.0 ** -15, 1023 * 2.0 ** -24)
-F16_MIN_NORMAL = 2.0 ** -14
-F16_MAX = 65504.0
 EXTREME_ROWS = 12
 
 
@@ -179,18 +167,6 @@ def fuzz_cases(n_cases: int = 16, seed: int = 614):
         k = 256 * int(rng.integers(1, 13))
         out.append((i, m, n, k, int(rng.choice(W_OFFSETS)), int(rng.choice(A_OFFSETS))))
     return out
-
-
-def dev_at(x: np.ndarray, offset: int):
-    """x on the GPU as a contiguous slice of one flat uint8 buffer, starting `offset` bytes past a 256-B boundary."""
-    import torch
-    x = np.ascontiguousarray(x)
-    flat = torch.zeros(x.nbytes + 512 + offset, dtype=torch.uint8, device="cuda")
-    start = (-flat.data_ptr()) % 256 + offset
-    t = flat[start:start + x.nbytes]
-    t.copy_(torch.from_numpy(x.view(np.uint8).reshape(-1)))
-    assert (t.data_ptr() - offset) % 256 == 0 and t.is_contiguous()
-    return t.reshape(x.shape)
 
 
 def quantize(x: np.ndarray) -> np.ndarray:

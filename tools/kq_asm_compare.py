@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Compare the K-quant kernels of two `make asm` outputs (csrc/Makefile), instantiation by instantiation.
+
+    python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
+
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq} by their integer / bool template arguments, and compares the
+instruction text from each kernel's label to its end (symbol names, labels' function numbers and comments
+normalised away) and the kernel-resource-usage remarks. Prints one line per file and every pair that differs."""
+import re
+import sys
+from pathlib import Path
+
+FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq"]
+RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
+
+
+def key(sym):
+    """The Li<n>E / Lb<n>E template arguments of a mangled kernel name, in order."""
+    return tuple(re.findall(r"L[ib](\d+)E", sym))
+
+
+def kernels(asm):
+    """mangled name -> normalised instruction lines of every *_kernel in a .s file"""
+    out, cur = {}, None
+    for line in asm.read_text().splitlines():
+        m = re.match(r"(_Z\w*_kernel\w*):", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        if cur is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        line = re.sub(r";.*", "", line).strip()
+        if not line or line.startswith((".loc", ".file", ".cfi")):
+            continue
+        line = re.sub(r"_Z\w+", "SYM", line)
+        cur.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+    return out
+
+
+def resources(txt):
+    out, cur = {}, None
+    for line in txt.read_text().splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+        m = re.search(r":\s+([A-Za-z][^:]*): (\S+) \[-Rpass", line)
+        if m and cur is not None and m.group(1) in RES:
+            cur[m.group(1)] = m.group(2)
+    return out
+
+
+def main(parent, result):
+    bad = 0
+    for f in FILES:
+        side = []
+        for d in (Path(parent), Path(result)):
+            k = kernels(d / f"{f}-hip-amdgcn-amd-amdhsa-gfx950.s")
+            r = resources(d / f"{f}.resource.txt")
+            side.append({key(s): (s, k[s], r[s]) for s in k})
+        assert side[0].keys() == side[1].keys(), (f, sorted(side[0].keys() ^ side[1].keys()))
+        same = 0
+        for kk in sorted(side[0]):
+            (sa, ia, ra), (sb, ib, rb) = side[0][kk], side[1][kk]
+            if ia == ib and ra == rb:
+                same += 1
+                continue
+            bad += 1
+            print(f"  DIFF {sb}\n    parent {len(ia)} instr {ra}\n    result {len(ib)} instr {rb}")
+        print(f"{f}: {len(side[0])} pairs, {same} identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(*sys.argv[1:3]))
