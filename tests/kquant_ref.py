@@ -195,11 +195,12 @@ def fuzz_cases(n_cases: int = 24, seed: int = 412):
     return out
 
 
-def dev_at(x: np.ndarray, offset: int):
-    """x on the GPU as a contiguous slice of one flat uint8 buffer, starting `offset` bytes past a 256-B boundary."""
+def dev_at(x: np.ndarray, offset: int, fill: int = 0):
+    """x on the GPU as a contiguous slice of one flat uint8 buffer, starting `offset` bytes past a 256-B boundary; every
+    other byte of the buffer (at least 256 after x, `offset` or more before it) is `fill`."""
     import torch
     x = np.ascontiguousarray(x)
-    flat = torch.zeros(x.nbytes + 512 + offset, dtype=torch.uint8, device="cuda")
+    flat = torch.full((x.nbytes + 512 + offset,), fill, dtype=torch.uint8, device="cuda")
     start = (-flat.data_ptr()) % 256 + offset
     t = flat[start:start + x.nbytes]
     t.copy_(torch.from_numpy(x.view(np.uint8).reshape(-1)))

@@ -169,6 +169,26 @@ def fuzz_cases(n_cases: int = 16, seed: int = 614):
     return out
 
 
+PATH_SWEEP_M = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 24, 31, 32, 33, 48, 64, 65, 96)
+# the first seed from 600 whose 24 cases hold every M of 1..8 and MFMA cases at K > 2048 for each of TT = 1, 2, 4
+# (tests/test_q6k_cpu.py::test_path_fuzz_cases_are_seeded_and_reach_the_loops pins what the sweep needs of it)
+PATH_SWEEP_SEED = 677
+
+
+def path_fuzz_cases(n_cases: int = 24, seed: int = PATH_SWEEP_SEED):
+    """(i, m, n, k, weight byte offset, activation byte offset): the seeded sweep of tests/test_gpu_q6k_paths.py. Every
+    M tile and token-tile form, N in 1..300, K = 256 * (1..20): past 2048 the MFMA kernel's eight K slices take a
+    second pass (the prefetch and reload loop)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n_cases):
+        m = int(rng.choice(PATH_SWEEP_M))
+        n = int(rng.integers(1, 301))
+        k = 256 * int(rng.integers(1, 21))
+        out.append((i, m, n, k, int(rng.choice(W_OFFSETS)), int(rng.choice(A_OFFSETS))))
+    return out
+
+
 def quantize(x: np.ndarray) -> np.ndarray:
     """A simple test-side min/max Q6_K quantizer (for NMSE only; not ggml's): float [N, K] -> uint8 [N, K/256, 210].
     Per 16-element group scale = max|x| / 31; d = f16(max scale / 127); sc = rint(scale / d);

@@ -110,11 +110,13 @@ def test_gemv_linear_tile_order(qg, m, n, k, lpr):
 
 
 # ---------------------------------------------------------------------------- 3. MMQ RG = 4, several super-blocks
-def rg4_extent():
+def rg4_extent(cus=None):
     """The smallest ragged extent e with ceil(e / 64) * 2 >= CUs: against 65 in the other dimension it is the
-    smallest grid, ragged both ways, that the rule ceil(N / 64) * ceil(M / 64) >= CUs sends to RG = 4."""
-    import torch
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    smallest grid, ragged both ways, that the rule ceil(N / 64) * ceil(M / 64) >= CUs sends to RG = 4. `cus`: the
+    device's count unless given (the routing tests that run without a GPU give the library's answer there, 256)."""
+    if cus is None:
+        import torch
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
     return 64 * ((cus + 1) // 2 - 1) + 1, cus
 
 
@@ -149,6 +151,34 @@ def test_mmq_rg1_edges(qg, m, n, k, tt, grid):
     K slices (K = 4096), four token tiles in gridDim.y."""
     cfg = qg.debug_config(m, n, k, Q4_K)
     assert f"q4k_mmq TT={tt} RG=1 KS=8 grid={grid}" == cfg, cfg
+    aq, bq, *ref = case(m, n, k)
+    check(qg, aq, bq, ref, "q4k_mmq")
+
+
+LINEAR_N_RG1, LINEAR_N_RG4 = 16 * 512 + 1, 64 * 512 + 1  # 513 tiles of 16 and of 64 weight rows
+
+
+def linear_rg4_m(qg, wtype, n=LINEAR_N_RG4, k=256):
+    """M for the 513 x gy grid of 64 x 64 tiles: 33 where 513 tiles fill the device (ceil(N / 64) * ceil(M / 64) >=
+    CUs), otherwise grown in steps of 64 until the dispatch picks RG = 4."""
+    m = 33
+    while "RG=4" not in qg.debug_config(m, n, k, wtype):
+        m += 64
+        assert m <= 33 + 64 * 8, "no RG = 4 grid of 513 tiles on this device"
+    return m
+
+
+@pytest.mark.parametrize("rg", [1, 4])
+def test_mmq_linear_tile_order(qg, rg):
+    """gridDim.x = 513: past one dispatch round the tiles are taken in linear order, in the 16-row and the 64-row form."""
+    k = 256
+    if rg == 1:
+        m, n, want = 9, LINEAR_N_RG1, "q4k_mmq TT=1 RG=1 KS=8 grid=513x1"
+    else:
+        m, n = linear_rg4_m(qg, Q4_K), LINEAR_N_RG4
+        want = f"q4k_mmq TT=4 RG=4 KS=2 grid=513x{(m + 63) // 64}"
+    cfg = qg.debug_config(m, n, k, Q4_K)
+    assert cfg == want, cfg
     aq, bq, *ref = case(m, n, k)
     check(qg, aq, bq, ref, "q4k_mmq")
 

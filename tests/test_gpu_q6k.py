@@ -13,6 +13,8 @@ row starts aligned with odd super-blocks shifted; N = 1 / 15 / 17 / 33 leave par
     LPR=64 ONE=1   K = 4096           LPR=64 ONE=0   K = 4352;   M = 8, K = 6912: LDS records above 64 KiB
   q6k_mmq  TT=1 RG=1 M = 9, 16 (and the forced M = 8)   TT=2 RG=1 M = 17   TT=4 RG=1 M = 33, 64
            TT=4 RG=4 M = 65, N = 8200 (130 x 2 tiles of 64 x 64 fill 256 CUs)
+  tests/test_gpu_q6k_paths.py: RG=4 with data in both K slices, the prefetch loops, gridDim.y > 1, grids past 512
+    workgroups, the LDS classes at 160 KiB, M inside a tile x every form, outputs inside guards, the bytes around the tensors
 """
 import functools
 

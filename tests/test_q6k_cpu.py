@@ -222,11 +222,58 @@ def test_every_instantiation_has_a_shape():
     for m, n, k in T.all_product_shapes():
         cfg = qg.debug_config(m, n, k, Q6_K)
         seen.add(" ".join(w for w in cfg.split() if w.split("=")[0] in ("q6k_gemv", "q6k_mmq", "MT", "LPR", "ONE", "TT", "RG")))
-    gemv = {f"q6k_gemv MT={mt} LPR={lpr} ONE={one}" for mt in (1, 2, 4, 8) for lpr, one in ((4, 1), (4, 0), (16, 0), (64, 1))}
-    # (LPR = 16 is K = 1024..4032, always more than 16 units: ONE = 0; LPR = 64 with a unit loop is K > 4096)
-    assert gemv <= seen, sorted(gemv - seen)
-    assert {"q6k_gemv MT=1 LPR=64 ONE=0"} <= seen
+    gemv = {f"q6k_gemv MT={mt} LPR={lpr} ONE={one}" for mt in (1, 2, 4, 8) for lpr in (4, 16, 64) for one in (1, 0)}
+    # (ONE = 1 is K / 64 <= LPR, one unit per lane: K = 256 at LPR = 4, K = 1024 at LPR = 16, K = 4096 at LPR = 64;
+    # every other K of a form runs the unit loop)
+    assert len(gemv) == 24 and gemv <= seen, sorted(gemv - seen)
     assert {f"q6k_mmq TT={tt} RG=1" for tt in (1, 2, 4)} | {"q6k_mmq TT=4 RG=4"} <= seen, sorted(seen)
+
+
+def _visible_cus():
+    """None (ask the device) where a GPU is visible, else 256, the library's answer without one."""
+    try:
+        import torch
+        return None if torch.cuda.is_available() else 256
+    except ImportError:
+        return 256
+
+
+def test_path_tables_reach_what_their_tests_name():
+    """The shape tables of tests/test_gpu_q6k_paths.py against debug_config alone: each shape reaches the instantiation,
+    grid and LDS size its GPU test names, and the refusals are refusals."""
+    import quant_gemm as qg
+    import test_gpu_q6k_paths as T
+    rows = T.path_table(qg, _visible_cus())
+    assert len(rows) == len(set(rows)) and len(rows) > 70
+    for m, n, k, algo, exact, needles in rows:
+        cfg = qg.debug_config(m, n, k, Q6_K, algo=algo)
+        T.assert_config(cfg, exact, needles)
+        assert cfg == qg.debug_config(m, n, k, Q6_K, algo=algo, sumi=True)
+    for m, n, k, lds in T.GEMV_LDS_TOP:
+        assert lds == m * (k // 256) * 304 <= 160 * 1024 < m * (k // 256 + 1) * 304
+    for m, n, k in T.GEMV_LDS_OVER:
+        assert qg.select_algo(m, n, k, Q6_K) == 2
+        with pytest.raises(RuntimeError, match="unsupported"):
+            qg.debug_config(m, n, k, Q6_K, algo=1)
+    # the 64 x 64 form against this device's CUs: the extent one tile column short stays in the 16-row form
+    m, n, k, _ = T.rg4_shapes(_visible_cus())[0]
+    assert " RG=1 " in qg.debug_config(m, n - 64, k, Q6_K)
+    # what each loop case is there for: passes of the eight (RG = 1) or two (RG = 4) K slices
+    passes = {(m, n, k): -(-(k // 256) // 8) for m, n, k, _ in T.MMQ_RG1_EDGES}
+    assert passes[(9, 32, 4096)] == 2 and passes[(31, 33, 2304)] == 2 and passes[(20, 17, 4352)] == 3
+    assert [-(-(k // 256) // 2) for k in T.RG4_K] == [2, 2, 3]
+
+
+def test_path_fuzz_cases_are_seeded_and_reach_the_loops():
+    cases = QR.path_fuzz_cases()
+    assert cases == QR.path_fuzz_cases() and len(cases) == 24
+    assert all(m in QR.PATH_SWEEP_M and 1 <= n <= 300 and k % 256 == 0 and 256 <= k <= 5120 for _, m, n, k, _, _ in cases)
+    assert {w for *_, w, _ in cases} == set(QR.W_OFFSETS) and {a for *_, a in cases} == set(QR.A_OFFSETS)
+    ms = [m for _, m, *_ in cases]
+    assert sum(m <= 8 for m in ms) >= 6 and sum(m >= 9 for m in ms) >= 6
+    assert 8 * 20 * 304 <= 160 * 1024  # every M <= 8 case is the GEMV's
+    deep = [m for _, m, _, k, _, _ in cases if m >= 9 and k > 2048]  # MFMA cases with a second pass of the K slices
+    assert len(deep) >= 3 and any(17 <= m <= 32 for m in deep), deep
 
 
 # ---------------------------------------------------------------------------- the view entry
