@@ -40,7 +40,8 @@ typedef enum {
     QG_TYPE_Q8_0 = 8,
     QG_TYPE_Q8_1 = 9,
     QG_TYPE_Q4_K = 12, /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
-    QG_TYPE_Q6_K = 14  /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
+    QG_TYPE_Q6_K = 14, /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
+    QG_TYPE_I32 = 26   /* int32 elements: the ids view of qg_mul_mat_id_from_view, nothing else */
 } qg_type;
 
 typedef enum {
@@ -292,7 +293,8 @@ int qg_gemm_w4a8_strided_batched(const void* A_q8_1, int64_t strideA, const void
                                  int64_t strideC, int batch, int M, int N, int K, int wtype, qg_stream_t stream);
 
 /* Grouped products with independent pointers and row counts (a decoder layer's Q / K / V or
- * gate / up projections; the experts an MoE step selects): item i computes
+ * gate / up projections; the experts an MoE step selects, when the HOST knows them -- ids that live on the
+ * device: qg_gemm_w4a8_moe below): item i computes
  * C_i[m * ldc_i + n] = A_i[M][K] . B_i[N_i][K]^T (ldc_i = 0 means N_i). One M, K and weight type for
  * the group. Where QG_ALGO_AUTO picks the GEMV for every item (M <= 4 at aligned shapes), up to 64
  * items go out in ONE launch (the descriptor travels in the kernel arguments: no device
@@ -308,6 +310,45 @@ typedef struct {
     int ldc;             /* output row stride in floats, 0 = N */
 } qg_gemv_item;
 int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, qg_stream_t stream);
+
+/* ---- expert-indexed decode GEMV: ggml_mul_mat_id for a decode step, ids read on the device ----
+ * Slot s = t * n_used + u (t < T, u < n_used):
+ *   e = ids[t * ids_stride + u]
+ *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k]      (n < N)
+ * B_experts: n_expert dense matrices [N][K/bs] of `wtype`, one after another (ggml's [K, N, n_expert]); any of
+ *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K (bs = 256).
+ * A: block_q8_1 [T][a_rows][K/32], a_rows == 1 (gate / up: one row per token, shared by its slots) or
+ *    a_rows == n_used (down: one row per slot).
+ * ids: int32 in DEVICE memory, read by the kernel; ids_stride >= n_used elements between tokens (ggml's top-k
+ *    result is a view with row stride n_expert).
+ * C: float, ldc floats between slots, 0 = N.
+ * A slot whose id is outside [0, n_expert) reads no weight byte and writes N times +0.0f (an expert-parallel rank
+ * passes ids - first_local_expert and sums the ranks' outputs).
+ * ONE launch for all T * n_used slots (the slot is a grid dimension), one workgroup-uniform load of the id per
+ * workgroup. The host never reads ids; no device allocation, no synchronisation: capture-safe, and a captured
+ * graph follows the ids its replay finds in the buffer. Captured, the call is a plain kernel node: the
+ * capture-time merge of qg_gemm_w4a8 neither absorbs it nor merges across it.
+ * Bits: each slot's N outputs are bit-identical to qg_gemm_w4a8(A_row, B_experts + e * N * K/bs * block_bytes,
+ * C_row, 1, N, K, wtype, stream) called eagerly, so each inherits that product's documented bound; two launches
+ * give identical bits.
+ * Served shapes: those where QG_ALGO_AUTO at M = 1 picks the decode GEMV of the type ("gemv", "q4k_gemv",
+ * "q6k_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32; LDS records of the activation
+ * row beyond 160 KiB (Q4_K: K > 124672, Q6_K: K > 137728, the 32-element types: K > 93568); an expert stride
+ * N * K/bs * block_bytes off the kernel's weight alignment; more than 65535 slots.
+ * Validation, in the order of every entry: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive
+ * multiple of bs -> QG_ERR_BAD_K; wtype -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched;
+ * a null pointer -> QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A and ids 4 B; B 4 B for the 32-element types,
+ * 16 B for Q4_K, 2 B for Q6_K). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
+ * 0 < ldc < N -> QG_ERR_INVALID_ARG (after the precheck: an empty call is a no-op whatever they are), then the
+ * unsupported shapes above.
+ * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
+ * 256-B aligned buffers, launch-free; the same status codes for the shape.
+ * Not built: prefill-size T (sorting tokens by expert for the MFMA kernels), slots of different
+ * tokens sharing one pass over an expert they both chose, tiled-layout experts, FP32 activations. */
+int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                     int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                     qg_stream_t stream);
+int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -403,6 +444,15 @@ int qg_gemm_w4a16_from_view(const qg_tensor_view* activation, const qg_tensor_vi
 /* gemm_fp32_from_ggml (llama_adapter.h:92-103): all three F32. */
 int qg_gemm_fp32_from_view(const qg_tensor_view* activation, const qg_tensor_view* weights, qg_tensor_view* output,
                            const char* kernel_type, qg_stream_t stream);
+/* ggml_mul_mat_id(as, b, ids) -> out on views, mapped onto qg_gemm_w4a8_moe:
+ *   as:  weights, ne = [K, N, n_expert], dense rows and nb[2] = N * row bytes (the dense expert stride);
+ *   b:   Q8_1, ne = [K, a_rows, T], dense; a_rows 1 or n_used (ggml's wider broadcast is not served);
+ *   ids: I32 (QG_TYPE_I32), ne = [n_used, T], nb[0] = 4, nb[1] a multiple of 4 (a strided top-k view is fine);
+ *   out: F32, ne = [N, n_used, T], nb[0] = 4, nb[1] a multiple of 4 and >= 4 N, nb[2] = n_used * nb[1].
+ * A view the entry cannot express (other strides, ne[3] > 1) is QG_ERR_UNSUPPORTED; mismatched dims are
+ * QG_ERR_INVALID_ARG. */
+int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                            qg_tensor_view* out, qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

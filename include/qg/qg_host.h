@@ -46,6 +46,14 @@ int qg_gemm_w8a8_cpu(const void* A_q8_1, const void* B_q8_0, float* C, int M, in
  * identical for every thread count (threads split the weight rows only). */
 int qg_gemm_w4a8_cpu_mt(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, int threads);
 
+/* Host twin of qg_gemm_w4a8_moe (qg.h): the same arguments with `ids` in host memory, and `threads` as above.
+ * Slot s = t * n_used + u takes expert e = ids[t * ids_stride + u]; its N outputs at C + s * ldc (0 = N) are
+ * bit-identical to qg_gemm_w4a8_cpu_mt on (A row t * a_rows + u % a_rows, expert e) with M = 1, for every thread
+ * count; an id outside [0, n_expert) gives N times +0.0f. The same validation codes; no shape is unsupported. */
+int qg_gemm_w4a8_moe_cpu(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                         int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                         int threads);
+
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */
 int qg_gemm_fp32_cpu(const float* A, const float* B, float* C, int M, int N, int K);
 

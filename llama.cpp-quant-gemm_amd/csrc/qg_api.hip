@@ -388,9 +388,82 @@ int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
     }
     return QG_ERR_UNSUPPORTED;
 }
+// qg_gemm_w4a8_moe and qg_moe_config (describe): the precheck in its order, then what is specific to the entry
+// (a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG), then the shapes the expert-indexed GEMV does not serve
+// (QG_ERR_UNSUPPORTED): more than 65535 slots, a shape AUTO at M = 1 does not send to the type's decode GEMV, LDS
+// records beyond 160 KiB, an expert stride off the kernel's weight alignment. ids is never read here.
+int run_moe(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride, float* C,
+            int64_t ldc, int T, int n_used, int N, int K, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    const bool ksb = is_sb_type(wtype);
+    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
+    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb || is_weight_type(wtype),
+                            {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
+    if (rc != QG_GO) return rc;
+    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
+        return QG_ERR_INVALID_ARG;
+    const int64_t slots = (int64_t)T * n_used;
+    if (slots > 65535) return QG_ERR_UNSUPPORTED;
+    const GemmArgs q = product_args(A, B, C, 1, N, K, wtype);
+    if (ksb ? select_algo_sb(q) != QG_ALGO_GEMV : !(select_algo(q) == QG_ALGO_GEMV && gemv_eligible(q)))
+        return QG_ERR_UNSUPPORTED;
+    MoeArgs a;
+    a.A = A; a.B = B; a.ids = ids; a.C = C;
+    a.ids_stride = (long)ids_stride;
+    a.ldc = ldc ? (long)ldc : (long)N;
+    a.arow = (long)(K / 32) * 36;
+    a.estride = (long)N * (long)(K / block_elems(wtype)) * block_bytes(wtype);
+    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
+    if (!moe_lds_ok(wtype, K) || ((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
+    return hip_status(launch_moe(a, wtype, st, describe, describe_len));
+}
 }  // namespace
 
 extern "C" {
+
+int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                     int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                     qg_stream_t stream) {
+    return run_moe(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype,
+                   (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    // the shape alone, as qg_debug_config: 256-B aligned stand-in pointers, one activation row per token
+    return run_moe((const void*)256, 1, (const void*)256, 1, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
+                   wtype, nullptr, buf, len);
+}
+
+int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                            qg_tensor_view* out, qg_stream_t stream) {
+    if (!as || !b || !ids || !out) return QG_ERR_INVALID_ARG;
+    if (b->type != QG_TYPE_Q8_1 || ids->type != QG_TYPE_I32 || out->type != QG_TYPE_F32 ||
+        !(is_weight_type(as->type) || is_sb_type(as->type)))
+        return QG_ERR_UNSUPPORTED;
+    auto one = [](int64_t v) { return v == 1 || v == 0; };
+    if (!one(as->ne[3]) || !one(b->ne[3]) || !one(ids->ne[2]) || !one(ids->ne[3]) || !one(out->ne[3])) return QG_ERR_UNSUPPORTED;
+    const int64_t K = as->ne[0], N = as->ne[1], n_expert = as->ne[2], a_rows = b->ne[1], T = b->ne[2], n_used = ids->ne[0];
+    if (b->ne[0] != K || ids->ne[1] != T || out->ne[0] != N || out->ne[1] != n_used || out->ne[2] != T)
+        return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % block_elems(as->type) != 0) return QG_ERR_BAD_K;
+    if (T > INT32_MAX || n_used > INT32_MAX || N > INT32_MAX || K > INT32_MAX || n_expert > INT32_MAX || a_rows > INT32_MAX)
+        return QG_ERR_UNSUPPORTED;
+    // dense weight rows and experts, dense activation rows and tokens, ids rows a whole number of int32 apart, output
+    // rows a whole number of floats apart with the token's slots one after another
+    const size_t wrow = row_bytes(as->type, K), arow = row_bytes(QG_TYPE_Q8_1, K);
+    if ((N > 1 && as->nb[1] != wrow) || (n_expert > 1 && as->nb[2] != (size_t)N * wrow) ||
+        (a_rows > 1 && b->nb[1] != arow) || (T > 1 && b->nb[2] != (size_t)a_rows * arow) ||
+        (n_used > 1 && ids->nb[0] != sizeof(int32_t)) || (T > 1 && ids->nb[1] % sizeof(int32_t) != 0) ||
+        out->nb[0] != sizeof(float) || (n_used > 1 && T > 1 && out->nb[2] != (size_t)n_used * out->nb[1]))
+        return QG_ERR_UNSUPPORTED;
+    const size_t slot_bytes = n_used > 1 ? out->nb[1] : T > 1 ? out->nb[2] : (size_t)N * sizeof(float);
+    if (slot_bytes % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
+    const int64_t ids_stride = T > 1 ? (int64_t)(ids->nb[1] / sizeof(int32_t)) : n_used;
+    const int64_t ldc = (int64_t)(slot_bytes / sizeof(float));
+    return qg_gemm_w4a8_moe(b->data, (int)a_rows, as->data, (int)n_expert, (const int32_t*)ids->data, ids_stride,
+                            (float*)out->data, ldc, (int)T, (int)n_used, (int)N, (int)K, as->type, stream);
+}
 
 void qg_release_workspaces(void) { release_workspaces(); }
 

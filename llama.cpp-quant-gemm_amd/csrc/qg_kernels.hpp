@@ -111,6 +111,22 @@ hipError_t launch_or_merge_gemv(const GemmArgs& g, hipStream_t st);
 void set_capture_fusion(int on);                                // qg_set_capture_fusion
 void capture_fusion_stats(uint64_t* merged, uint64_t* nodes);   // qg_capture_fusion_stats
 
+// The expert-indexed decode GEMV (qg_gemm_w4a8_moe; qg_moe.hip): slot s = t * n_used + u of the launch's grid.y reads
+// its expert e = ids[t * ids_stride + u] on the device and computes the M = 1 product of activation row
+// t * a_rows + u % a_rows with expert e's matrix into C + s * ldc. Passed by value as the kernel argument.
+struct MoeArgs {
+    const void* A;       // block_q8_1 [T][a_rows][K/32]
+    const void* B;       // n_expert matrices [N][K/bs], estride bytes apart
+    const int32_t* ids;  // device memory
+    float* C;
+    long ids_stride, ldc, estride, arow;  // elements, floats, bytes, bytes of one activation row
+    int a_rows, n_used, n_expert, N, K, slots;
+};
+// describe: name the kernel there (qg_moe_config) and launch nothing. The caller has checked that AUTO at M = 1
+// takes the GEMV of the type (gemv_eligible, q4k_/q6k_gemv_eligible) and moe_lds_ok.
+hipError_t launch_moe(const MoeArgs& a, int wtype, hipStream_t st, char* describe = nullptr, size_t describe_len = 0);
+bool moe_lds_ok(int wtype, int K);
+
 // The decode GEMV (M <= 4) on the tiled layout (qg_gemvt.hip, round 6): waves of 16 rows x 4 stages reading
 // whole 256-B plane runs, the row kernel's dot and per-block terms (bit-identical per block to the
 // reference's), fixed summation order. run_tiled sends it M = 1..2 up to K/32 = 256; M = 3..4 only in builds

@@ -309,6 +309,44 @@ int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, in
     return QG_ERR_UNSUPPORTED;
 }
 
+int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
+                         float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
+    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    int bb = 0;
+    switch (wtype) {
+        case QG_TYPE_Q4_0: bb = FmtQ4_0::bytes; break;
+        case QG_TYPE_Q4_1: bb = FmtQ4_1::bytes; break;
+        case QG_TYPE_Q5_0: bb = FmtQ5_0::bytes; break;
+        case QG_TYPE_Q5_1: bb = FmtQ5_1::bytes; break;
+        case QG_TYPE_Q8_0: bb = FmtQ8_0::bytes; break;
+        case QG_TYPE_Q4_K: bb = FmtQ4_K::bytes; break;
+        case QG_TYPE_Q6_K: bb = FmtQ6_K::bytes; break;
+    }
+    // the order of qg_gemm_w4a8_moe
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % (ksb ? 256 : QK) != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
+    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
+        return QG_ERR_INVALID_ARG;
+    const size_t arow = (size_t)(K / QK) * 36, estride = (size_t)N * (size_t)(K / (ksb ? 256 : QK)) * (size_t)bb;
+    if (ldc == 0) ldc = N;
+    for (int t = 0; t < T; ++t)
+        for (int u = 0; u < n_used; ++u) {
+            const int e = ids[(int64_t)t * ids_stride + u];
+            float* c = C + ((int64_t)t * n_used + u) * ldc;
+            if (e < 0 || e >= n_expert) {
+                for (int n = 0; n < N; ++n) c[n] = 0.0f;
+                continue;
+            }
+            const uint8_t* a = (const uint8_t*)A + ((size_t)t * a_rows + (size_t)(u % a_rows)) * arow;
+            const int rc = qg_gemm_w4a8_cpu_mt(a, (const uint8_t*)B + (size_t)e * estride, c, 1, N, K, wtype, threads);
+            if (rc != QG_OK) return rc;
+        }
+    return QG_OK;
+}
+
 int qg_gemm_w4a8_q4_0_cpu(const void* A, const void* B, float* C, int M, int N, int K) {
     return qg_gemm_w4a8_cpu_mt(A, B, C, M, N, K, QG_TYPE_Q4_0, 1);
 }

@@ -225,6 +225,57 @@ def gemm_w4a8_grouped(activations_q, weights_q, Ns, M: int, K: int, wtype: int =
     return res
 
 
+def gemm_w4a8_moe(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor, T: int, n_used: int, N: int,
+                  K: int, wtype: int = Q4_0, a_rows: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ggml's mul_mat_id for a decode step in ONE launch, the expert ids read on the device (qg_gemm_w4a8_moe):
+    C[t, u, :] = experts_q[ids[t, u]] . activation_q[t, u % a_rows], float32 [T, n_used, N].
+
+    ``activation_q``: Q8_1 [T, a_rows, K/32, 36], a_rows 1 (one row per token) or n_used (one per slot).
+    ``experts_q``: [n_expert, N, K/bs, block bytes] of ``wtype`` (any of GEMM_WEIGHT_TYPES), dense.
+    ``ids``: int32 CUDA tensor [T, n_used]; a view with a row stride is fine (``ids.stride(1) == 1``). Never copied
+    to the host: a captured graph follows the ids each replay finds. An id outside [0, n_expert) gives zeros.
+    ``out``: optional float32 [T, n_used, N] with ``out.stride(2) == 1``, ``out.stride(1) >= N`` floats between
+    slots and ``out.stride(0) == n_used * out.stride(1)``.
+    Each slot is bit-identical to ``gemm_w4a8`` on its row and expert. Shapes the expert-indexed GEMV does not
+    serve (odd K/32, more than 65535 slots, ...) raise."""
+    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
+    be = block_elems(wtype)
+    _require(K % be == 0, f"K must be divisible by {be}, got {K}")
+    _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
+    _check_blocks(activation_q, "Activation", T * a_rows, K, 36)
+    _require(experts_q.is_cuda and experts_q.dtype == torch.uint8, "Experts must be a CUDA uint8 tensor")
+    per = N * (K // be) * BLOCK_BYTES[wtype]
+    _require(per > 0 and experts_q.numel() % per == 0 and experts_q.numel() >= per,
+             f"Experts shape mismatch: {experts_q.numel()} bytes is no multiple of {per}")
+    n_expert = experts_q.numel() // per
+    _require(ids.is_cuda and ids.dtype == torch.int32 and ids.device == experts_q.device, "ids must be an int32 tensor on the experts' device")
+    _require(ids.dim() == 2 and tuple(ids.shape) == (T, n_used) and (n_used <= 1 or ids.stride(1) == 1),
+             "ids must be [T, n_used] with unit column stride")
+    ids_stride = ids.stride(0) if T > 1 else n_used
+    _require(ids_stride >= n_used, "ids row stride below n_used")
+    a, w = activation_q.contiguous(), experts_q.contiguous()
+    if out is None:
+        out = torch.empty((T, n_used, N), dtype=torch.float32, device=w.device)
+    else:
+        _require(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, n_used, N), "bad out tensor")
+        _require(out.device == w.device, "out must be on the experts' device")
+        _require(N <= 1 or out.stride(2) == 1, "bad out tensor: rows must be dense")
+    ldc = out.stride(1) if n_used > 1 else out.stride(0) if T > 1 else N
+    _require(ldc >= N and (T <= 1 or n_used <= 1 or out.stride(0) == n_used * ldc), "bad out tensor: slots must be evenly spaced")
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe(_ptr(a), a_rows, _ptr(w), n_expert, _ptr(ids), ids_stride, _ptr(out), ldc,
+                                                T, n_used, N, K, wtype, _stream(w.device)), "gemm_w4a8_moe")
+    return out
+
+
+def moe_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_0) -> str:
+    """The kernel ``gemm_w4a8_moe`` launches for this shape ("moe:<family> ..." with the family and the LPR / BPL /
+    ONE(U) of ``debug_config(1, N, K, wtype)``); nothing is launched. Raises where the shape is not served."""
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().qg_moe_config(T, n_used, N, K, wtype, buf, 256), "moe_config")
+    return buf.value.decode()
+
+
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
     """Load-time layout for K/32 not a multiple of 8 (qg_repack_weights): [N, K'/32, bb] uint8,
     the real blocks then zero blocks (K'/32 = round_up(K/32, 8)). Feed it to gemm_w4a8_prepacked."""
@@ -607,4 +658,5 @@ __all__ = [
     "quantize_q8_1_tiled", "tile_activations", "gemm_w4a8_tiled_act", "debug_sumi_tiled_act", "debug_config_tiled_act",
     "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "Q6_K", "block_elems",
     "set_capture_fusion", "capture_fusion_stats",
+    "gemm_w4a8_moe", "moe_config",
 ]

@@ -20,6 +20,7 @@ from . import _lib
 
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
 Q4_K, Q6_K = 12, 14
+I32 = 26  # the ids of mul_mat_id_from_ggml
 _BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210}
 _BE = {Q4_K: 256, Q6_K: 256}  # elements per block where it is not 32 (qg_block_elems)
 # the block types the GGUF reader serves (its own list: a Q6_K tensor is listed, not readable); views of bytes the
@@ -62,6 +63,14 @@ def gemm_w4a16_from_ggml(act: TensorView, w: TensorView, out: TensorView, kernel
 def gemm_fp32_from_ggml(act: TensorView, w: TensorView, out: TensorView, kernel_type: str | None = "naive") -> None:
     """include/llama_adapter.h:92-103: all F32."""
     _call("qg_gemm_fp32_from_view", act, w, out, kernel_type)
+
+
+def mul_mat_id_from_ggml(experts: TensorView, act: TensorView, ids: TensorView, out: TensorView) -> None:
+    """ggml_mul_mat_id on views (qg_mul_mat_id_from_view): experts [K, N, n_expert], Q8_1 act [K, a_rows, T], I32
+    ids [n_used, T] on the device (a strided top-k view is fine), F32 out [N, n_used, T]."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().qg_mul_mat_id_from_view(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
+                                                   ctypes.byref(out), st), "qg_mul_mat_id_from_view")
 
 
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:

@@ -19,6 +19,7 @@ SIGNATURES = {
     "qg_vec_dot_q8_0_q8_1_cpu": ([I, P, P, P], None),
     "qg_gemm_w8a8_cpu": ([P, P, P, I, I, I], I),
     "qg_gemm_w4a8_cpu_mt": ([P, P, P, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_fp32_cpu": ([P, P, P, I, I, I], I),
     "qg_quantize_row_q8_1_cpu": ([P, P, I64], I),
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
@@ -80,6 +81,23 @@ def gemm_w4a8(a_q: np.ndarray, b_q: np.ndarray, m: int, n: int, k: int, wtype: i
     c = np.empty((m, n), np.float32)
     a_q, b_q = np.ascontiguousarray(a_q), np.ascontiguousarray(b_q)
     _ok(load().qg_gemm_w4a8_cpu_mt(_p(a_q), _p(b_q), _p(c), m, n, k, wtype, threads), "gemm_w4a8_cpu")
+    return c
+
+
+def gemm_w4a8_moe(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, t: int, n_used: int, n: int, k: int,
+                  wtype: int = 2, a_rows: int = 1, threads: int = 1, ids_stride: int | None = None) -> np.ndarray:
+    """C[t, n_used, n] of qg_gemm_w4a8_moe_cpu: slot (t, u) = activation row t * a_rows + u % a_rows times expert
+    ids[t, u] of ``experts_q`` (n_expert matrices, one after another). ``ids``: int32 [t, ids_stride] (the
+    stride defaults to the array's row length); an id outside [0, n_expert) gives zeros."""
+    a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    be = 256 if wtype in (12, 14) else 32
+    n_expert = experts_q.size // (n * (k // be) * BLOCK_BYTES[wtype])
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    c = np.empty((t, n_used, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_cpu(_p(a_q), a_rows, _p(experts_q), n_expert, _p(ids), ids_stride, _p(c), n, t, n_used, n,
+                                    k, wtype, threads), "gemm_w4a8_moe_cpu")
     return c
 
 
