@@ -343,12 +343,66 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
  * unsupported shapes above.
  * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
  * 256-B aligned buffers, launch-free; the same status codes for the shape.
- * Not built: prefill-size T (sorting tokens by expert for the MFMA kernels), slots of different
- * tokens sharing one pass over an expert they both chose, tiled-layout experts, FP32 activations. */
+ * Prefill-size T of Q4_K / Q6_K experts: qg_gemm_w4a8_moe_prefill below (this entry streams the slot's whole
+ * expert matrix for every slot).
+ * Not built: prefill-size T for the five 32-element types, slots of different tokens sharing one
+ * pass over an expert they both chose within this decode entry, tiled-layout experts, FP32 activations. */
 int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                      int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                      qg_stream_t stream);
 int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- expert-grouped MFMA prefill: ggml_mul_mat_id at prompt sizes, ids sorted on the device ----
+ * The operands, the slot numbering s = t * n_used + u, a_rows, ids_stride and ldc (0 = N) are those of
+ * qg_gemm_w4a8_moe above, and so is the result:
+ *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k],   e = ids[t * ids_stride + u]
+ * and a slot whose id is outside [0, n_expert) reads no weight byte and gets N times +0.0f.
+ * Two launches: a plan kernel counting-sorts the slots by expert id into `workspace` (counts, the slots in expert
+ * order, one record per tile of R = 16, 32 or 64 rows of one expert), then one MFMA launch runs the Q4_K / Q6_K
+ * prefill body on every tile, its activation rows gathered and its output rows scattered through the sorted list:
+ * an expert's matrix is read once per tile of R slots instead of once per slot. The MFMA launch's grid is the
+ * host's upper bound floor(slots / R) + min(n_expert + 1, slots) on the number of tiles; workgroups past the true
+ * number return at once.
+ * The host never reads ids; no allocation, no synchronisation: capture-safe (two kernel nodes), and a replayed graph
+ * follows the ids it finds, with another number of rows per expert and of tiles on every replay.
+ * Bits: an output's arithmetic is that of the "q4k_mmq" / "q6k_mmq" family at the call's RG (qg_moe_prefill_config)
+ * on its own activation row and weight row; it does not depend on the tile's size or on where the sort put the
+ * slot, so two launches give identical bits and each output inherits the MFMA prefill's documented bound.
+ * Served: wtype QG_TYPE_Q4_K or QG_TYPE_Q6_K (the five 32-element types: QG_ERR_UNSUPPORTED), K % 256 == 0,
+ * n_expert <= 4096, at most 65535 slots, any N. QG_ERR_UNSUPPORTED beyond, and for an expert stride
+ * N * K/256 * block_bytes off the kernel's weight alignment (16 B for Q4_K, never for Q6_K).
+ * workspace: device memory, 16-B aligned, at least qg_gemm_w4a8_moe_prefill_workspace_size(T, n_used, n_expert)
+ * bytes (a function of these three alone, monotone in each; 0 where one of them is <= 0). It holds only what the
+ * plan writes: the call reads nothing from it that the same call has not written, so its previous content is
+ * arbitrary. In use until the call's kernels finish: calls on one stream may share it, concurrent streams need one
+ * each.
+ * Validation: the order of qg_gemm_w4a8_moe (precheck with the type check -- here Q4_K / Q6_K only -- then a_rows /
+ * ids_stride / n_expert / ldc), then workspace == NULL -> QG_ERR_INVALID_ARG, workspace off 16 B -> QG_ERR_ALIGN,
+ * workspace_bytes below the size function -> QG_ERR_INVALID_ARG, then the unsupported shapes. An empty call (T,
+ * n_used or N equal to 0) is QG_OK and touches nothing, whatever the later arguments are.
+ * qg_moe_prefill_config names the launch ("moe:q4k_mmq" / "moe:q6k_mmq", TT, RG, KS, R = 16 TT rows per tile, grid =
+ * row tiles x the upper bound above), launch-free, the same status codes for the shape. (TT, RG) is chosen from
+ * (T, n_used, n_expert, N, K, wtype, CU count): slots / n_expert (rounded up) <= 16 -> (1, 1), <= 32 -> (2, 1),
+ * beyond (4, 4) once ceil(N / 64) * ceil(slots / 64) fills the CUs, else (4, 1); Q6_K at K <= 1024 always (4, 4).
+ * Which entry for which T (measured on an MI355X with a uniform router): with 8 experts, 2 used
+ * (Mixtral, N x K = 14336 x 4096 and 4096 x 14336) this entry is below qg_gemm_w4a8_moe from T = 16 on (the smallest
+ * T measured; 0.67 .. 0.87 of it there, 0.09 .. 0.16 at T = 1024); with 128 experts, 8 used (Qwen3-MoE, 768 x 2048 and
+ * 2048 x 768) from T = 256 on (at T = 64 it takes 1.1 .. 2.2 times as long: two slots per expert leave nothing to
+ * share). As a rule: this entry once slots / n_expert reaches 16, qg_gemm_w4a8_moe below 4; between them it depends on
+ * the expert's size (ahead at 4 with Mixtral's 33 MB Q4_K experts, behind at 4 with Qwen3-MoE's 0.9 MB ones).
+ * qg_debug_moe_prefill_plan runs the plan alone for the tile size the product would use and copies the n_expert + 1
+ * counts (the last: the invalid bin) and the T * n_used sorted slots (the invalid bin's last) to caller device
+ * buffers; for tests, no stable layout promise.
+ * Not built: the five 32-element types (their MFMA kernel stages through LDS-DMA from linear bases), tiled-layout
+ * experts, FP32 activations, an automatic choice between the two entries, the plan fused into the router. */
+size_t qg_gemm_w4a8_moe_prefill_workspace_size(int T, int n_used, int n_expert);
+int qg_gemm_w4a8_moe_prefill(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                             int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                             void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_prefill_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
+int qg_debug_moe_prefill_plan(const int32_t* ids, int64_t ids_stride, int T, int n_used, int n_expert, int a_rows, int N,
+                              int K, int wtype, int32_t* counts, int32_t* sorted, void* workspace,
+                              size_t workspace_bytes, qg_stream_t stream);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -453,6 +507,10 @@ int qg_gemm_fp32_from_view(const qg_tensor_view* activation, const qg_tensor_vie
  * QG_ERR_INVALID_ARG. */
 int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                             qg_tensor_view* out, qg_stream_t stream);
+/* The same views and the same refusals, always through qg_gemm_w4a8_moe_prefill with the caller's workspace (of
+ * qg_gemm_w4a8_moe_prefill_workspace_size(T, n_used, n_expert) bytes): the entry for a prompt. */
+int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                               qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

@@ -10,6 +10,7 @@
 
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
+#include "qg_moe_prefill.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
 
@@ -416,27 +417,49 @@ int run_moe(const void* A, int a_rows, const void* B, int n_expert, const int32_
     if (!moe_lds_ok(wtype, K) || ((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
     return hip_status(launch_moe(a, wtype, st, describe, describe_len));
 }
-}  // namespace
 
-extern "C" {
-
-int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
-                     int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
-                     qg_stream_t stream) {
-    return run_moe(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype,
-                   (hipStream_t)stream, nullptr, 0);
+// qg_gemm_w4a8_moe_prefill, qg_moe_prefill_config (describe) and qg_debug_moe_prefill_plan (plan_only: A, B and C
+// are stand-ins): run_moe's order -- the precheck, then a_rows / ids_stride / n_expert / ldc -- then the workspace
+// (null: QG_ERR_INVALID_ARG, off 16 B: QG_ERR_ALIGN, too small: QG_ERR_INVALID_ARG), then the shapes the entry does
+// not serve (QG_ERR_UNSUPPORTED): more than 65535 slots, more than 4096 experts, an expert stride off the kernel's
+// weight alignment. A 32-element type is one the entry does not take (checked at the 32-element granule, as in
+// run_product). ids is never read here.
+size_t moe_prefill_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert) {
+    if (T <= 0 || n_used <= 0 || n_expert <= 0) return 0;
+    return (size_t)moe_plan_layout((long)(T * n_used), (long)n_expert).total * sizeof(int32_t);
 }
 
-int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    // the shape alone, as qg_debug_config: 256-B aligned stand-in pointers, one activation row per token
-    return run_moe((const void*)256, 1, (const void*)256, 1, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
-                   wtype, nullptr, buf, len);
+int run_moe_prefill(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
+                    float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, void* ws, size_t ws_bytes,
+                    hipStream_t st, char* describe, size_t describe_len, bool plan_only = false) {
+    const bool ksb = is_sb_type(wtype);
+    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
+    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb, {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
+    if (rc != QG_GO) return rc;
+    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
+        return QG_ERR_INVALID_ARG;
+    if (!ws) return QG_ERR_INVALID_ARG;
+    if (((uintptr_t)ws & (MOE_PREFILL_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
+    if (ws_bytes < moe_prefill_ws_bytes(T, n_used, n_expert)) return QG_ERR_INVALID_ARG;
+    const int64_t slots = (int64_t)T * n_used;
+    if (slots > MOE_PREFILL_MAX_SLOTS || n_expert > MOE_PREFILL_MAX_EXPERTS) return QG_ERR_UNSUPPORTED;
+    MoePrefillArgs a;
+    a.A = A; a.B = B; a.ids = ids; a.C = C; a.ws = (int32_t*)ws;
+    a.ids_stride = (long)ids_stride;
+    a.ldc = ldc ? (long)ldc : (long)N;
+    a.estride = (long)N * (long)(K / 256) * block_bytes(wtype);
+    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
+    if (((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
+    if (plan_only) return hip_status(launch_moe_plan(a, moe_prefill_tt(a, wtype), st));
+    return hip_status(launch_moe_prefill(a, wtype, st, describe, describe_len));
 }
 
-int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
-                            qg_tensor_view* out, qg_stream_t stream) {
+// The views of ggml_mul_mat_id -> the arguments of the two expert-indexed entries (qg.h, qg_mul_mat_id_from_view).
+struct MulMatIdArgs {
+    int64_t K, N, n_expert, a_rows, T, n_used, ids_stride, ldc;
+};
+int mul_mat_id_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids, const qg_tensor_view* out,
+                    MulMatIdArgs& m) {
     if (!as || !b || !ids || !out) return QG_ERR_INVALID_ARG;
     if (b->type != QG_TYPE_Q8_1 || ids->type != QG_TYPE_I32 || out->type != QG_TYPE_F32 ||
         !(is_weight_type(as->type) || is_sb_type(as->type)))
@@ -459,10 +482,82 @@ int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, c
         return QG_ERR_UNSUPPORTED;
     const size_t slot_bytes = n_used > 1 ? out->nb[1] : T > 1 ? out->nb[2] : (size_t)N * sizeof(float);
     if (slot_bytes % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
-    const int64_t ids_stride = T > 1 ? (int64_t)(ids->nb[1] / sizeof(int32_t)) : n_used;
-    const int64_t ldc = (int64_t)(slot_bytes / sizeof(float));
-    return qg_gemm_w4a8_moe(b->data, (int)a_rows, as->data, (int)n_expert, (const int32_t*)ids->data, ids_stride,
-                            (float*)out->data, ldc, (int)T, (int)n_used, (int)N, (int)K, as->type, stream);
+    m = {K, N, n_expert, a_rows, T, n_used, T > 1 ? (int64_t)(ids->nb[1] / sizeof(int32_t)) : n_used,
+         (int64_t)(slot_bytes / sizeof(float))};
+    return QG_GO;
+}
+}  // namespace
+
+extern "C" {
+
+int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                     int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                     qg_stream_t stream) {
+    return run_moe(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype,
+                   (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    // the shape alone, as qg_debug_config: 256-B aligned stand-in pointers, one activation row per token
+    return run_moe((const void*)256, 1, (const void*)256, 1, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
+                   wtype, nullptr, buf, len);
+}
+
+int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                            qg_tensor_view* out, qg_stream_t stream) {
+    MulMatIdArgs m;
+    const int rc = mul_mat_id_view(as, b, ids, out, m);
+    if (rc != QG_GO) return rc;
+    return qg_gemm_w4a8_moe(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data, m.ids_stride,
+                            (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K, as->type, stream);
+}
+
+size_t qg_gemm_w4a8_moe_prefill_workspace_size(int T, int n_used, int n_expert) {
+    return moe_prefill_ws_bytes(T, n_used, n_expert);
+}
+
+int qg_gemm_w4a8_moe_prefill(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                             int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                             void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    return run_moe_prefill(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+                           workspace_bytes, (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_moe_prefill_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    // the shape alone, as qg_moe_config: 256-B aligned stand-in pointers, one activation row per token
+    return run_moe_prefill((const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T,
+                           n_used, N, K, wtype, (void*)256, SIZE_MAX, nullptr, buf, len);
+}
+
+int qg_debug_moe_prefill_plan(const int32_t* ids, int64_t ids_stride, int T, int n_used, int n_expert, int a_rows, int N,
+                              int K, int wtype, int32_t* counts, int32_t* sorted, void* workspace, size_t workspace_bytes,
+                              qg_stream_t stream) {
+    if (T > 0 && n_used > 0 && N > 0 && (!counts || !sorted)) return QG_ERR_INVALID_ARG;
+    const int rc = run_moe_prefill((const void*)256, a_rows, (const void*)256, n_expert, ids, ids_stride, (float*)256, 0, T,
+                                   n_used, N, K, wtype, workspace, workspace_bytes, (hipStream_t)stream, nullptr, 0, true);
+    if (rc != QG_OK || T == 0 || n_used == 0 || N == 0) return rc;
+    const MoePlanLayout L = moe_plan_layout((long)T * n_used, n_expert);
+    const int32_t* ws = (const int32_t*)workspace;
+    hipError_t e = hipMemcpyAsync(counts, ws + L.counts, sizeof(int32_t) * ((size_t)n_expert + 1), hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(sorted, ws + L.sorted, sizeof(int32_t) * (size_t)T * n_used, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream);
+    return hip_status(e);
+}
+
+int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                               qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MulMatIdArgs m;
+    const int rc = mul_mat_id_view(as, b, ids, out, m);
+    if (rc != QG_GO) return rc;
+    return qg_gemm_w4a8_moe_prefill(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data,
+                                    m.ids_stride, (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K,
+                                    as->type, workspace, workspace_bytes, stream);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -1,0 +1,552 @@
+// qg_moe_prefill.hip — the expert-grouped MFMA prefill (qg_gemm_w4a8_moe_prefill, ggml's mul_mat_id at prompt
+// sizes), families "moe:q4k_mmq" and "moe:q6k_mmq". DESIGN.md 3d.
+//
+// Two launches on the caller's stream, no allocation, no synchronisation, the host never reads ids:
+//  1. moe_plan_kernel: one workgroup counting-sorts the T * n_used slots by expert id into the caller's workspace
+//     (qg_moe_prefill.hpp, MoePlanLayout): counts per bin (ids that name no expert: a bin of their own, the last),
+//     the slots and their activation rows in bin order, and one record {bin, first sorted position, rows} per tile
+//     of R = 16 TT rows with their number n_tiles. Its counters live in LDS and are zeroed by the kernel, so a
+//     replay starts clean. The order of the slots of one expert is whatever the LDS atomics give.
+//  2. q4k_moe_mmq_kernel / q6k_moe_mmq_kernel<TT, RG>: the bodies of q4k_mmq_kernel / q6k_mmq_kernel (qg_q4k_mmq.hip,
+//     qg_q6k_mmq.hip: the work decomposition is described there) as copies, because changing the shipped kernels'
+//     source changes their code objects. What differs:
+//       * blockIdx.y is a tile index. The workgroup reads n_tiles and its record (uniform) and returns at once
+//         beyond n_tiles: gridDim.y is the host's upper bound moe_prefill_max_tiles.
+//       * the activation row of tile position p is rows[first + min(p, rows - 1)]: positions past the tile's rows
+//         are loaded and multiplied, never stored (the shipped kernels' rule at M - 1). Each lane loads the row
+//         indices it needs once, before the K loop; a token load takes its (wave-uniform) index with v_readlane.
+//       * the expert's matrix is B + e * estride, formed in 64 bits before any weight address.
+//       * the output row of position p is C + sorted[first + p] * ldc.
+//       * a tile of the invalid bin stores +0.0f to its rows and returns before any weight address is formed.
+//     Staging, the one barrier per step, the Q6_K realigned loads, the clamps at N - 1 and the K-slice reduction
+//     through LDS in slice order are the shipped kernels'; every workgroup that passes the tile lookup runs the same
+//     number of barriers. An output's arithmetic depends on its activation row, its weight row and KS alone, so its
+//     bits do not depend on TT, on the tile or on the position the sort gave its slot.
+#include "../../include/qg/qg.h"
+#include "qg_kq_launch.hpp"
+#include "qg_moe_prefill.hpp"
+#include "qg_q4k.hpp"
+#include "qg_q6k.hpp"
+
+namespace qg {
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// (TT, RG) of the product (0: by shape, moe_prefill_form; A/B builds force 1 = (1,1), 2 = (2,1), 3 = (4,1), 4 = (4,4))
+#ifndef QG_MOE_PREFILL_FORM
+#define QG_MOE_PREFILL_FORM 0
+#endif
+
+// ---- the plan ---------------------------------------------------------------------------------------------------
+constexpr int PLAN_WGS = 1024;
+constexpr int PLAN_BINS = MOE_PREFILL_MAX_EXPERTS + 1;
+
+// rsh: log2 of the tile's rows
+__global__ __launch_bounds__(PLAN_WGS) void moe_plan_kernel(const MoePrefillArgs a, int rsh) {
+    __shared__ int cnt[PLAN_BINS];       // slots per bin; the scatter's cursors afterwards
+    __shared__ int poff[PLAN_BINS + 1];  // first sorted position of a bin
+    __shared__ int toff[PLAN_BINS + 1];  // first tile of a bin
+    __shared__ int scan_p[PLAN_WGS], scan_t[PLAN_WGS];
+    const int tid = threadIdx.x, E = a.n_expert, nbin = E + 1, R = 1 << rsh;
+    const MoePlanLayout L = moe_plan_layout(a.slots, E);
+    int32_t* __restrict__ ws = a.ws;
+
+    for (int b = tid; b < nbin; b += PLAN_WGS) cnt[b] = 0;
+    __syncthreads();
+    for (int s = tid; s < a.slots; s += PLAN_WGS) {
+        const int t = s / a.n_used, u = s - t * a.n_used;
+        const int e = a.ids[(long)t * a.ids_stride + u];
+        atomicAdd(&cnt[(unsigned)e < (unsigned)E ? e : E], 1);
+    }
+    __syncthreads();
+    // exclusive prefix sums of the counts and of the tiles per bin: thread i owns bins [b0, b1)
+    const int per = (nbin + PLAN_WGS - 1) / PLAN_WGS;
+    const int b0 = min(tid * per, nbin), b1 = min(b0 + per, nbin);
+    int sp = 0, stl = 0;
+    for (int b = b0; b < b1; ++b) {
+        sp += cnt[b];
+        stl += (cnt[b] + R - 1) >> rsh;
+    }
+    scan_p[tid] = sp;
+    scan_t[tid] = stl;
+    __syncthreads();
+    for (int d = 1; d < PLAN_WGS; d <<= 1) {
+        const int vp = tid >= d ? scan_p[tid - d] : 0, vt = tid >= d ? scan_t[tid - d] : 0;
+        __syncthreads();
+        scan_p[tid] += vp;
+        scan_t[tid] += vt;
+        __syncthreads();
+    }
+    {
+        int p = scan_p[tid] - sp, tl = scan_t[tid] - stl;
+        for (int b = b0; b < b1; ++b) {
+            poff[b] = p;
+            toff[b] = tl;
+            p += cnt[b];
+            tl += (cnt[b] + R - 1) >> rsh;
+        }
+        if (tid == PLAN_WGS - 1) {
+            poff[nbin] = scan_p[tid];
+            toff[nbin] = scan_t[tid];
+        }
+    }
+    __syncthreads();
+    const int n_tiles = toff[nbin];
+    if (tid == 0) *reinterpret_cast<int4*>(ws) = make_int4(n_tiles, poff[E], R, 0);
+    for (int b = tid; b < nbin; b += PLAN_WGS) ws[L.counts + b] = cnt[b];
+    // tile j belongs to the bin b with toff[b] <= j < toff[b + 1] (empty bins have no such j)
+    for (int j = tid; j < n_tiles; j += PLAN_WGS) {
+        int lo = 0, hi = nbin;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (toff[mid] <= j) lo = mid;
+            else hi = mid;
+        }
+        const int i = j - toff[lo];
+        reinterpret_cast<int4*>(ws + L.tiles)[j] = make_int4(lo, poff[lo] + (i << rsh), min(R, cnt[lo] - (i << rsh)), 0);
+    }
+    __syncthreads();
+    for (int b = tid; b < nbin; b += PLAN_WGS) cnt[b] = poff[b];
+    __syncthreads();
+    for (int s = tid; s < a.slots; s += PLAN_WGS) {
+        const int t = s / a.n_used, u = s - t * a.n_used;
+        const int e = a.ids[(long)t * a.ids_stride + u];
+        const int p = atomicAdd(&cnt[(unsigned)e < (unsigned)E ? e : E], 1);
+        ws[L.sorted + p] = s;
+        // a_rows is 1 (the token's one row) or n_used (a row per slot): u % a_rows
+        ws[L.rows + p] = t * a.a_rows + (a.a_rows > 1 ? u : 0);
+    }
+}
+
+// ---- what the two gathered kernels share --------------------------------------------------------------------------
+constexpr int MMQ_WAVES = 8;
+constexpr int MMQ_WGS = 64 * MMQ_WAVES;
+constexpr int TOK_DW = 72;             // one token's 8 blocks of a super-block: 288 B
+constexpr int TILE_DW = 16 * TOK_DW;   // a 16-token tile: 1152 dwords
+
+// The tile of this workgroup. false: blockIdx.y is beyond n_tiles.
+struct MoeTile {
+    int e, first, rows;        // bin, first sorted position, rows (1 .. 16 TT)
+    const int32_t* sorted;     // + first: the tile's slots
+    const int32_t* arows;      // + first: their activation rows
+};
+__device__ __forceinline__ bool moe_tile_lookup(const MoePrefillArgs& a, MoeTile& t) {
+    const int32_t* __restrict__ ws = a.ws;
+    const MoePlanLayout L = moe_plan_layout(a.slots, a.n_expert);
+    // both loads at once (the record's place is inside the workspace for every blockIdx.y of the grid, whatever it
+    // holds beyond n_tiles): one round trip to memory before the workgroup knows its work, not two
+    const int n_tiles = ws[0];
+    const int4 rec = reinterpret_cast<const int4*>(ws + L.tiles)[blockIdx.y];
+    if ((int)blockIdx.y >= __builtin_amdgcn_readfirstlane(n_tiles)) return false;
+    t.e = __builtin_amdgcn_readfirstlane(rec.x);
+    t.first = __builtin_amdgcn_readfirstlane(rec.y);
+    t.rows = __builtin_amdgcn_readfirstlane(rec.z);
+    t.sorted = ws + L.sorted + t.first;
+    t.arows = ws + L.rows + t.first;
+    return true;
+}
+
+// The activation rows this lane needs, loaded once: rowv[t] that of position 16 t + (lane & 15) (a token load reads
+// position p's from lane p & 15), tailv[t][b] that of the lane's tail load b. Positions past the tile's rows take
+// the last valid row.
+template <int TT, int RG> struct MoeRows {
+    static constexpr int NT = RG == 1 ? 2 : 1;
+    int rowv[TT], tailv[TT][NT];
+    __device__ __forceinline__ void load(const MoeTile& tl, int lane, int rg) {
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            rowv[t] = tl.arows[min(16 * t + (lane & 15), tl.rows - 1)];
+#pragma unroll
+            for (int b = 0; b < NT; ++b)
+                tailv[t][b] = tl.arows[min(16 * t + 8 * (RG == 1 ? b : rg) + (lane >> 3), tl.rows - 1)];
+        }
+    }
+};
+
+// this wave's share of a 16-token tile of super-block sb: token loads r take dwords 0..63 of token NR rg + r (the
+// token's row is wave-uniform, so its address lives in SGPRs), a tail load dwords 64..71 of 8 tokens
+template <int TT, int RG>
+__device__ __forceinline__ void moe_load_tile(uint32_t (&dst)[16 / RG + (RG == 1 ? 2 : 1)], const uint32_t* A, long arow,
+                                              const MoeRows<TT, RG>& rows, int sb, int t, int lane, int rg) {
+    constexpr int NR = 16 / RG, NT = RG == 1 ? 2 : 1;
+    const uint32_t* a = A + (long)sb * TOK_DW;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) dst[r] = a[(long)__builtin_amdgcn_readlane(rows.rowv[t], NR * rg + r) * arow + lane];
+    if (RG == 1 || rg < 2) {
+#pragma unroll
+        for (int b = 0; b < NT; ++b) dst[NR + b] = a[(long)rows.tailv[t][b] * arow + 64 + (lane & 7)];
+    }
+}
+template <int RG>
+__device__ __forceinline__ void moe_store_tile(const uint32_t (&src)[16 / RG + (RG == 1 ? 2 : 1)], uint32_t* buf, int lane,
+                                               int rg) {
+    constexpr int NR = 16 / RG, NT = RG == 1 ? 2 : 1;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) buf[(NR * rg + r) * TOK_DW + lane] = src[r];
+    if (RG == 1 || rg < 2) {
+#pragma unroll
+        for (int b = 0; b < NT; ++b) buf[(8 * (RG == 1 ? b : rg) + (lane >> 3)) * TOK_DW + 64 + (lane & 7)] = src[NR + b];
+    }
+}
+
+// A tile of the invalid bin: +0.0f to this workgroup's 16 RG rows of the tile's slots.
+template <int TT, int RG> __device__ __forceinline__ void moe_zero_tile(const MoePrefillArgs& a, const MoeTile& tl, int tile) {
+    constexpr int PT = TT * 256;
+    for (int idx = threadIdx.x; idx < RG * PT; idx += MMQ_WGS) {
+        const int g = idx / PT, o = idx - g * PT;
+        const int p = o >> 4, n = tile * (16 * RG) + 16 * g + (o & 15);
+        if (p < tl.rows && n < a.N) a.C[(long)tl.sorted[p] * a.ldc + n] = 0.0f;
+    }
+}
+
+// The K-slice reduction: partial tiles as [slice][row group][token][row] (over the staging buffers, once every wave
+// has read its last tile), lane (c, q) writes rows 4q .. 4q + 3 of token c (one 16-B store); then each output is the
+// sum of its KS partials in slice order, stored to its slot's row.
+template <int TT, int RG>
+__device__ __forceinline__ void moe_reduce_store(const MoePrefillArgs& a, const MoeTile& tl, uint32_t* smem,
+                                                 const float (&acc)[TT][4], int ks, int rg, int r16, int q, int tile) {
+    constexpr int KS = MMQ_WAVES / RG, PT = TT * 256;  // outputs per (slice, row group)
+    __syncthreads();
+    float* part = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+        *reinterpret_cast<float4*>(&part[(ks * RG + rg) * PT + (16 * t + r16) * 16 + 4 * q]) =
+            make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < RG * PT; idx += MMQ_WGS) {
+        float sum = part[idx];
+#pragma unroll
+        for (int k = 1; k < KS; ++k) sum += part[k * (RG * PT) + idx];
+        const int g = idx / PT, o = idx - g * PT;
+        const int p = o >> 4, n = tile * (16 * RG) + 16 * g + (o & 15);
+        if (p < tl.rows && n < a.N) a.C[(long)tl.sorted[p] * a.ldc + n] = sum;
+    }
+}
+
+// ---- Q4_K: q4k_mmq_kernel (qg_q4k_mmq.hip) on a tile of gathered rows ----------------------------------------------
+template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq_kernel(const MoePrefillArgs a) {
+    static_assert(RG == 1 || RG == 4, "row groups per workgroup");
+    constexpr int W = MMQ_WAVES, KS = W / RG;
+    constexpr int NBUF = RG > 1 ? 2 : 1;
+    constexpr int NR = 16 / RG;          // token loads (dwords 0..63 of a token) per wave and tile
+    constexpr int NT = RG == 1 ? 2 : 1;  // tail loads (dwords 64..71 of 8 tokens) per wave (RG = 4: waves 0, 1)
+    constexpr int STAGE_DW = KS * NBUF * TILE_DW, PART_DW = W * TT * 256;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
+    MoeTile tl;
+    if (!moe_tile_lookup(a, tl)) return;
+    const int N = a.N, nb = a.K / QK, nsb = a.K / SB_ELEMS;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int rg = wave % RG, ks = wave / RG;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    if (tl.e >= a.n_expert) {
+        moe_zero_tile<TT, RG>(a, tl, tile);
+        return;
+    }
+    const int n0 = tile * (16 * RG) + 16 * rg;
+    const long wrow = (long)nsb * Q4K_BYTES;
+    const long arow = (long)nb * 9;  // dwords per activation row
+    const uint32_t* A = static_cast<const uint32_t*>(a.A);
+    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)tl.e * a.estride;
+    // rows past the end are clamped to the last one: loaded and multiplied, never stored
+    const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * wrow + 16 + 8 * q;
+    const uint8_t* wh[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wh[e] = B + (long)min(n0 + 4 * q + e, N - 1) * wrow;
+    uint32_t* stage = smem + ks * (NBUF * TILE_DW);
+    MoeRows<TT, RG> rows;
+    rows.load(tl, lane, rg);
+
+    struct wregs {
+        uint2 qs[4];
+        uint4 hd[4];
+    };
+    auto load_weights = [&](wregs& w, int sb) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w.qs[i] = *reinterpret_cast<const uint2*>(wq + (long)sb * Q4K_BYTES + 32 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w.hd[e] = *reinterpret_cast<const uint4*>(wh[e] + (long)sb * Q4K_BYTES);
+    };
+
+    float acc[TT][4];
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0f;
+    const v4i zero = {0, 0, 0, 0};
+
+    const int iters = (nsb + KS - 1) / KS;  // the same for every wave
+    uint32_t tlr[NR + NT];
+    wregs wc;
+    {
+        const int sb0 = min(ks, nsb - 1);
+        moe_load_tile<TT, RG>(tlr, A, arow, rows, sb0, 0, lane, rg);
+        load_weights(wc, sb0);
+    }
+    for (int it = 0; it < iters; ++it) {
+        const int sb = it * KS + ks;
+        const bool valid = sb < nsb;  // wave-uniform
+        const int sbn = min(sb + KS, nsb - 1);
+        long afr[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint2 v = wc.qs[i];
+            const uint32_t l0 = v.x & 0x0F0F0F0Fu, l1 = v.y & 0x0F0F0F0Fu;
+            const uint32_t h0 = (v.x >> 4) & 0x0F0F0F0Fu, h1 = (v.y >> 4) & 0x0F0F0F0Fu;
+            afr[2 * i] = (long)(((unsigned long)l1 << 32) | l0);
+            afr[2 * i + 1] = (long)(((unsigned long)h1 << 32) | h0);
+        }
+        q4k_scales s[4];
+        float d[4], dmin[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s[e] = q4k_unpack_scales(wc.hd[e].y, wc.hd[e].z, wc.hd[e].w);
+            d[e] = h2f(wc.hd[e].x & 0xFFFFu);
+            dmin[e] = h2f(wc.hd[e].x >> 16);
+        }
+        static_for<TT>([&](auto T) {
+            constexpr int t = decltype(T)::value;
+            // this tile into the slice's LDS buffer, the next one (and after the last, the next super-block's
+            // weights) in flight, then the barrier between the writes and the operand reads
+            uint32_t* buf = stage + (NBUF > 1 ? ((TT == 1 ? it : t) & 1) * TILE_DW : 0);
+            moe_store_tile<RG>(tlr, buf, lane, rg);
+            if constexpr (t + 1 < TT) {
+                moe_load_tile<TT, RG>(tlr, A, arow, rows, min(sb, nsb - 1), t + 1, lane, rg);
+            } else {
+                if (it + 1 < iters) {
+                    moe_load_tile<TT, RG>(tlr, A, arow, rows, sbn, 0, lane, rg);
+                    load_weights(wc, sbn);
+                }
+            }
+            __syncthreads();
+            if (valid) {
+                const uint32_t* tok = buf + r16 * TOK_DW;
+                static_for<8>([&](auto J) {
+                    constexpr int j = decltype(J)::value;
+                    const uint32_t b0 = tok[9 * j + 1 + 2 * q], b1 = tok[9 * j + 2 + 2 * q];
+                    const long bfr = (long)(((unsigned long)b1 << 32) | b0);
+                    const v4i c = __builtin_amdgcn_mfma_i32_16x16x32_i8(afr[j], bfr, zero, 0, 0, 0);
+                    const uint32_t ds = tok[9 * j];
+                    const float da = h2f(ds & 0xFFFFu), sa = h2f(ds >> 16);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float dsc = d[e] * (float)q4k_byte<j>(s[e].sc);
+                        const float dm = -(dmin[e] * (float)q4k_byte<j>(s[e].mn));
+                        acc[t][e] = __builtin_fmaf(dsc * da, (float)c[e], acc[t][e]);
+                        acc[t][e] = __builtin_fmaf(dm, sa, acc[t][e]);
+                    }
+                    // a chunk's two MFMAs and their epilogues stay together (qg_q4k_mmq.hip)
+                    if constexpr (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+        });
+    }
+    moe_reduce_store<TT, RG>(a, tl, smem, acc, ks, rg, r16, q, tile);
+}
+
+// ---- Q6_K: q6k_mmq_kernel (qg_q6k_mmq.hip) on a tile of gathered rows ----------------------------------------------
+// byte J (0..15) of a 16-byte group held in four dwords, sign extended
+template <int J> __device__ __forceinline__ int q6k_scale(const uint32_t (&v)[4]) {
+    return (int)(int8_t)(v[J / 4] >> (8 * (J % 4)));
+}
+
+template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq_kernel(const MoePrefillArgs a) {
+    static_assert(RG == 1 || RG == 4, "row groups per workgroup");
+    constexpr int W = MMQ_WAVES, KS = W / RG;
+    constexpr int NBUF = RG > 1 ? 2 : 1;
+    constexpr int NR = 16 / RG;
+    constexpr int NT = RG == 1 ? 2 : 1;
+    constexpr int STAGE_DW = KS * NBUF * TILE_DW, PART_DW = W * TT * 256;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
+    MoeTile tl;
+    if (!moe_tile_lookup(a, tl)) return;
+    const int N = a.N, nb = a.K / QK, nsb = a.K / SB_ELEMS;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int rg = wave % RG, ks = wave / RG;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    if (tl.e >= a.n_expert) {
+        moe_zero_tile<TT, RG>(a, tl, tile);
+        return;
+    }
+    const int n0 = tile * (16 * RG) + 16 * rg;
+    const long wrow = (long)nsb * Q6K_BYTES;
+    const long arow = (long)nb * 9;  // dwords per activation row
+    const uint32_t* A = static_cast<const uint32_t*>(a.A);
+    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)tl.e * a.estride;
+    // rows past the end are clamped to the last one: loaded and multiplied, never stored
+    const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * wrow;  // the operand row of MFMA lane (r16, q)
+    const uint8_t* wh[4];                                       // the result lane's rows 4q .. 4q + 3
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wh[e] = B + (long)min(n0 + 4 * q + e, N - 1) * wrow;
+    uint32_t* stage = smem + ks * (NBUF * TILE_DW);
+    MoeRows<TT, RG> rows;
+    rows.load(tl, lane, rg);
+
+    struct wregs {
+        uint32_t ql[4][3];  // 8 bytes at 32 i + 8q of ql (+ the realignment dword)
+        uint32_t qh[2][3];  // 8 bytes at 32 h + 8q of qh
+        uint32_t hd[4][5];  // scales[16] and d of the result lane's four rows
+    };
+    auto load_weights = [&](wregs& w, int sb) {
+        const uint8_t* sbp = wq + (long)sb * Q6K_BYTES + 8 * q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q6k_load<2>(sbp + 32 * i, w.ql[i]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) q6k_load<2>(sbp + Q6K_QH + 32 * h, w.qh[h]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q6k_load<4>(wh[e] + (long)sb * Q6K_BYTES + Q6K_SC, w.hd[e]);
+    };
+
+    float acc[TT][4];
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0f;
+    const v4i zero = {0, 0, 0, 0};
+    // the A operand of the s0 MFMA keeps lanes q < 2 (elements 0..15 of the block), that of the s1 MFMA the others
+    const uint32_t keep0 = q < 2 ? 0xFFFFFFFFu : 0u, keep1 = ~keep0;
+
+    const int iters = (nsb + KS - 1) / KS;  // the same for every wave
+    uint32_t tlr[NR + NT];
+    wregs wc;
+    {
+        const int sb0 = min(ks, nsb - 1);
+        moe_load_tile<TT, RG>(tlr, A, arow, rows, sb0, 0, lane, rg);
+        load_weights(wc, sb0);
+    }
+    for (int it = 0; it < iters; ++it) {
+        const int sb = it * KS + ks;
+        const bool valid = sb < nsb;       // wave-uniform
+        const int sbl = min(sb, nsb - 1);  // the super-block wc holds
+        const int sbn = min(sb + KS, nsb - 1);
+        // realign by the parity of each row's super-block address (every piece sits at a multiple of 4 past it)
+        uint32_t cl[8][2];  // the signed codes of blocks 0..7, this lane's 8 elements
+        {
+            const uint32_t sh = (uint32_t)((uintptr_t)(wq + (long)sbl * Q6K_BYTES) & 3);
+            uint32_t l[4][2], hq[2][2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) q6k_realign<2>(wc.ql[i], sh, l[i]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) q6k_realign<2>(wc.qh[h], sh, hq[h]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    cl[4 * h + 0][x] = q6k_codes<0>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 1][x] = q6k_codes<1>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 2][x] = q6k_codes<2>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                    cl[4 * h + 3][x] = q6k_codes<3>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
+                }
+        }
+        uint32_t sc[4][4];
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t sh = (uint32_t)((uintptr_t)(wh[e] + (long)sbl * Q6K_BYTES) & 3);
+            q6k_realign<4>(wc.hd[e], sh, sc[e]);
+            d[e] = h2f((wc.hd[e][4] >> (8 * sh)) & 0xFFFFu);
+        }
+        static_for<TT>([&](auto T) {
+            constexpr int t = decltype(T)::value;
+            uint32_t* buf = stage + (NBUF > 1 ? ((TT == 1 ? it : t) & 1) * TILE_DW : 0);
+            moe_store_tile<RG>(tlr, buf, lane, rg);
+            if constexpr (t + 1 < TT) {
+                moe_load_tile<TT, RG>(tlr, A, arow, rows, min(sb, nsb - 1), t + 1, lane, rg);
+            } else {
+                if (it + 1 < iters) {
+                    moe_load_tile<TT, RG>(tlr, A, arow, rows, sbn, 0, lane, rg);
+                    load_weights(wc, sbn);
+                }
+            }
+            __syncthreads();
+            if (valid) {
+                const uint32_t* tok = buf + r16 * TOK_DW;
+                static_for<8>([&](auto J) {
+                    constexpr int j = decltype(J)::value;
+                    const uint32_t b0 = tok[9 * j + 1 + 2 * q], b1 = tok[9 * j + 2 + 2 * q];
+                    const long bfr = (long)(((unsigned long)b1 << 32) | b0);
+                    const long a0 = (long)(((unsigned long)(cl[j][1] & keep0) << 32) | (cl[j][0] & keep0));
+                    const long a1 = (long)(((unsigned long)(cl[j][1] & keep1) << 32) | (cl[j][0] & keep1));
+                    const v4i c0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a0, bfr, zero, 0, 0, 0);
+                    const v4i c1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a1, bfr, zero, 0, 0, 0);
+                    const float da = h2f(tok[9 * j] & 0xFFFFu);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int isum = q6k_scale<2 * j>(sc[e]) * c0[e] + q6k_scale<2 * j + 1>(sc[e]) * c1[e];
+                        acc[t][e] = __builtin_fmaf(d[e] * da, (float)isum, acc[t][e]);
+                    }
+                    // a block's two MFMAs and their epilogue stay together (qg_q6k_mmq.hip)
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+        });
+    }
+    moe_reduce_store<TT, RG>(a, tl, smem, acc, ks, rg, r16, q, tile);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+// (TT, RG) from (T, n_used, n_expert, N, K, the type, CU count) alone: the shipped prefill's rule (kq_mmq_launch_t)
+// with the expected rows per expert, slots / n_expert, in the place of M for the tile's rows, and all the slots in
+// the place of M for the 64 x 64 tiles' grid. One rule of its own: Q6_K at K <= 1024 takes the 64 x 64 tiles at any
+// T -- with K / 256 <= 4 super-blocks at least half of the KS = 8 forms' waves idle, and its heavier body pays for
+// that. profiles/moe_prefill/ab_moe_prefill_forms.txt, us per call, Qwen3-MoE down (N = 2048, K = 768, 128 experts,
+// 8 used), (1, 1) -> (4, 4): Q6_K T = 16 169.5 -> 157.1, T = 64 255.0 -> 224.8, T = 256 362.9 -> 230.5; Q4_K
+// T = 16 84.8 -> 137.1, T = 64 126.8 -> 196.7, T = 256 181.9 -> 202.6 (so Q4_K keeps the rule). Only K = 768 is
+// measured below K = 2048, where (1, 1) wins for both types up to T = 256. The other thresholds: DESIGN.md 3d.
+struct MoeForm {
+    int tt, rg;
+};
+MoeForm moe_prefill_form(const MoePrefillArgs& a, int wtype) {
+    constexpr MoeForm forms[] = {{1, 1}, {2, 1}, {4, 1}, {4, 4}};
+    if (QG_MOE_PREFILL_FORM) return forms[QG_MOE_PREFILL_FORM - 1];
+    if (wtype == QG_TYPE_Q6_K && a.K <= 4 * SB_ELEMS) return forms[3];
+    const long per = (a.slots + a.n_expert - 1) / a.n_expert;
+    if (per <= 16) return forms[0];
+    if (per <= 32) return forms[1];
+    if ((long)((a.N + 63) / 64) * ((a.slots + 63) / 64) >= device_cus()) return forms[3];
+    return forms[2];
+}
+
+template <int WT, int TT, int RG>
+hipError_t moe_prefill_k(const MoePrefillArgs& a, hipStream_t st, char* describe, size_t describe_len) {
+    const int gx = (a.N + 16 * RG - 1) / (16 * RG), gy = (int)moe_prefill_max_tiles(a.slots, a.n_expert, 16 * TT);
+    if (describe) {
+        GemmArgs g;
+        g.describe = describe; g.describe_len = describe_len;
+        describe_kernel(g, "moe:%s TT=%d RG=%d KS=%d R=%d grid=%dx%d", WT == QG_TYPE_Q4_K ? "q4k_mmq" : "q6k_mmq", TT, RG,
+                        MMQ_WAVES / RG, 16 * TT, gx, gy);
+        return hipSuccess;
+    }
+    const hipError_t e = launch_moe_plan(a, TT, st);
+    if (e != hipSuccess) return e;
+    if constexpr (WT == QG_TYPE_Q4_K) hipLaunchKernelGGL((q4k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, st, a);
+    else hipLaunchKernelGGL((q6k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, st, a);
+    return hipGetLastError();
+}
+
+template <int WT> hipError_t moe_prefill_t(const MoePrefillArgs& a, hipStream_t st, char* describe, size_t describe_len) {
+    const MoeForm f = moe_prefill_form(a, WT);
+    if (f.rg == 4) return moe_prefill_k<WT, 4, 4>(a, st, describe, describe_len);
+    if (f.tt == 4) return moe_prefill_k<WT, 4, 1>(a, st, describe, describe_len);
+    if (f.tt == 2) return moe_prefill_k<WT, 2, 1>(a, st, describe, describe_len);
+    return moe_prefill_k<WT, 1, 1>(a, st, describe, describe_len);
+}
+
+}  // namespace
+
+int moe_prefill_tt(const MoePrefillArgs& a, int wtype) { return moe_prefill_form(a, wtype).tt; }
+
+hipError_t launch_moe_plan(const MoePrefillArgs& a, int tt, hipStream_t st) {
+    hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(PLAN_WGS), 0, st, a, tt == 4 ? 6 : tt == 2 ? 5 : 4);
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_prefill(const MoePrefillArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    if (wtype == QG_TYPE_Q4_K) return moe_prefill_t<QG_TYPE_Q4_K>(a, st, describe, describe_len);
+    if (wtype == QG_TYPE_Q6_K) return moe_prefill_t<QG_TYPE_Q6_K>(a, st, describe, describe_len);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace qg
