@@ -10,8 +10,9 @@
 //     qg_moe_config against qg_debug_config). The workgroup size and the row tiles per workgroup are the grouped
 //     launch's: half-size workgroups of two tiles while N fits one round of full-size ones, full-size ones beyond
 //     (of one tile for Q8_0, moe_big_tpw). Neither changes a row's arithmetic.
-//   * Q4_K / Q6_K: q4k_moe_body / q6k_moe_body<LPR, WGS, ONE> (qg_moe_kq.hpp: the shipped kernels' bodies at one
-//     activation row, and why they are copies), the single call's LPR, WGS and ONE (kq_gemv_launch_lpr).
+//   * Q4_K / Q6_K: q4k_moe_body / q6k_moe_body<LPR, WGS, ONE> (below: the shipped kernels' bodies at one activation
+//     row, the same text included: qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc), the single call's LPR, WGS and ONE
+//     (kq_gemv_launch_lpr).
 // So every slot's outputs are bit-identical to the eager qg_gemm_w4a8 on that slot's operands.
 // An id outside [0, n_expert) is a workgroup-uniform branch taken before any weight address is formed: the
 // workgroup stores +0.0f to its rows of the slot and returns.
@@ -19,9 +20,33 @@
 #include "../../include/qg/qg.h"
 #include "qg_gemv_impl.hpp"
 #include "qg_kq_launch.hpp"
-#include "qg_moe_kq.hpp"
+#include "qg_q4k.hpp"
+#include "qg_q6k.hpp"
 
 namespace qg {
+
+// The shipped Q4_K / Q6_K decode GEMV bodies at one activation row: the four constants the single call passes at
+// M = 1, the row tile as a parameter, and the very text q4k_gemv_kernel / q6k_gemv_kernel include.
+#define QG_KQ_DECLARE_TILE  // tile is a parameter here
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ void q4k_moe_body(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                             void* __restrict__ out, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    constexpr long ldc = 0;
+#include "qg_q4k_gemv_body.inc"
+}
+
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ void q6k_moe_body(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                             void* __restrict__ out, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    constexpr long ldc = 0;
+#include "qg_q6k_gemv_body.inc"
+}
+#undef QG_KQ_DECLARE_TILE
+
 namespace {
 
 constexpr size_t MOE_LDS_MAX = 160 * 1024;

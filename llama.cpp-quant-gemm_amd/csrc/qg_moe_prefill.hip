@@ -7,9 +7,10 @@
 //     the slots and their activation rows in bin order, and one record {bin, first sorted position, rows} per tile
 //     of R = 16 TT rows with their number n_tiles. Its counters live in LDS and are zeroed by the kernel, so a
 //     replay starts clean. The order of the slots of one expert is whatever the LDS atomics give.
-//  2. q4k_moe_mmq_kernel / q6k_moe_mmq_kernel<TT, RG>: the bodies of q4k_mmq_kernel / q6k_mmq_kernel (qg_q4k_mmq.hip,
-//     qg_q6k_mmq.hip: the work decomposition is described there) as copies, because changing the shipped kernels'
-//     source changes their code objects. What differs:
+//  2. q4k_moe_mmq_kernel / q6k_moe_mmq_kernel<TT, RG>: the K loops of q4k_mmq_kernel / q6k_mmq_kernel (qg_q4k_mmq.hip,
+//     qg_q6k_mmq.hip: the work decomposition is described there), the same text included (qg_q4k_mmq_body.inc,
+//     qg_q6k_mmq_body.inc; text and not a function, so that the shipped code objects do not move: DESIGN.md 3c), between
+//     a prologue and a reduction of their own. What differs:
 //       * blockIdx.y is a tile index. The workgroup reads n_tiles and its record (uniform) and returns at once
 //         beyond n_tiles: gridDim.y is the host's upper bound moe_prefill_max_tiles.
 //       * the activation row of tile position p is rows[first + min(p, rows - 1)]: positions past the tile's rows
@@ -122,8 +123,8 @@ __global__ __launch_bounds__(PLAN_WGS) void moe_plan_kernel(const MoePrefillArgs
 // ---- what the two gathered kernels share --------------------------------------------------------------------------
 constexpr int MMQ_WAVES = 8;
 constexpr int MMQ_WGS = 64 * MMQ_WAVES;
-constexpr int TOK_DW = 72;             // one token's 8 blocks of a super-block: 288 B
-constexpr int TILE_DW = 16 * TOK_DW;   // a 16-token tile: 1152 dwords
+constexpr int TOK_DW = Q4K_TOK_DW;  // one token's 8 blocks of a super-block: the gathered loads serve both types
+static_assert(Q6K_TOK_DW == TOK_DW, "one activation staging layout");
 
 // The tile of this workgroup. false: blockIdx.y is beyond n_tiles.
 struct MoeTile {
@@ -231,259 +232,87 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq
     constexpr int NBUF = RG > 1 ? 2 : 1;
     constexpr int NR = 16 / RG;          // token loads (dwords 0..63 of a token) per wave and tile
     constexpr int NT = RG == 1 ? 2 : 1;  // tail loads (dwords 64..71 of 8 tokens) per wave (RG = 4: waves 0, 1)
-    constexpr int STAGE_DW = KS * NBUF * TILE_DW, PART_DW = W * TT * 256;
+    constexpr int STAGE_DW = KS * NBUF * Q4K_TILE_DW, PART_DW = W * TT * 256;
     __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
-    MoeTile tl;
-    if (!moe_tile_lookup(a, tl)) return;
+    MoeTile mt;
+    if (!moe_tile_lookup(a, mt)) return;
     const int N = a.N, nb = a.K / QK, nsb = a.K / SB_ELEMS;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int rg = wave % RG, ks = wave / RG;
     const int r16 = lane & 15, q = lane >> 4;
     const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    if (tl.e >= a.n_expert) {
-        moe_zero_tile<TT, RG>(a, tl, tile);
+    if (mt.e >= a.n_expert) {
+        moe_zero_tile<TT, RG>(a, mt, tile);
         return;
     }
     const int n0 = tile * (16 * RG) + 16 * rg;
     const long wrow = (long)nsb * Q4K_BYTES;
     const long arow = (long)nb * 9;  // dwords per activation row
     const uint32_t* A = static_cast<const uint32_t*>(a.A);
-    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)tl.e * a.estride;
+    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)mt.e * a.estride;
     // rows past the end are clamped to the last one: loaded and multiplied, never stored
     const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * wrow + 16 + 8 * q;
     const uint8_t* wh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) wh[e] = B + (long)min(n0 + 4 * q + e, N - 1) * wrow;
-    uint32_t* stage = smem + ks * (NBUF * TILE_DW);
+    uint32_t* stage = smem + ks * (NBUF * Q4K_TILE_DW);
     MoeRows<TT, RG> rows;
-    rows.load(tl, lane, rg);
-
-    struct wregs {
-        uint2 qs[4];
-        uint4 hd[4];
+    rows.load(mt, lane, rg);
+    // the gathered loads under the names the K loop uses; its SUMI branch is discarded here, its names resolve to these
+    auto load_tile = [&](uint32_t (&dst)[NR + NT], int sb, int t) {
+        moe_load_tile<TT, RG>(dst, A, arow, rows, sb, t, lane, rg);
     };
-    auto load_weights = [&](wregs& w, int sb) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w.qs[i] = *reinterpret_cast<const uint2*>(wq + (long)sb * Q4K_BYTES + 32 * i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w.hd[e] = *reinterpret_cast<const uint4*>(wh[e] + (long)sb * Q4K_BYTES);
-    };
-
-    float acc[TT][4];
-#pragma unroll
-    for (int t = 0; t < TT; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0f;
-    const v4i zero = {0, 0, 0, 0};
-
-    const int iters = (nsb + KS - 1) / KS;  // the same for every wave
-    uint32_t tlr[NR + NT];
-    wregs wc;
-    {
-        const int sb0 = min(ks, nsb - 1);
-        moe_load_tile<TT, RG>(tlr, A, arow, rows, sb0, 0, lane, rg);
-        load_weights(wc, sb0);
-    }
-    for (int it = 0; it < iters; ++it) {
-        const int sb = it * KS + ks;
-        const bool valid = sb < nsb;  // wave-uniform
-        const int sbn = min(sb + KS, nsb - 1);
-        long afr[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint2 v = wc.qs[i];
-            const uint32_t l0 = v.x & 0x0F0F0F0Fu, l1 = v.y & 0x0F0F0F0Fu;
-            const uint32_t h0 = (v.x >> 4) & 0x0F0F0F0Fu, h1 = (v.y >> 4) & 0x0F0F0F0Fu;
-            afr[2 * i] = (long)(((unsigned long)l1 << 32) | l0);
-            afr[2 * i + 1] = (long)(((unsigned long)h1 << 32) | h0);
-        }
-        q4k_scales s[4];
-        float d[4], dmin[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            s[e] = q4k_unpack_scales(wc.hd[e].y, wc.hd[e].z, wc.hd[e].w);
-            d[e] = h2f(wc.hd[e].x & 0xFFFFu);
-            dmin[e] = h2f(wc.hd[e].x >> 16);
-        }
-        static_for<TT>([&](auto T) {
-            constexpr int t = decltype(T)::value;
-            // this tile into the slice's LDS buffer, the next one (and after the last, the next super-block's
-            // weights) in flight, then the barrier between the writes and the operand reads
-            uint32_t* buf = stage + (NBUF > 1 ? ((TT == 1 ? it : t) & 1) * TILE_DW : 0);
-            moe_store_tile<RG>(tlr, buf, lane, rg);
-            if constexpr (t + 1 < TT) {
-                moe_load_tile<TT, RG>(tlr, A, arow, rows, min(sb, nsb - 1), t + 1, lane, rg);
-            } else {
-                if (it + 1 < iters) {
-                    moe_load_tile<TT, RG>(tlr, A, arow, rows, sbn, 0, lane, rg);
-                    load_weights(wc, sbn);
-                }
-            }
-            __syncthreads();
-            if (valid) {
-                const uint32_t* tok = buf + r16 * TOK_DW;
-                static_for<8>([&](auto J) {
-                    constexpr int j = decltype(J)::value;
-                    const uint32_t b0 = tok[9 * j + 1 + 2 * q], b1 = tok[9 * j + 2 + 2 * q];
-                    const long bfr = (long)(((unsigned long)b1 << 32) | b0);
-                    const v4i c = __builtin_amdgcn_mfma_i32_16x16x32_i8(afr[j], bfr, zero, 0, 0, 0);
-                    const uint32_t ds = tok[9 * j];
-                    const float da = h2f(ds & 0xFFFFu), sa = h2f(ds >> 16);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float dsc = d[e] * (float)q4k_byte<j>(s[e].sc);
-                        const float dm = -(dmin[e] * (float)q4k_byte<j>(s[e].mn));
-                        acc[t][e] = __builtin_fmaf(dsc * da, (float)c[e], acc[t][e]);
-                        acc[t][e] = __builtin_fmaf(dm, sa, acc[t][e]);
-                    }
-                    // a chunk's two MFMAs and their epilogues stay together (qg_q4k_mmq.hip)
-                    if constexpr (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);
-                });
-            }
-        });
-    }
-    moe_reduce_store<TT, RG>(a, tl, smem, acc, ks, rg, r16, q, tile);
+    auto store_tile = [&](const uint32_t (&src)[NR + NT], uint32_t* buf) { moe_store_tile<RG>(src, buf, lane, rg); };
+    constexpr bool SUMI = false;
+    constexpr int m0 = 0, M = 0;
+    constexpr void* out = nullptr;
+#include "qg_q4k_mmq_body.inc"
+    moe_reduce_store<TT, RG>(a, mt, smem, acc, ks, rg, r16, q, tile);
 }
 
 // ---- Q6_K: q6k_mmq_kernel (qg_q6k_mmq.hip) on a tile of gathered rows ----------------------------------------------
-// byte J (0..15) of a 16-byte group held in four dwords, sign extended
-template <int J> __device__ __forceinline__ int q6k_scale(const uint32_t (&v)[4]) {
-    return (int)(int8_t)(v[J / 4] >> (8 * (J % 4)));
-}
-
 template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq_kernel(const MoePrefillArgs a) {
     static_assert(RG == 1 || RG == 4, "row groups per workgroup");
     constexpr int W = MMQ_WAVES, KS = W / RG;
     constexpr int NBUF = RG > 1 ? 2 : 1;
     constexpr int NR = 16 / RG;
     constexpr int NT = RG == 1 ? 2 : 1;
-    constexpr int STAGE_DW = KS * NBUF * TILE_DW, PART_DW = W * TT * 256;
+    constexpr int STAGE_DW = KS * NBUF * Q6K_TILE_DW, PART_DW = W * TT * 256;
     __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
-    MoeTile tl;
-    if (!moe_tile_lookup(a, tl)) return;
+    MoeTile mt;
+    if (!moe_tile_lookup(a, mt)) return;
     const int N = a.N, nb = a.K / QK, nsb = a.K / SB_ELEMS;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int rg = wave % RG, ks = wave / RG;
     const int r16 = lane & 15, q = lane >> 4;
     const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    if (tl.e >= a.n_expert) {
-        moe_zero_tile<TT, RG>(a, tl, tile);
+    if (mt.e >= a.n_expert) {
+        moe_zero_tile<TT, RG>(a, mt, tile);
         return;
     }
     const int n0 = tile * (16 * RG) + 16 * rg;
     const long wrow = (long)nsb * Q6K_BYTES;
     const long arow = (long)nb * 9;  // dwords per activation row
     const uint32_t* A = static_cast<const uint32_t*>(a.A);
-    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)tl.e * a.estride;
+    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)mt.e * a.estride;
     // rows past the end are clamped to the last one: loaded and multiplied, never stored
     const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * wrow;  // the operand row of MFMA lane (r16, q)
     const uint8_t* wh[4];                                       // the result lane's rows 4q .. 4q + 3
 #pragma unroll
     for (int e = 0; e < 4; ++e) wh[e] = B + (long)min(n0 + 4 * q + e, N - 1) * wrow;
-    uint32_t* stage = smem + ks * (NBUF * TILE_DW);
+    uint32_t* stage = smem + ks * (NBUF * Q6K_TILE_DW);
     MoeRows<TT, RG> rows;
-    rows.load(tl, lane, rg);
-
-    struct wregs {
-        uint32_t ql[4][3];  // 8 bytes at 32 i + 8q of ql (+ the realignment dword)
-        uint32_t qh[2][3];  // 8 bytes at 32 h + 8q of qh
-        uint32_t hd[4][5];  // scales[16] and d of the result lane's four rows
+    rows.load(mt, lane, rg);
+    // the gathered loads under the names the K loop uses; its SUMI branch is discarded here, its names resolve to these
+    auto load_tile = [&](uint32_t (&dst)[NR + NT], int sb, int t) {
+        moe_load_tile<TT, RG>(dst, A, arow, rows, sb, t, lane, rg);
     };
-    auto load_weights = [&](wregs& w, int sb) {
-        const uint8_t* sbp = wq + (long)sb * Q6K_BYTES + 8 * q;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q6k_load<2>(sbp + 32 * i, w.ql[i]);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) q6k_load<2>(sbp + Q6K_QH + 32 * h, w.qh[h]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q6k_load<4>(wh[e] + (long)sb * Q6K_BYTES + Q6K_SC, w.hd[e]);
-    };
-
-    float acc[TT][4];
-#pragma unroll
-    for (int t = 0; t < TT; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0f;
-    const v4i zero = {0, 0, 0, 0};
-    // the A operand of the s0 MFMA keeps lanes q < 2 (elements 0..15 of the block), that of the s1 MFMA the others
-    const uint32_t keep0 = q < 2 ? 0xFFFFFFFFu : 0u, keep1 = ~keep0;
-
-    const int iters = (nsb + KS - 1) / KS;  // the same for every wave
-    uint32_t tlr[NR + NT];
-    wregs wc;
-    {
-        const int sb0 = min(ks, nsb - 1);
-        moe_load_tile<TT, RG>(tlr, A, arow, rows, sb0, 0, lane, rg);
-        load_weights(wc, sb0);
-    }
-    for (int it = 0; it < iters; ++it) {
-        const int sb = it * KS + ks;
-        const bool valid = sb < nsb;       // wave-uniform
-        const int sbl = min(sb, nsb - 1);  // the super-block wc holds
-        const int sbn = min(sb + KS, nsb - 1);
-        // realign by the parity of each row's super-block address (every piece sits at a multiple of 4 past it)
-        uint32_t cl[8][2];  // the signed codes of blocks 0..7, this lane's 8 elements
-        {
-            const uint32_t sh = (uint32_t)((uintptr_t)(wq + (long)sbl * Q6K_BYTES) & 3);
-            uint32_t l[4][2], hq[2][2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) q6k_realign<2>(wc.ql[i], sh, l[i]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) q6k_realign<2>(wc.qh[h], sh, hq[h]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    cl[4 * h + 0][x] = q6k_codes<0>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
-                    cl[4 * h + 1][x] = q6k_codes<1>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
-                    cl[4 * h + 2][x] = q6k_codes<2>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
-                    cl[4 * h + 3][x] = q6k_codes<3>(l[2 * h][x], l[2 * h + 1][x], hq[h][x]);
-                }
-        }
-        uint32_t sc[4][4];
-        float d[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t sh = (uint32_t)((uintptr_t)(wh[e] + (long)sbl * Q6K_BYTES) & 3);
-            q6k_realign<4>(wc.hd[e], sh, sc[e]);
-            d[e] = h2f((wc.hd[e][4] >> (8 * sh)) & 0xFFFFu);
-        }
-        static_for<TT>([&](auto T) {
-            constexpr int t = decltype(T)::value;
-            uint32_t* buf = stage + (NBUF > 1 ? ((TT == 1 ? it : t) & 1) * TILE_DW : 0);
-            moe_store_tile<RG>(tlr, buf, lane, rg);
-            if constexpr (t + 1 < TT) {
-                moe_load_tile<TT, RG>(tlr, A, arow, rows, min(sb, nsb - 1), t + 1, lane, rg);
-            } else {
-                if (it + 1 < iters) {
-                    moe_load_tile<TT, RG>(tlr, A, arow, rows, sbn, 0, lane, rg);
-                    load_weights(wc, sbn);
-                }
-            }
-            __syncthreads();
-            if (valid) {
-                const uint32_t* tok = buf + r16 * TOK_DW;
-                static_for<8>([&](auto J) {
-                    constexpr int j = decltype(J)::value;
-                    const uint32_t b0 = tok[9 * j + 1 + 2 * q], b1 = tok[9 * j + 2 + 2 * q];
-                    const long bfr = (long)(((unsigned long)b1 << 32) | b0);
-                    const long a0 = (long)(((unsigned long)(cl[j][1] & keep0) << 32) | (cl[j][0] & keep0));
-                    const long a1 = (long)(((unsigned long)(cl[j][1] & keep1) << 32) | (cl[j][0] & keep1));
-                    const v4i c0 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a0, bfr, zero, 0, 0, 0);
-                    const v4i c1 = __builtin_amdgcn_mfma_i32_16x16x32_i8(a1, bfr, zero, 0, 0, 0);
-                    const float da = h2f(tok[9 * j] & 0xFFFFu);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int isum = q6k_scale<2 * j>(sc[e]) * c0[e] + q6k_scale<2 * j + 1>(sc[e]) * c1[e];
-                        acc[t][e] = __builtin_fmaf(d[e] * da, (float)isum, acc[t][e]);
-                    }
-                    // a block's two MFMAs and their epilogue stay together (qg_q6k_mmq.hip)
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            }
-        });
-    }
-    moe_reduce_store<TT, RG>(a, tl, smem, acc, ks, rg, r16, q, tile);
+    auto store_tile = [&](const uint32_t (&src)[NR + NT], uint32_t* buf) { moe_store_tile<RG>(src, buf, lane, rg); };
+    constexpr bool SUMI = false;
+    constexpr int m0 = 0, M = 0;
+    constexpr void* out = nullptr;
+#include "qg_q6k_mmq_body.inc"
+    moe_reduce_store<TT, RG>(a, mt, smem, acc, ks, rg, r16, q, tile);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------

@@ -39,6 +39,22 @@ template <int J> __host__ __device__ __forceinline__ int q4k_byte(const uint32_t
 // Decode GEMV (M <= 8): see qg_q4k_gemv.hip. LDS per (token, super-block): 64 qs dwords, 8 x (d_a, s_a) fp32,
 // 4 pad dwords (84 = 4 x odd: the 16-B reads of lanes on consecutive super-blocks hit distinct bank groups).
 constexpr int Q4K_REC_DW = 84;
+constexpr int Q4K_UNIT_DW = 12;  // a lane's unit: header (4) + one chunk's qs (8)
+
+// Weight loads: plain, as the row GEMV's product instantiations (NT = false there). 1 (A/B builds): the
+// nontemporal hint, measured slower on every decode shape — M = 1, N = K = 4096: 4.00 us with it, 3.50 without;
+// K = 14336: 10.26 against 8.30 (profiles/q4k/ab_q4k_variants.txt).
+#ifndef QG_Q4K_NT
+#define QG_Q4K_NT 0
+#endif
+template <class T> __device__ __forceinline__ T q4k_wload(const T* p) {
+    if constexpr (QG_Q4K_NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
+// MFMA prefill (M >= 9): see qg_q4k_mmq.hip. The activation staging in LDS.
+constexpr int Q4K_TOK_DW = 72;               // one token's 8 blocks of a super-block: 288 B
+constexpr int Q4K_TILE_DW = 16 * Q4K_TOK_DW;  // a 16-token tile: 1152 dwords
 
 // Shape / pointer rules of the two families (K % 256 == 0 and the alignments are checked by the C-ABI first).
 bool q4k_gemv_eligible(const GemmArgs& g);

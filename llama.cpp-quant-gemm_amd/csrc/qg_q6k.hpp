@@ -65,6 +65,17 @@ __device__ __forceinline__ uint32_t q6k_signed(uint32_t u) { return QG_Q6K_ASUM 
 // as fp32 (8), with QG_Q6K_ASUM the 16 half-block sums x 32 (16), 4 pad dwords (76 / 92 = 4 x odd: the 16-B reads
 // of lanes on consecutive super-blocks hit distinct bank groups).
 constexpr int Q6K_REC_DW = QG_Q6K_ASUM ? 92 : 76;
+// raw dwords of a unit: the ql and qh pieces (9 each: 32 bytes + the realignment dword), the half's scales (3), d (1)
+constexpr int Q6K_UNIT_DW = 22;
+
+// MFMA prefill (M >= 9): see qg_q6k_mmq.hip. The activation staging in LDS.
+constexpr int Q6K_TOK_DW = 72;               // one token's 8 blocks of a super-block: 288 B
+constexpr int Q6K_TILE_DW = 16 * Q6K_TOK_DW;  // a 16-token tile: 1152 dwords
+
+// byte J (0..15) of a 16-byte group held in four dwords, sign extended
+template <int J> __device__ __forceinline__ int q6k_scale(const uint32_t (&v)[4]) {
+    return (int)(int8_t)(v[J / 4] >> (8 * (J % 4)));
+}
 
 // Shape / pointer rules of the two families (K % 256 == 0 and the alignments are checked by the C-ABI first).
 bool q6k_gemv_eligible(const GemmArgs& g);

@@ -41,20 +41,25 @@ def test_new_symbols_are_exported(H):
     assert callable(G.mul_mat_id_from_ggml) and callable(H.gemm_w4a8_moe)
 
 
+@pytest.mark.parametrize("kind", ["gemv", "mmq"])
 @pytest.mark.parametrize("tag", ["q4k", "q6k"])
-def test_indexed_kquant_body_is_the_shipped_kernels(tag):
-    """csrc/qg_moe_kq.hpp copies the bodies of q4k_gemv_kernel / q6k_gemv_kernel (a shared function changed the
-    shipped code objects): after its four fixed constants the copy must be the shipped body line for line, less
-    the line that computes the row tile."""
+def test_kquant_body_exists_once_and_both_entries_include_it(tag, kind):
+    """The body of each Q4_K / Q6_K kernel is one text, csrc/qg_<tag>_<kind>_body.inc, included by the shipped kernel
+    and by its expert-indexed (gemv) / expert-grouped (mmq) twin: both files include it, and the lambda that defines
+    the body occurs in no other file under csrc/, so the MoE entries cannot carry a copy of it."""
+    import glob
     import os
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llama.cpp-quant-gemm_amd", "csrc")
-    shipped = open(os.path.join(csrc, f"qg_{tag}_gemv.hip")).read()
-    copy = open(os.path.join(csrc, "qg_moe_kq.hpp")).read()
-    body = shipped.split("void* __restrict__ out, long ldc) {\n", 1)[1].split("\n}\n", 1)[0]
-    tile = "    const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;\n"
-    assert body.count(tile) == 1
-    mine = copy.split(f"void {tag}_moe_body(", 1)[1].split("    constexpr long ldc = 0;\n", 1)[1].split("\n}\n", 1)[0]
-    assert mine == body.replace(tile, "")
+    body = f"qg_{tag}_{kind}_body.inc"
+    moe_file = {"gemv": "qg_moe.hip", "mmq": "qg_moe_prefill.hip"}[kind]
+    for f in (f"qg_{tag}_{kind}.hip", moe_file):
+        assert open(os.path.join(csrc, f)).read().count(f'#include "{body}"\n') == 1, f
+    # the GEMV's marker carries the type's unit size (the row GEMV of the 32-element types has a do_unit of its own);
+    # the prefill's is the same text in both types, so its holders are the two types' bodies
+    marker = {"gemv": f"auto do_unit = [&](const uint32_t (&w)[{tag.upper()}_UNIT_DW]", "mmq": "auto load_weights = [&]"}[kind]
+    want = {body: 1} if kind == "gemv" else {"qg_q4k_mmq_body.inc": 1, "qg_q6k_mmq_body.inc": 1}
+    holders = {os.path.basename(f): open(f).read().count(marker) for f in glob.glob(os.path.join(csrc, "*")) if os.path.isfile(f)}
+    assert {f: n for f, n in holders.items() if n} == want
 
 
 def moe(so, A=4096, a_rows=1, B=4096, n_expert=4, ids=4096, ids_stride=2, C=4096, ldc=0, T=1, n_used=2, N=8, K=256, t=Q4_0):

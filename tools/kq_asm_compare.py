@@ -3,20 +3,33 @@
 
     python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq} by their integer / bool template arguments, and compares the
-instruction text from each kernel's label to its end (symbol names, labels' function numbers and comments
-normalised away) and the kernel-resource-usage remarks. Prints one line per file and every pair that differs."""
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe and qg_moe_prefill by their name and integer / bool template
+arguments, and compares the instruction text from each kernel's label to its end (symbol names, labels' function
+numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file and every pair
+that differs: REGS where the instruction sequence and the remarks are the parent's and only register numbers moved,
+DIFF otherwise. Exit status 1 if any pair differs."""
 import re
 import sys
 from pathlib import Path
 
-FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq"]
+FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
 def key(sym):
-    """The Li<n>E / Lb<n>E template arguments of a mangled kernel name, in order."""
-    return tuple(re.findall(r"L[ib](\d+)E", sym))
+    """The kernel's own name (the last <length><name> of the mangled nested name) and its Li<n>E / Lb<n>E template
+    arguments, in order."""
+    i, name = (3 if sym.startswith("_ZN") else 2), ""
+    while m := re.match(r"\d+", sym[i:]):
+        i += len(m.group())
+        name = sym[i : i + int(m.group())]
+        i += len(name)
+    return (name,) + tuple(re.findall(r"L[ib](\d+)E", sym))
+
+
+def masked(lines):
+    """register numbers away: v12, s[4:5], a3 -> v, s[:], a"""
+    return [re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1", l) for l in lines]
 
 
 def kernels(asm):
@@ -58,8 +71,9 @@ def main(parent, result):
         side = []
         for d in (Path(parent), Path(result)):
             k = kernels(d / f"{f}-hip-amdgcn-amd-amdhsa-gfx950.s")
-            r = resources(d / f"{f}.resource.txt")
+            r = resources(d / f"{f}.hip.resource.txt")
             side.append({key(s): (s, k[s], r[s]) for s in k})
+            assert len(side[-1]) == len(k), (f, "two kernels with one key")
         assert side[0].keys() == side[1].keys(), (f, sorted(side[0].keys() ^ side[1].keys()))
         same = 0
         for kk in sorted(side[0]):
@@ -68,7 +82,8 @@ def main(parent, result):
                 same += 1
                 continue
             bad += 1
-            print(f"  DIFF {sb}\n    parent {len(ia)} instr {ra}\n    result {len(ib)} instr {rb}")
+            tag = "REGS" if ra == rb and masked(ia) == masked(ib) else "DIFF"
+            print(f"  {tag} {sb}\n    parent {len(ia)} instr {ra}\n    result {len(ib)} instr {rb}")
         print(f"{f}: {len(side[0])} pairs, {same} identical")
     return 1 if bad else 0
 
