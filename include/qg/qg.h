@@ -344,9 +344,10 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
  * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
  * 256-B aligned buffers, launch-free; the same status codes for the shape.
  * Prefill-size T of Q4_K / Q6_K experts: qg_gemm_w4a8_moe_prefill below (this entry streams the slot's whole
- * expert matrix for every slot).
- * Not built: prefill-size T for the five 32-element types, slots of different tokens sharing one
- * pass over an expert they both chose within this decode entry, tiled-layout experts, FP32 activations. */
+ * expert matrix for every slot); slots of different tokens sharing one pass over an expert they both chose, at decode
+ * sizes: qg_gemm_w4a8_moe_batch below.
+ * Not built: prefill-size T and shared passes for the five 32-element types, tiled-layout experts,
+ * FP32 activations. */
 int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                      int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                      qg_stream_t stream);
@@ -394,7 +395,7 @@ int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t 
  * counts (the last: the invalid bin) and the T * n_used sorted slots (the invalid bin's last) to caller device
  * buffers; for tests, no stable layout promise.
  * Not built: the five 32-element types (their MFMA kernel stages through LDS-DMA from linear bases), tiled-layout
- * experts, FP32 activations, an automatic choice between the two entries, the plan fused into the router. */
+ * experts, FP32 activations, an automatic choice between the entries, the plan fused into the router. */
 size_t qg_gemm_w4a8_moe_prefill_workspace_size(int T, int n_used, int n_expert);
 int qg_gemm_w4a8_moe_prefill(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
@@ -403,6 +404,58 @@ int qg_moe_prefill_config(int T, int n_used, int n_expert, int N, int K, int wty
 int qg_debug_moe_prefill_plan(const int32_t* ids, int64_t ids_stride, int T, int n_used, int n_expert, int a_rows, int N,
                               int K, int wtype, int32_t* counts, int32_t* sorted, void* workspace,
                               size_t workspace_bytes, qg_stream_t stream);
+
+/* ---- expert-grouped decode GEMV: ggml_mul_mat_id for batched decode, ids sorted on the device ----
+ * The operands, the slot numbering s = t * n_used + u, a_rows, ids_stride and ldc (0 = N) are those of
+ * qg_gemm_w4a8_moe above, and so is the result:
+ *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k],   e = ids[t * ids_stride + u]
+ * and a slot whose id is outside [0, n_expert) reads no weight byte and gets N times +0.0f.
+ * Two launches: the plan kernel of qg_gemm_w4a8_moe_prefill counting-sorts the slots by expert id into `workspace`,
+ * here with tiles of R = 2, 4 or 8 rows of one expert; then one launch runs the Q4_K / Q6_K decode GEMV body on every
+ * tile (MT = R activation rows per weight pass), its activation rows gathered into the LDS records and its output rows
+ * scattered through the sorted list: slots of different tokens that chose the same expert share one pass over its
+ * matrix. The GEMV launch's grid is row tiles x the host's upper bound floor(slots / R) + min(n_expert + 1, slots) on
+ * the number of tiles; workgroups past the true number return at once.
+ * The host never reads ids; no allocation, no synchronisation: capture-safe (two kernel nodes), and a replayed graph
+ * follows the ids it finds, with another number of rows per expert and of tiles on every replay.
+ * Bits: every slot's N outputs are bit-identical to qg_gemm_w4a8_moe on the same operands, so also to the eager M = 1
+ * qg_gemm_w4a8: the arithmetic is that of the "q4k_gemv" / "q6k_gemv" family at the single call's LPR, WGS and ONE, a
+ * token's accumulation chain is its own, and nothing depends on R, on the tile or on where the sort put the slot. Each
+ * output inherits the decode GEMV's documented bound.
+ * R is a function of (T, n_used, n_expert, K, wtype) alone: per = ceil(slots / n_expert) <= 2 -> 2, <= 4 -> 4, else 8,
+ * then halved until R * K/256 records (336 B for Q4_K, 304 B for Q6_K) fit 160 KiB of LDS: Q4_K takes R = 8 up to
+ * K = 15360 and R = 4 up to K = 30976, Q6_K R = 8 up to K = 17152 and R = 4 up to K = 34304.
+ * Served: wtype QG_TYPE_Q4_K or QG_TYPE_Q6_K (the five 32-element types: QG_ERR_UNSUPPORTED), K % 256 == 0,
+ * n_expert <= 4096, at most 65535 slots, any N. QG_ERR_UNSUPPORTED, nothing launched: beyond these; the shapes
+ * qg_gemm_w4a8_moe refuses; K whose records of two rows exceed the LDS (Q4_K: K > 62208, Q6_K: K > 68864); an expert
+ * stride N * K/256 * block_bytes off the kernel's weight alignment (16 B for Q4_K, never for Q6_K); a tile bound
+ * beyond 65535 (not reachable within the bounds above).
+ * workspace: device memory, 16-B aligned, at least qg_gemm_w4a8_moe_batch_workspace_size(T, n_used, n_expert) bytes (a
+ * function of these three alone, monotone in each; 0 where one of them is <= 0; larger than the prefill's, whose
+ * tile records are sized for R = 16: 4 + bins + 2 slots + 4 max_tiles(R = 2) int32, each region rounded up to 16 B).
+ * It holds only what the plan writes; its previous content is arbitrary. In use until the call's kernels finish:
+ * calls on one stream may share it, concurrent streams need one each.
+ * Validation: the order of qg_gemm_w4a8_moe_prefill: the precheck with the type check (Q4_K / Q6_K only), a_rows /
+ * ids_stride / n_expert / ldc -> QG_ERR_INVALID_ARG, workspace == NULL -> QG_ERR_INVALID_ARG, workspace off 16 B ->
+ * QG_ERR_ALIGN, workspace_bytes below the size function -> QG_ERR_INVALID_ARG, then the unsupported shapes. An empty
+ * call (T, n_used or N equal to 0) is QG_OK and touches nothing, whatever the later arguments are.
+ * qg_moe_batch_config names the launch ("moeb:q4k_gemv" / "moeb:q6k_gemv", R, LPR, WGS, ONE, grid, lds), launch-free,
+ * the same status codes for the shape.
+ * Which of the three entries for which T: measured on an MI355X with a uniform router (DESIGN.md 3e,
+ * profiles/moe_batch/ab_moe_batch.txt; per = slots / n_expert). per <= 1: qg_gemm_w4a8_moe (this entry takes 1.05 ..
+ * 1.6 times as long with Qwen3-MoE's 128 experts, 0.95 .. 1.08 with Mixtral's 8). per = 2 .. 4: this entry, in all 16
+ * measured classes (0.58 .. 0.97 of the better of the two others). per = 8 .. 16: this entry where experts are small
+ * (Qwen3-MoE, 0.9 .. 1.3 MB: 0.38 .. 0.85), qg_gemm_w4a8_moe_prefill where they are large (Mixtral, 33 .. 48 MB: this
+ * entry at 1.03 .. 1.56 of it, below it only for Q6_K gate/up, 0.79 and 0.97). per >= 32: qg_gemm_w4a8_moe_prefill
+ * (this entry at 1.1 .. 2.4 of it on Mixtral; not measured on Qwen3-MoE, T > 256).
+ * Not built: the five 32-element types (their GEMV body is a function shared by many shipped kernels), one plan shared
+ * by the gate / up / down products of a layer, an automatic choice between the three entries, tiled-layout experts,
+ * FP32 activations. */
+size_t qg_gemm_w4a8_moe_batch_workspace_size(int T, int n_used, int n_expert);
+int qg_gemm_w4a8_moe_batch(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                           int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                           void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -511,6 +564,10 @@ int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, c
  * qg_gemm_w4a8_moe_prefill_workspace_size(T, n_used, n_expert) bytes): the entry for a prompt. */
 int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+/* The same views and the same refusals, always through qg_gemm_w4a8_moe_batch with the caller's workspace (of
+ * qg_gemm_w4a8_moe_batch_workspace_size(T, n_used, n_expert) bytes): the entry for batched decode. */
+int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                  qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

@@ -10,6 +10,7 @@
 
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
+#include "qg_moe_batch.hpp"
 #include "qg_moe_prefill.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
@@ -454,6 +455,43 @@ int run_moe_prefill(const void* A, int a_rows, const void* B, int n_expert, cons
     return hip_status(launch_moe_prefill(a, wtype, st, describe, describe_len));
 }
 
+// qg_gemm_w4a8_moe_batch and qg_moe_batch_config (describe): run_moe_prefill's order -- the precheck with the type
+// check (Q4_K / Q6_K), a_rows / ids_stride / n_expert / ldc, the workspace (null, off 16 B, too small) -- then the
+// shapes the entry does not serve (QG_ERR_UNSUPPORTED): what run_moe refuses (more than 65535 slots, a shape AUTO at
+// M = 1 does not send to the type's decode GEMV, an expert stride off the weight alignment), more than 4096 experts,
+// K whose records of two rows exceed the LDS (moe_batch_rows), a tile bound beyond 65535. ids is never read here.
+size_t moe_batch_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert) {
+    if (T <= 0 || n_used <= 0 || n_expert <= 0) return 0;
+    return (size_t)moe_batch_layout((long)(T * n_used), (long)n_expert).total * sizeof(int32_t);
+}
+
+int run_moe_batch(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride, float* C,
+                  int64_t ldc, int T, int n_used, int N, int K, int wtype, void* ws, size_t ws_bytes, hipStream_t st,
+                  char* describe, size_t describe_len) {
+    const bool ksb = is_sb_type(wtype);
+    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
+    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb, {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
+    if (rc != QG_GO) return rc;
+    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
+        return QG_ERR_INVALID_ARG;
+    if (!ws) return QG_ERR_INVALID_ARG;
+    if (((uintptr_t)ws & (MOE_PREFILL_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
+    if (ws_bytes < moe_batch_ws_bytes(T, n_used, n_expert)) return QG_ERR_INVALID_ARG;
+    const int64_t slots = (int64_t)T * n_used;
+    if (slots > MOE_PREFILL_MAX_SLOTS || n_expert > MOE_PREFILL_MAX_EXPERTS) return QG_ERR_UNSUPPORTED;
+    if (select_algo_sb(product_args(A, B, C, 1, N, K, wtype)) != QG_ALGO_GEMV) return QG_ERR_UNSUPPORTED;
+    MoePrefillArgs a;
+    a.A = A; a.B = B; a.ids = ids; a.C = C; a.ws = (int32_t*)ws;
+    a.ids_stride = (long)ids_stride;
+    a.ldc = ldc ? (long)ldc : (long)N;
+    a.estride = (long)N * (long)(K / 256) * block_bytes(wtype);
+    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
+    if (((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
+    const int R = moe_batch_rows(a.slots, n_expert, K, wtype);
+    if (R == 0 || moe_prefill_max_tiles(a.slots, n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
+    return hip_status(launch_moe_batch(a, wtype, st, describe, describe_len));
+}
+
 // The views of ggml_mul_mat_id -> the arguments of the two expert-indexed entries (qg.h, qg_mul_mat_id_from_view).
 struct MulMatIdArgs {
     int64_t K, N, n_expert, a_rows, T, n_used, ids_stride, ldc;
@@ -558,6 +596,35 @@ int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b
     return qg_gemm_w4a8_moe_prefill(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data,
                                     m.ids_stride, (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K,
                                     as->type, workspace, workspace_bytes, stream);
+}
+
+size_t qg_gemm_w4a8_moe_batch_workspace_size(int T, int n_used, int n_expert) {
+    return moe_batch_ws_bytes(T, n_used, n_expert);
+}
+
+int qg_gemm_w4a8_moe_batch(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
+                           int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                           void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    return run_moe_batch(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+                         workspace_bytes, (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    // the shape alone, as qg_moe_config: 256-B aligned stand-in pointers, one activation row per token
+    return run_moe_batch((const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T,
+                         n_used, N, K, wtype, (void*)256, SIZE_MAX, nullptr, buf, len);
+}
+
+int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                  qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MulMatIdArgs m;
+    const int rc = mul_mat_id_view(as, b, ids, out, m);
+    if (rc != QG_GO) return rc;
+    return qg_gemm_w4a8_moe_batch(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data,
+                                  m.ids_stride, (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K,
+                                  as->type, workspace, workspace_bytes, stream);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -28,6 +28,8 @@ namespace qg {
 // The shipped Q4_K / Q6_K decode GEMV bodies at one activation row: the four constants the single call passes at
 // M = 1, the row tile as a parameter, and the very text q4k_gemv_kernel / q6k_gemv_kernel include.
 #define QG_KQ_DECLARE_TILE  // tile is a parameter here
+#define QG_KQ_ABLK(g) A + (long)g * 9
+#define QG_KQ_OUT(m) C[m * ldc + row]
 template <int LPR, int WGS, bool ONE>
 __device__ __forceinline__ void q4k_moe_body(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
                                              void* __restrict__ out, const int tile) {
@@ -45,6 +47,8 @@ __device__ __forceinline__ void q6k_moe_body(const uint32_t* __restrict__ A, con
     constexpr long ldc = 0;
 #include "qg_q6k_gemv_body.inc"
 }
+#undef QG_KQ_OUT
+#undef QG_KQ_ABLK
 #undef QG_KQ_DECLARE_TILE
 
 namespace {

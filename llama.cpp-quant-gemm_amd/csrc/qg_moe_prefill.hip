@@ -367,9 +367,13 @@ template <int WT> hipError_t moe_prefill_t(const MoePrefillArgs& a, hipStream_t 
 
 int moe_prefill_tt(const MoePrefillArgs& a, int wtype) { return moe_prefill_form(a, wtype).tt; }
 
-hipError_t launch_moe_plan(const MoePrefillArgs& a, int tt, hipStream_t st) {
-    hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(PLAN_WGS), 0, st, a, tt == 4 ? 6 : tt == 2 ? 5 : 4);
+hipError_t launch_moe_plan_rows(const MoePrefillArgs& a, int rsh, hipStream_t st) {
+    hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(PLAN_WGS), 0, st, a, rsh);
     return hipGetLastError();
+}
+
+hipError_t launch_moe_plan(const MoePrefillArgs& a, int tt, hipStream_t st) {
+    return launch_moe_plan_rows(a, tt == 4 ? 6 : tt == 2 ? 5 : 4, st);
 }
 
 hipError_t launch_moe_prefill(const MoePrefillArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {

@@ -23,17 +23,19 @@ __host__ __device__ inline long moe_prefill_max_tiles(long slots, long n_expert,
 //   counts              n_expert + 1 slot counts, the last the invalid bin
 //   sorted              the slots in bin order (the invalid bin's last), `slots` entries
 //   rows                the activation row t * a_rows + u % a_rows of each sorted slot
-//   tiles               {bin, first sorted position, rows, 0} per tile, sized for R = 16 (the smallest tile)
+//   tiles               {bin, first sorted position, rows, 0} per tile, sized for the smallest tile of the entry: R = 16
+//                       for the prefill, min_r = 2 for the expert-grouped decode GEMV (qg_moe_batch.hpp). The region
+//                       is the last, so every offset is the same for both and the plan kernel needs no min_r.
 struct MoePlanLayout {
     long counts, sorted, rows, tiles, total;
 };
-__host__ __device__ inline MoePlanLayout moe_plan_layout(long slots, long n_expert) {
+__host__ __device__ inline MoePlanLayout moe_plan_layout(long slots, long n_expert, int min_r = 16) {
     MoePlanLayout L;
     L.counts = 4;
     L.sorted = L.counts + ((n_expert + 1 + 3) & ~3L);
     L.rows = L.sorted + ((slots + 3) & ~3L);
     L.tiles = L.rows + ((slots + 3) & ~3L);
-    L.total = L.tiles + 4 * moe_prefill_max_tiles(slots, n_expert, 16);
+    L.total = L.tiles + 4 * moe_prefill_max_tiles(slots, n_expert, min_r);
     return L;
 }
 
@@ -50,6 +52,9 @@ struct MoePrefillArgs {
 
 // The plan alone for tiles of 16 * tt rows (tt = 1, 2 or 4), one launch.
 hipError_t launch_moe_plan(const MoePrefillArgs& a, int tt, hipStream_t st);
+// The plan alone for tiles of 1 << rsh rows (rsh = 1 .. 6); the workspace's tile region holds moe_prefill_max_tiles
+// at that size.
+hipError_t launch_moe_plan_rows(const MoePrefillArgs& a, int rsh, hipStream_t st);
 // The plan and the product (two launches); describe: name them there (qg_moe_prefill_config) and launch nothing.
 // The caller has checked the type (Q4_K / Q6_K), the bounds above and the workspace.
 hipError_t launch_moe_prefill(const MoePrefillArgs& a, int wtype, hipStream_t st, char* describe = nullptr,

@@ -1,9 +1,13 @@
 // qg_q4k_gemv_body.inc — the body of the Q4_K decode GEMV, included as text into q4k_gemv_kernel (qg_q4k_gemv.hip,
-// where the work decomposition is described) and q4k_moe_body (qg_moe.hip). Text and not a function both call: the
+// where the work decomposition is described) and q4k_moe_body (qg_moe.hip) and
+// q4k_moeb_kernel (qg_moe_batch.hip). Text and not a function they call: the
 // compiler sees the same tokens in the same function as before, so the shipped code objects do not move (DESIGN.md 3c).
 // Expects in scope: A, B (the operands), M, N, K, out, ldc, the template parameters or constants MT, LPR, WGS, SUMI,
-// ONE, and the row tile: the macro QG_KQ_DECLARE_TILE is the one line in which the includers differ, the declaration
-// of `const int tile` in the kernel, nothing where tile is a parameter.
+// ONE, and three macros, the lines in which the includers differ:
+//   QG_KQ_DECLARE_TILE  the declaration of `const int tile` in the kernel, nothing where tile is a parameter
+//   QG_KQ_ABLK(g)       the address of activation block g = m * K/32 + b in staging: `A + (long)g * 9` for dense rows,
+//                       the gathered row of tile position m in the expert-grouped GEMV (qg_moe_batch.hip)
+//   QG_KQ_OUT(m)        the output of token m at this lane's row: `C[m * ldc + row]`, the slot's row there
     constexpr int RPW = 64 / LPR;
     constexpr int RPB = (WGS / 64) * RPW;  // rows per workgroup
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -30,7 +34,7 @@
     // 1) this thread's first activation block, 2) the lane's first unit, 3) the LDS records
     const int totb = M * nb;
     auto load_ablk = [&](int g, uint32_t (&d)[9]) {
-        const uint32_t* p = A + (long)g * 9;
+        const uint32_t* p = QG_KQ_ABLK(g);
 #pragma unroll
         for (int i = 0; i < 9; ++i) d[i] = p[i];
     };
@@ -124,6 +128,6 @@
         if (row_ok && lir == LPR - 1) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
-                if (m < M) C[m * ldc + row] = acc[m];
+                if (m < M) QG_KQ_OUT(m) = acc[m];
         }
     }

@@ -44,12 +44,16 @@
 namespace qg {
 namespace {
 
-// The body is qg_q6k_gemv_body.inc, shared as text with the expert-indexed launch (qg_moe.hip).
+// The body is qg_q6k_gemv_body.inc, shared as text with the MoE launches (qg_moe.hip, qg_moe_batch.hip).
 template <int MT, int LPR, int WGS, bool SUMI, bool ONE>
 __global__ __launch_bounds__(WGS) void q6k_gemv_kernel(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B,
                                                       int M, int N, int K, void* __restrict__ out, long ldc) {
 #define QG_KQ_DECLARE_TILE const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+#define QG_KQ_ABLK(g) A + (long)g * 9
+#define QG_KQ_OUT(m) C[m * ldc + row]
 #include "qg_q6k_gemv_body.inc"
+#undef QG_KQ_OUT
+#undef QG_KQ_ABLK
 #undef QG_KQ_DECLARE_TILE
 }
 

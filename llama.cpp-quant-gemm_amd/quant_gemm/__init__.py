@@ -355,6 +355,66 @@ def debug_moe_prefill_plan(ids: torch.Tensor, n_expert: int, N: int, K: int, wty
     return counts, order
 
 
+def moe_batch_workspace_size(T: int, n_used: int, n_expert: int) -> int:
+    """Bytes of the workspace ``gemm_w4a8_moe_batch`` needs (qg_gemm_w4a8_moe_batch_workspace_size)."""
+    return int(_lib.load().qg_gemm_w4a8_moe_batch_workspace_size(T, n_used, n_expert))
+
+
+def gemm_w4a8_moe_batch(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor, T: int, n_used: int,
+                        N: int, K: int, wtype: int = Q4_K, a_rows: int = 1, workspace: torch.Tensor | None = None,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """ggml's mul_mat_id for batched decode (qg_gemm_w4a8_moe_batch): the slots are sorted by expert id on the device
+    and every expert's rows go through the Q4_K / Q6_K decode GEMV in tiles of 2, 4 or 8, so tokens that chose the same
+    expert share one pass over its matrix. The operands, the result and ``out`` are those of ``gemm_w4a8_moe``, and every
+    slot is bit-identical to it; ``wtype`` is Q4_K or Q6_K.
+
+    ``workspace``: a contiguous CUDA uint8 tensor of ``moe_batch_workspace_size(T, n_used, n_expert)`` bytes or more,
+    16-B aligned, its content arbitrary; allocated here when None. Calls on one stream may share one.
+    The ids are never copied to the host: a captured graph follows the ids each replay finds."""
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the expert-grouped decode GEMV takes Q4_K and Q6_K")
+    _require(K % 256 == 0, f"K must be divisible by 256, got {K}")
+    _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
+    _check_blocks(activation_q, "Activation", T * a_rows, K, 36)
+    _require(experts_q.is_cuda and experts_q.dtype == torch.uint8, "Experts must be a CUDA uint8 tensor")
+    per = N * (K // 256) * BLOCK_BYTES[wtype]
+    _require(per > 0 and experts_q.numel() % per == 0 and experts_q.numel() >= per,
+             f"Experts shape mismatch: {experts_q.numel()} bytes is no multiple of {per}")
+    n_expert = experts_q.numel() // per
+    _require(ids.is_cuda and ids.dtype == torch.int32 and ids.device == experts_q.device, "ids must be an int32 tensor on the experts' device")
+    _require(ids.dim() == 2 and tuple(ids.shape) == (T, n_used) and (n_used <= 1 or ids.stride(1) == 1),
+             "ids must be [T, n_used] with unit column stride")
+    ids_stride = ids.stride(0) if T > 1 else n_used
+    _require(ids_stride >= n_used, "ids row stride below n_used")
+    a, w = activation_q.contiguous(), experts_q.contiguous()
+    if out is None:
+        out = torch.empty((T, n_used, N), dtype=torch.float32, device=w.device)
+    else:
+        _require(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, n_used, N), "bad out tensor")
+        _require(out.device == w.device, "out must be on the experts' device")
+        _require(N <= 1 or out.stride(2) == 1, "bad out tensor: rows must be dense")
+    ldc = out.stride(1) if n_used > 1 else out.stride(0) if T > 1 else N
+    _require(ldc >= N and (T <= 1 or n_used <= 1 or out.stride(0) == n_used * ldc), "bad out tensor: slots must be evenly spaced")
+    if workspace is None:
+        workspace = torch.empty(max(moe_batch_workspace_size(T, n_used, n_expert), 16), dtype=torch.uint8, device=w.device)
+    else:
+        _require(workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
+                 "workspace must be a contiguous CUDA uint8 tensor")
+        _require(workspace.device == w.device, "workspace must be on the experts' device")
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_batch(_ptr(a), a_rows, _ptr(w), n_expert, _ptr(ids), ids_stride, _ptr(out),
+                                                      ldc, T, n_used, N, K, wtype, _ptr(workspace), workspace.numel(),
+                                                      _stream(w.device)), "gemm_w4a8_moe_batch")
+    return out
+
+
+def moe_batch_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_batch`` makes for this shape ("moeb:q4k_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=..",
+    R the rows per tile, Y the host's upper bound on the tiles); nothing is launched. Raises where the shape is not served."""
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().qg_moe_batch_config(T, n_used, n_expert, N, K, wtype, buf, 256), "moe_batch_config")
+    return buf.value.decode()
+
+
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
     """Load-time layout for K/32 not a multiple of 8 (qg_repack_weights): [N, K'/32, bb] uint8,
     the real blocks then zero blocks (K'/32 = round_up(K/32, 8)). Feed it to gemm_w4a8_prepacked."""
@@ -739,4 +799,5 @@ __all__ = [
     "set_capture_fusion", "capture_fusion_stats",
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
+    "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
 ]

@@ -86,6 +86,19 @@ def mul_mat_id_from_ggml_ws(experts: TensorView, act: TensorView, ids: TensorVie
                                                       workspace.numel(), st), "qg_mul_mat_id_from_view_ws")
 
 
+def mul_mat_id_from_ggml_batch(experts: TensorView, act: TensorView, ids: TensorView, out: TensorView,
+                               workspace: torch.Tensor) -> None:
+    """The same views through the expert-grouped decode GEMV (qg_mul_mat_id_from_view_batch): Q4_K / Q6_K experts for
+    batched decode. ``workspace``: a CUDA uint8 tensor of quant_gemm.moe_batch_workspace_size(T, n_used, n_expert)
+    bytes or more."""
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().qg_mul_mat_id_from_view_batch(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
+                                                         ctypes.byref(out), ctypes.c_void_p(workspace.data_ptr()),
+                                                         workspace.numel(), st), "qg_mul_mat_id_from_view_batch")
+
+
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:
     """include/llama_adapter.h:110-117."""
     return bool(_lib.load().qg_validate_view_types(ctypes.byref(act), ctypes.byref(w), ctypes.byref(out), ea, ew, eo))
