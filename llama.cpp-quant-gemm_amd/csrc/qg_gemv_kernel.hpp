@@ -31,6 +31,8 @@
 //    constant is exact), c*s_a precomputed in the record (exact: c is 8, 16 or 1), d_w (and m_w)
 //    taken straight from the f16 bits by v_fma_mix_f32 with a zero addend (= one rounding of the
 //    f32 product, as the reference's d_w * (...)).
+//    tests/test_gpu_q32_extremes.py pins this over the whole finite f16 range (subnormal, negative, zero and
+//    +-65504 d_a, s_a, d_w and m_w: v_fma_mix_f32 keeps f16 subnormal inputs on gfx950).
 //  * Per-lane partials (unit order, block order) are reduced across the row's LPR lanes with DPP
 //    row ops (group_sum_last); the row's last lane stores. Deterministic.
 //  * AIN != 0 (fused activation quantization): A is FP32 (AIN_F32, quantized as

@@ -18,9 +18,12 @@
 // populated forms the outer product d_w (x) d_a (exact f16 x f16 in f32) in the accumulator layout,
 // so the VALU work per element is acc += dd * (cf - 1.5*2^23) (one packed op per two elements); the
 // compensation term sum_b X[n][b] s_a[m][b] (X = d_w, or m_w for Q4_1 / Q5_1) accumulates over each
-// stage's 4 blocks in one more MFMA per tile and is added once at the end (x -8 / -16 / +1). Within the
-// reassociation bound of the parity tests (oracle.reassoc_tol; the per-term rounding differs from the
-// reference's d_w * (d_a * sumi - c * s_a)).
+// stage's 4 blocks in one more MFMA per tile, v_mfma_f32_16x16x4_f32 on the fields converted to f32, and is
+// added once at the end (x -8 / -16 / +1). Within the reassociation bound of the parity tests
+// (oracle.reassoc_tol; the per-term rounding differs from the reference's d_w * (d_a * sumi - c * s_a)).
+// The outer product is exact for f16 subnormal fields too (one product into a zero accumulator), the
+// compensation sum only as an f32 MFMA: tests/test_gpu_q32_extremes.py pins both over the whole finite f16
+// range (profiles/q32_extremes/README.md has what the f16 MFMA does with a sum of subnormal products).
 //
 // Tiling: a workgroup owns BN weight rows x 16*TT tokens and ALL of K; its W waves
 // split K into 4-block stages, wave w taking stages w, w+W, ... Each wave streams its stages with
@@ -413,17 +416,24 @@ __device__ __forceinline__ void mmq_body(const uint8_t* __restrict__ A, const ui
                     cc[b][i][t] = __builtin_amdgcn_mfma_i32_16x16x32_i8(afrag[b][i], bfrag[b][t], bias, 0, 0, 0);
         });
         if constexpr (HAS_S) {
-            // k-slots 0..3 = the stage's 4 blocks (lanes q = 0 only)
+            // k-slot q = block q of the stage: lane q converts its block's X and s_a to f32 and
+            // v_mfma_f32_16x16x4_f32 adds the 4 products as an fmaf chain. (Not the f16 MFMA: it keeps f16
+            // subnormal inputs, but sums its products and C aligned to a subnormal's unnormalised exponent,
+            // which costs up to 10 bits: 2^-15 of sum |X s_a| measured on an MI355X,
+            // profiles/q32_extremes/README.md. One product into a zero C, as dd above, is exact.)
+            // (bit selects, v_bfi_b32: a ?: between two array elements leaves the arrays in scratch)
+            const uint32_t mhi = (q & 2) ? ~0u : 0u, modd = (q & 1) ? ~0u : 0u;
+            auto pick = [](uint32_t m, uint32_t a, uint32_t b) { return (a & ~m) | (b & m); };
+            float sq[TT];
+#pragma unroll
+            for (int t = 0; t < TT; ++t)
+                sq[t] = h2f(pick(mhi, pick(modd, adb[0][t], adb[1][t]), pick(modd, adb[2][t], adb[3][t])) >> 16);
 #pragma unroll
             for (int i = 0; i < G::RT; ++i) {
-                const unsigned long xa = q0 ? (((unsigned long)xs[i][1] << 32) | xs[i][0]) : 0ul;
+                const uint32_t xp = pick(mhi, xs[i][0], xs[i][1]);
+                const float xq = h2f(pick(modd, xp, xp >> 16) & 0xFFFFu);
 #pragma unroll
-                for (int t = 0; t < TT; ++t) {
-                    const uint32_t s01 = __builtin_amdgcn_perm(adb[1][t], adb[0][t], 0x07060302u);
-                    const uint32_t s23 = __builtin_amdgcn_perm(adb[3][t], adb[2][t], 0x07060302u);
-                    const unsigned long sb = q0 ? (((unsigned long)s23 << 32) | s01) : 0ul;
-                    c2[i][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(h4(xa), h4(sb), c2[i][t], 0, 0, 0);
-                }
+                for (int t = 0; t < TT; ++t) c2[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xq, sq[t], c2[i][t], 0, 0, 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);

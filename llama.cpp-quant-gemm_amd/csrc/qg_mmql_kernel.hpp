@@ -2,10 +2,10 @@
 // four waves each owning a disjoint 32 x 32 output tile, 4-block stages ingested cooperatively into LDS.
 //
 // Same block arithmetic as qg_mmq_kernel.hpp — the int32 sumi of each Q-block from an integer MFMA seeded with
-// the 1.5 * 2^23 bias, d_w (x) d_a as an f16 outer-product MFMA, the m / offset term from one compensation
-// MFMA per stage — but on the 32 x 32 shapes: v_mfma_i32_32x32x32_i8 computes a whole 32 x 32 tile of one block
-// (K = 32 = one Q-block) at gfx950's full i8 rate, where the small-tile kernel's v_mfma_i32_16x16x32_i8 (the
-// CDNA3 form) runs at half of it, and v_mfma_f32_32x32x8_f16 forms the scale products. Per-block sumi are
+// the 1.5 * 2^23 bias, d_w (x) d_a as an f16 outer-product MFMA, the m / offset term from f32-input compensation
+// MFMAs (two v_mfma_f32_32x32x2_f32 per stage) — but on the 32 x 32 shapes: v_mfma_i32_32x32x32_i8 computes a
+// whole 32 x 32 tile of one block (K = 32 = one Q-block) at gfx950's full i8 rate, where the small-tile kernel's v_mfma_i32_16x16x32_i8 (the
+// CDNA3 form) runs at half of it, and v_mfma_f32_32x32x8_f16 forms the outer products. Per-block sumi are
 // bit-identical to the reference's (tests/test_gpu_mmql.py); outputs are within the reassociation bound.
 //
 // Why a second kernel: the small-tile kernel gives each workgroup a 32 x 32 output tile and ALL of K with its
@@ -295,6 +295,17 @@ __device__ __forceinline__ void mmql_body(const uint8_t* __restrict__ A, const u
         f32x16 z16;
 #pragma unroll
         for (int e = 0; e < 16; ++e) z16[e] = 0.0f;
+        // The compensation sum: two v_mfma_f32_32x32x2_f32 (k = half), blocks 0 | 1, then 2 | 3, X and s_a converted
+        // to f32 — an fmaf chain in block order, exact for f16 subnormals too (qg_mmq_kernel.hpp on why not the f16
+        // MFMA). Block 2's d_a | s_a dword (byte 72) is among half 0's slots as well. The second one is issued behind
+        // the stage's other MFMAs: it waits for the first one's result (64 cycles).
+        float x23 = 0.0f, s23 = 0.0f;
+        if constexpr (HAS_S) {
+            const float x01 = h2f((hh == 0 ? xw[0] : xw[1]) & 0xFFFFu), s01 = h2f((hh == 0 ? ads[0] : ads[1]) >> 16);
+            x23 = h2f((hh == 0 ? xw[2] : xw[3]) & 0xFFFFu);
+            s23 = h2f((hh == 0 ? adw(72) : ads[3]) >> 16);
+            c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x01, s01, c2, 0, 0, 0);
+        }
         static_for<MMQ_SB>([&](auto BI) {
             constexpr int b = decltype(BI)::value;
             const bool on = hh == (b == 0 ? 0 : 1);  // the half that holds block b's d_a
@@ -305,14 +316,7 @@ __device__ __forceinline__ void mmql_body(const uint8_t* __restrict__ A, const u
             constexpr int b = decltype(BI)::value;
             cc[b] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[b], bfrag[b], bias, 0, 0, 0);
         });
-        if constexpr (HAS_S) {
-            // k-slot 0 (half 0) = block 0, k-slots 4..6 (half 1) = blocks 1..3
-            const unsigned long xa = hh == 0 ? (unsigned long)(xw[0] & 0xFFFFu)
-                                             : ((unsigned long)(xw[3] & 0xFFFFu) << 32) | (xw[2] << 16) | (xw[1] & 0xFFFFu);
-            const unsigned long sb = hh == 0 ? (unsigned long)(ads[0] >> 16)
-                                             : ((unsigned long)(ads[3] >> 16) << 32) | (ads[2] & 0xFFFF0000u) | (ads[1] >> 16);
-            c2 = __builtin_amdgcn_mfma_f32_32x32x8f16(h4(xa), h4(sb), c2, 0, 0, 0);
-        }
+        if constexpr (HAS_S) c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x23, s23, c2, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         epi(dd, cc, h);
     };
