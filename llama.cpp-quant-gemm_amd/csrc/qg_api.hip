@@ -390,114 +390,125 @@ int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
     }
     return QG_ERR_UNSUPPORTED;
 }
-// qg_gemm_w4a8_moe and qg_moe_config (describe): the precheck in its order, then what is specific to the entry
-// (a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG), then the shapes the expert-indexed GEMV does not serve
-// (QG_ERR_UNSUPPORTED): more than 65535 slots, a shape AUTO at M = 1 does not send to the type's decode GEMV, LDS
-// records beyond 160 KiB, an expert stride off the kernel's weight alignment. ids is never read here.
-int run_moe(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride, float* C,
-            int64_t ldc, int T, int n_used, int N, int K, int wtype, hipStream_t st, char* describe, size_t describe_len) {
-    const bool ksb = is_sb_type(wtype);
-    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
-    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb || is_weight_type(wtype),
-                            {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
-    if (rc != QG_GO) return rc;
-    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
-        return QG_ERR_INVALID_ARG;
-    const int64_t slots = (int64_t)T * n_used;
-    if (slots > 65535) return QG_ERR_UNSUPPORTED;
-    const GemmArgs q = product_args(A, B, C, 1, N, K, wtype);
-    if (ksb ? select_algo_sb(q) != QG_ALGO_GEMV : !(select_algo(q) == QG_ALGO_GEMV && gemv_eligible(q)))
-        return QG_ERR_UNSUPPORTED;
-    MoeArgs a;
-    a.A = A; a.B = B; a.ids = ids; a.C = C;
-    a.ids_stride = (long)ids_stride;
-    a.ldc = ldc ? (long)ldc : (long)N;
-    a.arow = (long)(K / 32) * 36;
-    a.estride = (long)N * (long)(K / block_elems(wtype)) * block_bytes(wtype);
-    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
-    if (!moe_lds_ok(wtype, K) || ((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
-    return hip_status(launch_moe(a, wtype, st, describe, describe_len));
-}
 
-// qg_gemm_w4a8_moe_prefill, qg_moe_prefill_config (describe) and qg_debug_moe_prefill_plan (plan_only: A, B and C
-// are stand-ins): run_moe's order -- the precheck, then a_rows / ids_stride / n_expert / ldc -- then the workspace
-// (null: QG_ERR_INVALID_ARG, off 16 B: QG_ERR_ALIGN, too small: QG_ERR_INVALID_ARG), then the shapes the entry does
-// not serve (QG_ERR_UNSUPPORTED): more than 65535 slots, more than 4096 experts, an expert stride off the kernel's
-// weight alignment. A 32-element type is one the entry does not take (checked at the 32-element granule, as in
-// run_product). ids is never read here.
-size_t moe_prefill_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert) {
-    if (T <= 0 || n_used <= 0 || n_expert <= 0) return 0;
-    return (size_t)moe_plan_layout((long)(T * n_used), (long)n_expert).total * sizeof(int32_t);
-}
-
-int run_moe_prefill(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
-                    float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, void* ws, size_t ws_bytes,
-                    hipStream_t st, char* describe, size_t describe_len, bool plan_only = false) {
-    const bool ksb = is_sb_type(wtype);
-    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
-    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb, {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
-    if (rc != QG_GO) return rc;
-    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
-        return QG_ERR_INVALID_ARG;
-    if (!ws) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)ws & (MOE_PREFILL_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
-    if (ws_bytes < moe_prefill_ws_bytes(T, n_used, n_expert)) return QG_ERR_INVALID_ARG;
-    const int64_t slots = (int64_t)T * n_used;
-    if (slots > MOE_PREFILL_MAX_SLOTS || n_expert > MOE_PREFILL_MAX_EXPERTS) return QG_ERR_UNSUPPORTED;
-    MoePrefillArgs a;
-    a.A = A; a.B = B; a.ids = ids; a.C = C; a.ws = (int32_t*)ws;
-    a.ids_stride = (long)ids_stride;
-    a.ldc = ldc ? (long)ldc : (long)N;
-    a.estride = (long)N * (long)(K / 256) * block_bytes(wtype);
-    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
-    if (((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
-    if (plan_only) return hip_status(launch_moe_plan(a, moe_prefill_tt(a, wtype), st));
-    return hip_status(launch_moe_prefill(a, wtype, st, describe, describe_len));
-}
-
-// qg_gemm_w4a8_moe_batch and qg_moe_batch_config (describe): run_moe_prefill's order -- the precheck with the type
-// check (Q4_K / Q6_K), a_rows / ids_stride / n_expert / ldc, the workspace (null, off 16 B, too small) -- then the
-// shapes the entry does not serve (QG_ERR_UNSUPPORTED): what run_moe refuses (more than 65535 slots, a shape AUTO at
-// M = 1 does not send to the type's decode GEMV, an expert stride off the weight alignment), more than 4096 experts,
-// K whose records of two rows exceed the LDS (moe_batch_rows), a tile bound beyond 65535. ids is never read here.
-size_t moe_batch_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert) {
-    if (T <= 0 || n_used <= 0 || n_expert <= 0) return 0;
-    return (size_t)moe_batch_layout((long)(T * n_used), (long)n_expert).total * sizeof(int32_t);
-}
-
-int run_moe_batch(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride, float* C,
-                  int64_t ldc, int T, int n_used, int N, int K, int wtype, void* ws, size_t ws_bytes, hipStream_t st,
-                  char* describe, size_t describe_len) {
-    const bool ksb = is_sb_type(wtype);
-    const uintptr_t wmask = ksb ? sb_weight_mask(wtype) : 3u;
-    const int rc = precheck({T, n_used, N}, K, ksb ? 256 : 32, ksb, {{A, 3}, {B, wmask}, {ids, 3}, {C, 0}});
-    if (rc != QG_GO) return rc;
-    if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
-        return QG_ERR_INVALID_ARG;
-    if (!ws) return QG_ERR_INVALID_ARG;
-    if (((uintptr_t)ws & (MOE_PREFILL_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
-    if (ws_bytes < moe_batch_ws_bytes(T, n_used, n_expert)) return QG_ERR_INVALID_ARG;
-    const int64_t slots = (int64_t)T * n_used;
-    if (slots > MOE_PREFILL_MAX_SLOTS || n_expert > MOE_PREFILL_MAX_EXPERTS) return QG_ERR_UNSUPPORTED;
-    if (select_algo_sb(product_args(A, B, C, 1, N, K, wtype)) != QG_ALGO_GEMV) return QG_ERR_UNSUPPORTED;
-    MoePrefillArgs a;
-    a.A = A; a.B = B; a.ids = ids; a.C = C; a.ws = (int32_t*)ws;
-    a.ids_stride = (long)ids_stride;
-    a.ldc = ldc ? (long)ldc : (long)N;
-    a.estride = (long)N * (long)(K / 256) * block_bytes(wtype);
-    a.a_rows = a_rows; a.n_used = n_used; a.n_expert = n_expert; a.N = N; a.K = K; a.slots = (int)slots;
-    if (((uintptr_t)a.estride & wmask) != 0) return QG_ERR_UNSUPPORTED;
-    const int R = moe_batch_rows(a.slots, n_expert, K, wtype);
-    if (R == 0 || moe_prefill_max_tiles(a.slots, n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
-    return hip_status(launch_moe_batch(a, wtype, st, describe, describe_len));
-}
-
-// The views of ggml_mul_mat_id -> the arguments of the two expert-indexed entries (qg.h, qg_mul_mat_id_from_view).
-struct MulMatIdArgs {
-    int64_t K, N, n_expert, a_rows, T, n_used, ids_stride, ldc;
+// ---- mul_mat_id: the three expert entries -------------------------------------------------------------------
+// A call of qg_gemm_w4a8_moe, _moe_prefill or _moe_batch under the names of qg.h (ws: the entries with a plan), a
+// qg_moe*_config query of one (describe: name the launch there and launch nothing), and what moe_front adds.
+struct MoeCall {
+    const void* A; int a_rows;
+    const void* B; int n_expert;
+    const int32_t* ids; int64_t ids_stride;
+    float* C; int64_t ldc;  // after moe_front: the floats between slots, never 0
+    int T, n_used, N, K, wtype;
+    void* ws; size_t ws_bytes;
+    hipStream_t st;
+    char* describe; size_t describe_len;
+    long estride;  // moe_front: bytes between experts
+    int slots;     // moe_front: T * n_used
 };
+
+// Bytes of a plan's workspace whose tile region is sized for tiles of min_r rows (qg_moe_plan.hpp).
+size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
+    if (T <= 0 || n_used <= 0 || n_expert <= 0) return 0;
+    return (size_t)moe_plan_layout((long)(T * n_used), (long)n_expert, min_r).total * sizeof(int32_t);
+}
+
+// What the three entries check alike, in the order qg.h documents. rows_ok: the entry takes the 32-element types
+// (otherwise one of them is a type it does not take, checked at the 32-element granule as in run_product). min_r: 0,
+// or the entry runs a plan in a workspace sized for tiles of min_r rows.
+//   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
+//   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
+//   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
+//      an expert stride off the kernel's weight alignment.
+// QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
+int moe_front(MoeCall& c, bool rows_ok, int min_r) {
+    const bool ksb = is_sb_type(c.wtype);
+    const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
+    const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? 256 : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
+                            {{c.A, 3}, {c.B, wmask}, {c.ids, 3}, {c.C, 0}});
+    if (rc != QG_GO) return rc;
+    if ((c.a_rows != 1 && c.a_rows != c.n_used) || c.ids_stride < c.n_used || c.n_expert < 1 || c.ldc < 0 ||
+        (c.ldc > 0 && c.ldc < c.N))
+        return QG_ERR_INVALID_ARG;
+    if (min_r) {
+        if (!c.ws) return QG_ERR_INVALID_ARG;
+        if (((uintptr_t)c.ws & (MOE_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
+        if (c.ws_bytes < moe_ws_bytes(c.T, c.n_used, c.n_expert, min_r)) return QG_ERR_INVALID_ARG;
+    }
+    const int64_t slots = (int64_t)c.T * c.n_used;
+    if (slots > MOE_MAX_SLOTS || (min_r && c.n_expert > MOE_MAX_EXPERTS)) return QG_ERR_UNSUPPORTED;
+    c.slots = (int)slots;
+    if (!c.ldc) c.ldc = c.N;
+    c.estride = (long)c.N * (long)(c.K / block_elems(c.wtype)) * block_bytes(c.wtype);
+    return ((uintptr_t)c.estride & wmask) != 0 ? QG_ERR_UNSUPPORTED : QG_GO;
+}
+
+// the fields MoeArgs and MoePlanArgs have in common
+template <class KernArgs> KernArgs moe_kernel_args(const MoeCall& c) {
+    KernArgs a;
+    a.A = c.A; a.B = c.B; a.ids = c.ids; a.C = c.C;
+    a.ids_stride = (long)c.ids_stride; a.ldc = (long)c.ldc; a.estride = c.estride;
+    a.a_rows = c.a_rows; a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots;
+    return a;
+}
+
+// AUTO at M = 1 sends this (N, K, type) to the type's decode GEMV: the body the two decode entries run per slot
+bool moe_gemv_route(const MoeCall& c) {
+    const GemmArgs q = product_args(c.A, c.B, c.C, 1, c.N, c.K, c.wtype);
+    return is_sb_type(c.wtype) ? select_algo_sb(q) == QG_ALGO_GEMV : select_algo(q) == QG_ALGO_GEMV && gemv_eligible(q);
+}
+
+// qg_gemm_w4a8_moe, qg_moe_config. Its own refusals: a shape off the decode GEMV, LDS records beyond 160 KiB.
+int run_moe(MoeCall& c) {
+    const int rc = moe_front(c, true, 0);
+    if (rc != QG_GO) return rc;
+    if (!moe_gemv_route(c) || !moe_lds_ok(c.wtype, c.K)) return QG_ERR_UNSUPPORTED;
+    MoeArgs a = moe_kernel_args<MoeArgs>(c);
+    a.arow = (long)(c.K / 32) * 36;
+    return hip_status(launch_moe(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_prefill, qg_moe_prefill_config and qg_debug_moe_prefill_plan (which stops after the plan): Q4_K / Q6_K.
+int moe_prefill_args(MoeCall& c, MoePlanArgs& a) {
+    const int rc = moe_front(c, false, MOE_PREFILL_MIN_R);
+    if (rc != QG_GO) return rc;
+    a = moe_kernel_args<MoePlanArgs>(c);
+    a.ws = (int32_t*)c.ws;
+    return QG_GO;
+}
+
+int run_moe_prefill(MoeCall& c) {
+    MoePlanArgs a;
+    const int rc = moe_prefill_args(c, a);
+    if (rc != QG_GO) return rc;
+    return hip_status(launch_moe_prefill(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_batch, qg_moe_batch_config: Q4_K / Q6_K. Its own refusals: a shape off the decode GEMV, K whose
+// records of two rows exceed the LDS (moe_batch_rows), a tile bound beyond 65535.
+int run_moe_batch(MoeCall& c) {
+    const int rc = moe_front(c, false, MOE_BATCH_MIN_R);
+    if (rc != QG_GO) return rc;
+    const int R = moe_batch_rows(c.slots, c.n_expert, c.K, c.wtype);
+    if (!moe_gemv_route(c) || R == 0 || moe_max_tiles(c.slots, c.n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
+    MoePlanArgs a = moe_kernel_args<MoePlanArgs>(c);
+    a.ws = (int32_t*)c.ws;
+    return hip_status(launch_moe_batch(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_moe*_config: the shape alone, as qg_debug_config: 256-B aligned stand-in pointers (a workspace of any size among
+// them), one activation row per token.
+int moe_config(int (*run)(MoeCall&), int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    MoeCall c{(const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
+              wtype, (void*)256, SIZE_MAX, nullptr, buf, len};
+    return run(c);
+}
+
+// The views of ggml_mul_mat_id -> the operands and sizes of an expert entry's call (qg.h, qg_mul_mat_id_from_view).
 int mul_mat_id_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids, const qg_tensor_view* out,
-                    MulMatIdArgs& m) {
+                    MoeCall& c) {
     if (!as || !b || !ids || !out) return QG_ERR_INVALID_ARG;
     if (b->type != QG_TYPE_Q8_1 || ids->type != QG_TYPE_I32 || out->type != QG_TYPE_F32 ||
         !(is_weight_type(as->type) || is_sb_type(as->type)))
@@ -520,9 +531,20 @@ int mul_mat_id_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_
         return QG_ERR_UNSUPPORTED;
     const size_t slot_bytes = n_used > 1 ? out->nb[1] : T > 1 ? out->nb[2] : (size_t)N * sizeof(float);
     if (slot_bytes % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
-    m = {K, N, n_expert, a_rows, T, n_used, T > 1 ? (int64_t)(ids->nb[1] / sizeof(int32_t)) : n_used,
-         (int64_t)(slot_bytes / sizeof(float))};
+    c = {b->data, (int)a_rows, as->data, (int)n_expert, (const int32_t*)ids->data,
+         T > 1 ? (int64_t)(ids->nb[1] / sizeof(int32_t)) : n_used, (float*)out->data, (int64_t)(slot_bytes / sizeof(float)),
+         (int)T, (int)n_used, (int)N, (int)K, as->type};
     return QG_GO;
+}
+
+// qg_mul_mat_id_from_view*: the views, then the entry
+int mul_mat_id_from_view(int (*run)(MoeCall&), const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                         const qg_tensor_view* out, void* ws, size_t ws_bytes, qg_stream_t stream) {
+    MoeCall c;
+    const int rc = mul_mat_id_view(as, b, ids, out, c);
+    if (rc != QG_GO) return rc;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    return run(c);
 }
 }  // namespace
 
@@ -531,100 +553,79 @@ extern "C" {
 int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                      int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                      qg_stream_t stream) {
-    return run_moe(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype,
-                   (hipStream_t)stream, nullptr, 0);
+    MoeCall c{A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, nullptr, 0,
+              (hipStream_t)stream};
+    return run_moe(c);
 }
 
 int qg_moe_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    // the shape alone, as qg_debug_config: 256-B aligned stand-in pointers, one activation row per token
-    return run_moe((const void*)256, 1, (const void*)256, 1, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
-                   wtype, nullptr, buf, len);
+    return moe_config(run_moe, T, n_used, 1, N, K, wtype, buf, len);
 }
 
 int qg_mul_mat_id_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                             qg_tensor_view* out, qg_stream_t stream) {
-    MulMatIdArgs m;
-    const int rc = mul_mat_id_view(as, b, ids, out, m);
-    if (rc != QG_GO) return rc;
-    return qg_gemm_w4a8_moe(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data, m.ids_stride,
-                            (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K, as->type, stream);
+    return mul_mat_id_from_view(run_moe, as, b, ids, out, nullptr, 0, stream);
 }
 
 size_t qg_gemm_w4a8_moe_prefill_workspace_size(int T, int n_used, int n_expert) {
-    return moe_prefill_ws_bytes(T, n_used, n_expert);
+    return moe_ws_bytes(T, n_used, n_expert, MOE_PREFILL_MIN_R);
 }
 
 int qg_gemm_w4a8_moe_prefill(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                              void* workspace, size_t workspace_bytes, qg_stream_t stream) {
-    return run_moe_prefill(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
-                           workspace_bytes, (hipStream_t)stream, nullptr, 0);
+    MoeCall c{A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+              workspace_bytes, (hipStream_t)stream};
+    return run_moe_prefill(c);
 }
 
 int qg_moe_prefill_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    // the shape alone, as qg_moe_config: 256-B aligned stand-in pointers, one activation row per token
-    return run_moe_prefill((const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T,
-                           n_used, N, K, wtype, (void*)256, SIZE_MAX, nullptr, buf, len);
+    return moe_config(run_moe_prefill, T, n_used, n_expert, N, K, wtype, buf, len);
 }
 
 int qg_debug_moe_prefill_plan(const int32_t* ids, int64_t ids_stride, int T, int n_used, int n_expert, int a_rows, int N,
                               int K, int wtype, int32_t* counts, int32_t* sorted, void* workspace, size_t workspace_bytes,
                               qg_stream_t stream) {
     if (T > 0 && n_used > 0 && N > 0 && (!counts || !sorted)) return QG_ERR_INVALID_ARG;
-    const int rc = run_moe_prefill((const void*)256, a_rows, (const void*)256, n_expert, ids, ids_stride, (float*)256, 0, T,
-                                   n_used, N, K, wtype, workspace, workspace_bytes, (hipStream_t)stream, nullptr, 0, true);
-    if (rc != QG_OK || T == 0 || n_used == 0 || N == 0) return rc;
-    const MoePlanLayout L = moe_plan_layout((long)T * n_used, n_expert);
-    const int32_t* ws = (const int32_t*)workspace;
-    hipError_t e = hipMemcpyAsync(counts, ws + L.counts, sizeof(int32_t) * ((size_t)n_expert + 1), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream);
+    // A, B and C are stand-ins: the plan reads none of them
+    MoeCall c{(const void*)256, a_rows, (const void*)256, n_expert, ids, ids_stride, (float*)256, 0, T, n_used, N, K, wtype,
+              workspace, workspace_bytes, (hipStream_t)stream};
+    MoePlanArgs a;
+    const int rc = moe_prefill_args(c, a);
+    if (rc != QG_GO) return rc;
+    hipError_t e = launch_moe_plan(a, moe_prefill_tt(a, wtype), c.st);
+    const MoePlanLayout L = moe_plan_layout(a.slots, n_expert);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(sorted, ws + L.sorted, sizeof(int32_t) * (size_t)T * n_used, hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream);
+        e = hipMemcpyAsync(counts, a.ws + L.counts, sizeof(int32_t) * ((size_t)n_expert + 1), hipMemcpyDeviceToDevice, c.st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(sorted, a.ws + L.sorted, sizeof(int32_t) * (size_t)a.slots, hipMemcpyDeviceToDevice, c.st);
     return hip_status(e);
 }
 
 int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
-    MulMatIdArgs m;
-    const int rc = mul_mat_id_view(as, b, ids, out, m);
-    if (rc != QG_GO) return rc;
-    return qg_gemm_w4a8_moe_prefill(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data,
-                                    m.ids_stride, (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K,
-                                    as->type, workspace, workspace_bytes, stream);
+    return mul_mat_id_from_view(run_moe_prefill, as, b, ids, out, workspace, workspace_bytes, stream);
 }
 
 size_t qg_gemm_w4a8_moe_batch_workspace_size(int T, int n_used, int n_expert) {
-    return moe_batch_ws_bytes(T, n_used, n_expert);
+    return moe_ws_bytes(T, n_used, n_expert, MOE_BATCH_MIN_R);
 }
 
 int qg_gemm_w4a8_moe_batch(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
                            int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                            void* workspace, size_t workspace_bytes, qg_stream_t stream) {
-    return run_moe_batch(A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
-                         workspace_bytes, (hipStream_t)stream, nullptr, 0);
+    MoeCall c{A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+              workspace_bytes, (hipStream_t)stream};
+    return run_moe_batch(c);
 }
 
 int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
-    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
-    buf[0] = 0;
-    // the shape alone, as qg_moe_config: 256-B aligned stand-in pointers, one activation row per token
-    return run_moe_batch((const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T,
-                         n_used, N, K, wtype, (void*)256, SIZE_MAX, nullptr, buf, len);
+    return moe_config(run_moe_batch, T, n_used, n_expert, N, K, wtype, buf, len);
 }
 
 int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                   qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
-    MulMatIdArgs m;
-    const int rc = mul_mat_id_view(as, b, ids, out, m);
-    if (rc != QG_GO) return rc;
-    return qg_gemm_w4a8_moe_batch(b->data, (int)m.a_rows, as->data, (int)m.n_expert, (const int32_t*)ids->data,
-                                  m.ids_stride, (float*)out->data, m.ldc, (int)m.T, (int)m.n_used, (int)m.N, (int)m.K,
-                                  as->type, workspace, workspace_bytes, stream);
+    return mul_mat_id_from_view(run_moe_batch, as, b, ids, out, workspace, workspace_bytes, stream);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -172,6 +172,10 @@ __device__ __forceinline__ int xcd_tile(int b, int G) {
     const int g8 = G >> 3, r8 = G & 7, x = b & 7;
     return x * g8 + min(x, r8) + (b >> 3);
 }
+// this workgroup's tile along x: the XCD order on a grid of one dispatch round (512 workgroups), the linear one beyond
+__device__ __forceinline__ int xcd_tile_x() {
+    return gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+}
 
 // Per-block fp32 term, operation order as in the reference (see header comment).
 // fs = (float)sumi (exact: |sumi| < 2^24).

@@ -2,7 +2,9 @@
 // (qg_workspace.hip, qg_capture_fuse.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <atomic>
 #include <mutex>
@@ -99,6 +101,10 @@ int device_cus();
 // printf-style description of a kernel instantiation into g.describe (qg_debug_config). SUMI is
 // deliberately not part of it: the parity hook must name the product's kernel.
 void describe_kernel(const GemmArgs& g, const char* fmt, ...);
+// the same into any buffer: the config lines of the mul_mat_id entries (qg_moe*_config), which have no GemmArgs
+template <class... V> void describe_line(char* buf, size_t len, const char* fmt, V... v) {
+    if (buf && len) snprintf(buf, len, fmt, v...);
+}
 
 // GEMV / small batch (M <= 8): nibble-plane v_dot8 (Q4_0 / Q4_1) or v_dot4 (Q5_x / Q8_0) on
 // register-resident weight units, activation records staged in LDS.
@@ -122,6 +128,9 @@ struct MoeArgs {
     long ids_stride, ldc, estride, arow;  // elements, floats, bytes, bytes of one activation row
     int a_rows, n_used, n_expert, N, K, slots;
 };
+static_assert(sizeof(MoeArgs) == 88 && offsetof(MoeArgs, ids_stride) == 32 && offsetof(MoeArgs, estride) == 48 &&
+                  offsetof(MoeArgs, arow) == 56 && offsetof(MoeArgs, a_rows) == 64 && offsetof(MoeArgs, slots) == 84,
+              "the kernarg layout");
 // describe: name the kernel there (qg_moe_config) and launch nothing. The caller has checked that AUTO at M = 1
 // takes the GEMV of the type (gemv_eligible, q4k_/q6k_gemv_eligible) and moe_lds_ok.
 hipError_t launch_moe(const MoeArgs& a, int wtype, hipStream_t st, char* describe = nullptr, size_t describe_len = 0);

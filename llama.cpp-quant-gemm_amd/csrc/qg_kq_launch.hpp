@@ -2,7 +2,7 @@
 // eligibility of the decode GEMV (qg_q4k_gemv.hip, qg_q6k_gemv.hip) and of the MFMA prefill (qg_q4k_mmq.hip,
 // qg_q6k_mmq.hip). The kernels themselves stay one per type ("Q4_K": what was tried to share them); within
 // a type a kernel's body is one text, qg_<type>_{gemv,mmq}_body.inc, which the shipped kernel and its expert-indexed /
-// expert-grouped twins (qg_moe.hip, qg_moe_batch.hip, qg_moe_prefill.hip) all include.
+// expert-grouped twins (qg_moe.hip, qg_moe_batch.hip, qg_moe_prefill.hip; their plan: qg_moe_plan.hip) all include.
 //
 // A type's file passes a struct F of constants and static functions:
 //   GEMV:  REC_DW, LDS_MAX (dwords of an LDS record per (token, super-block), the bound on all of them), WMASK (the

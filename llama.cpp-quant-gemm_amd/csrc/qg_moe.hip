@@ -87,15 +87,10 @@ template <int WGS> __device__ __forceinline__ bool moe_slot(const MoeArgs& a, in
     return true;
 }
 
-// the single launch's XCD-aware tile order within the slot (gemv_body, gemvg_kernel)
-__device__ __forceinline__ int moe_tile() {
-    return gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-}
-
 template <int F, int BPL, int LPR, int WGS, int ONEU, int TPW>
 __global__ __launch_bounds__(WGS) void gemv_moe_kernel(const MoeArgs a) {
     constexpr int RPB = (WGS / 64) * (64 / LPR) * TPW;  // rows per workgroup
-    const int tile = moe_tile();
+    const int tile = xcd_tile_x();  // the single launch's order within the slot
     MoeSlot s;
     if (!moe_slot<WGS>(a, RPB, tile, s)) return;
     gemv_body<F, 1, BPL, LPR, WGS, false, AIN_Q8_1, false, true, ONEU, TPW>(s.A, s.B, 0, 0, 1, a.N, a.K, s.C, 0, 0, 1,
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(WGS) void gemv_moe_kernel(const MoeArgs a) {
 template <int WT, int LPR, int WGS, bool ONE>
 __global__ __launch_bounds__(WGS) void kq_moe_kernel(const MoeArgs a) {
     constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const int tile = moe_tile();
+    const int tile = xcd_tile_x();  // the single launch's order within the slot
     MoeSlot s;
     if (!moe_slot<WGS>(a, RPB, tile, s)) return;
     if constexpr (WT == QG_TYPE_Q4_K) q4k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
@@ -119,12 +114,6 @@ struct MoeLaunch {
     char* describe;  // qg_moe_config: name the kernel here, launch nothing
     size_t describe_len;
 };
-
-template <class... V> void moe_describe(const MoeLaunch& L, const char* fmt, V... v) {
-    GemmArgs g;
-    g.describe = L.describe; g.describe_len = L.describe_len;
-    describe_kernel(g, fmt, v...);
-}
 
 template <class Kern>
 hipError_t moe_enqueue(Kern k, const MoeLaunch& L, int rpb, int wgs, size_t lds, std::atomic<unsigned long long>& done) {
@@ -140,8 +129,8 @@ template <int F, int BPL, int LPR, int WGS, int ONEU, int TPW> hipError_t moe_ro
     constexpr int RPB = (WGS / 64) * (64 / LPR) * TPW;
     const size_t lds = gemv_lds_bytes<F, BPL>(1, L.a.K);
     if (L.describe) {
-        moe_describe(L, "moe:gemv F=%d BPL=%d LPR=%d WGS=%d ONEU=%d TPW=%d grid=%dx%d lds=%zu", F, BPL, LPR, WGS, ONEU, TPW,
-                     (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
+        describe_line(L.describe, L.describe_len, "moe:gemv F=%d BPL=%d LPR=%d WGS=%d ONEU=%d TPW=%d grid=%dx%d lds=%zu", F, BPL,
+                      LPR, WGS, ONEU, TPW, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
         return hipSuccess;
     }
     static std::atomic<unsigned long long> done;
@@ -188,8 +177,8 @@ template <int WT, int LPR, int WGS, bool ONE> hipError_t moe_kq_k(const MoeLaunc
     constexpr int RPB = (WGS / 64) * (64 / LPR);
     const size_t lds = (size_t)(L.a.K / SB_ELEMS) * (WT == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4;
     if (L.describe) {
-        moe_describe(L, "moe:%s LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", LPR,
-                     WGS, (int)ONE, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
+        describe_line(L.describe, L.describe_len, "moe:%s LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
+                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", LPR, WGS, (int)ONE, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
         return hipSuccess;
     }
     static std::atomic<unsigned long long> done;

@@ -2,14 +2,14 @@
 // families "moeb:q4k_gemv" and "moeb:q6k_gemv". DESIGN.md 3e.
 //
 // Two launches on the caller's stream, no allocation, no synchronisation, the host never reads ids:
-//  1. moe_plan_kernel (qg_moe_prefill.hip) with tiles of R = 2, 4 or 8 rows: the T * n_used slots counting-sorted by
+//  1. moe_plan_kernel (qg_moe_plan.hip) with tiles of R = 2, 4 or 8 rows: the T * n_used slots counting-sorted by
 //     expert id into the caller's workspace, one record {bin, first sorted position, rows} per tile.
 //  2. q4k_moeb_kernel / q6k_moeb_kernel<MT = R, LPR, WGS, ONE>: the body of q4k_gemv_kernel / q6k_gemv_kernel
 //     (qg_q4k_gemv.hip, qg_q6k_gemv.hip: the work decomposition is described there), the same text included
 //     (qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc), at the LPR, WGS and ONE the single M = 1 call takes for this K
 //     (kq_gemv_launch_lpr). What differs, all of it in the prologue and in the body's two hooks:
 //       * blockIdx.y is a tile index. The workgroup reads n_tiles and its record (uniform) and returns at once
-//         beyond n_tiles: gridDim.y is the host's upper bound moe_prefill_max_tiles.
+//         beyond n_tiles: gridDim.y is the host's upper bound moe_max_tiles.
 //       * activation block g = m * K/32 + b of the staging is block b of row rows[first + m] (QG_KQ_ABLK): the R
 //         gathered rows land in the LDS records of tokens 0 .. rows - 1, and the body runs with M = tile.rows.
 //       * the expert's matrix is B + e * estride, formed in 64 bits before any weight address.
@@ -27,26 +27,10 @@
 namespace qg {
 namespace {
 
-// The tile of this workgroup. false: blockIdx.y is beyond n_tiles, or the tile belongs to the invalid bin and its
-// rows are zeroed here (RPB: the workgroup's weight rows).
-struct MoebTile {
-    int e, rows;               // expert, rows (1 .. R)
-    const int32_t* sorted;     // the tile's slots
-    const int32_t* arows;      // their activation rows
-};
-template <int RPB, int WGS> __device__ __forceinline__ bool moeb_tile(const MoePrefillArgs& a, int tile, MoebTile& t) {
-    const int32_t* __restrict__ ws = a.ws;
-    const MoePlanLayout L = moe_plan_layout(a.slots, a.n_expert);  // (the offsets do not depend on the tile size)
-    // both loads at once (the record's place is inside the workspace for every blockIdx.y of the grid, whatever it
-    // holds beyond n_tiles): one round trip to memory before the workgroup knows its work, not two
-    const int n_tiles = ws[0];
-    const int4 rec = reinterpret_cast<const int4*>(ws + L.tiles)[blockIdx.y];
-    if ((int)blockIdx.y >= __builtin_amdgcn_readfirstlane(n_tiles)) return false;
-    t.e = __builtin_amdgcn_readfirstlane(rec.x);
-    const int first = __builtin_amdgcn_readfirstlane(rec.y);
-    t.rows = __builtin_amdgcn_readfirstlane(rec.z);
-    t.sorted = ws + L.sorted + first;
-    t.arows = ws + L.rows + first;
+// The tile of this workgroup (moe_tile_lookup). false: blockIdx.y is beyond n_tiles, or the tile belongs to the invalid
+// bin and its rows are zeroed here (RPB: the workgroup's weight rows).
+template <int RPB, int WGS> __device__ __forceinline__ bool moeb_tile(const MoePlanArgs& a, int tile, MoeTile& t) {
+    if (!moe_tile_lookup(a, t)) return false;
     if ((unsigned)t.e >= (unsigned)a.n_expert) {
         for (int idx = threadIdx.x; idx < t.rows * RPB; idx += WGS) {
             const int p = idx / RPB, n = tile * RPB + (idx - p * RPB);
@@ -57,11 +41,6 @@ template <int RPB, int WGS> __device__ __forceinline__ bool moeb_tile(const MoeP
     return true;
 }
 
-// the single launch's XCD-aware tile order within the tile's expert (q4k_gemv_kernel, kq_moe_kernel)
-__device__ __forceinline__ int moeb_row_tile() {
-    return gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-}
-
 // The body's names: the operands of the tile's expert, M = the tile's rows, and the two hooks. srt[m]: the slot of
 // position m (positions past the tile's rows take the last one: loaded, never used), read before the weight stream.
 #define QG_KQ_DECLARE_TILE  // declared by the kernels below, before the tile lookup
@@ -69,8 +48,8 @@ __device__ __forceinline__ int moeb_row_tile() {
 #define QG_KQ_OUT(m) C[(long)srt[m] * ldc + row]
 #define QG_MOEB_PROLOGUE                                                                          \
     constexpr int RPB_ = (WGS / 64) * (64 / LPR);                                                 \
-    const int tile = moeb_row_tile();                                                             \
-    MoebTile mt;                                                                                  \
+    const int tile = xcd_tile_x();                                                                \
+    MoeTile mt;                                                                                   \
     if (!moeb_tile<RPB_, WGS>(a, tile, mt)) return;                                               \
     const uint32_t* __restrict__ A = static_cast<const uint32_t*>(a.A);                           \
     const uint8_t* __restrict__ B = static_cast<const uint8_t*>(a.B) + (long)mt.e * a.estride;    \
@@ -81,12 +60,12 @@ __device__ __forceinline__ int moeb_row_tile() {
     int srt[MT];                                                                                  \
     _Pragma("unroll") for (int m = 0; m < MT; ++m) srt[m] = mt.sorted[min(m, mt.rows - 1)];
 
-template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) void q4k_moeb_kernel(const MoePrefillArgs a) {
+template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) void q4k_moeb_kernel(const MoePlanArgs a) {
     QG_MOEB_PROLOGUE
 #include "qg_q4k_gemv_body.inc"
 }
 
-template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) void q6k_moeb_kernel(const MoePrefillArgs a) {
+template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) void q6k_moeb_kernel(const MoePlanArgs a) {
     QG_MOEB_PROLOGUE
 #include "qg_q6k_gemv_body.inc"
 }
@@ -99,7 +78,7 @@ template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) 
 constexpr size_t moeb_rec_bytes(int wtype) { return (wtype == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4; }
 
 struct MoebLaunch {
-    const MoePrefillArgs& a;
+    const MoePlanArgs& a;
     hipStream_t st;
     char* describe;
     size_t describe_len;
@@ -107,14 +86,12 @@ struct MoebLaunch {
 
 template <int WT, int MT, int LPR, int WGS, bool ONE> hipError_t moeb_k(const MoebLaunch& L) {
     constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const MoePrefillArgs& a = L.a;
+    const MoePlanArgs& a = L.a;
     const size_t lds = (size_t)MT * (a.K / SB_ELEMS) * moeb_rec_bytes(WT);
-    const int gx = (a.N + RPB - 1) / RPB, gy = (int)moe_prefill_max_tiles(a.slots, a.n_expert, MT);
+    const int gx = (a.N + RPB - 1) / RPB, gy = (int)moe_max_tiles(a.slots, a.n_expert, MT);
     if (L.describe) {
-        GemmArgs g;
-        g.describe = L.describe; g.describe_len = L.describe_len;
-        describe_kernel(g, "moeb:%s R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv",
-                        MT, LPR, WGS, (int)ONE, gx, gy, lds);
+        describe_line(L.describe, L.describe_len, "moeb:%s R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
+                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", MT, LPR, WGS, (int)ONE, gx, gy, lds);
         return hipSuccess;
     }
     auto k = [] {
@@ -166,7 +143,7 @@ int moe_batch_rows(long slots, int n_expert, int K, int wtype) {
     return r >= MOE_BATCH_MIN_R ? r : 0;
 }
 
-hipError_t launch_moe_batch(const MoePrefillArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+hipError_t launch_moe_batch(const MoePlanArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
     const MoebLaunch L{a, st, describe, describe_len};
     if (wtype == QG_TYPE_Q4_K) return moeb_r<QG_TYPE_Q4_K>(L);
     if (wtype == QG_TYPE_Q6_K) return moeb_r<QG_TYPE_Q6_K>(L);

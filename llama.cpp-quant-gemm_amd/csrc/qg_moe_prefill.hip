@@ -2,17 +2,15 @@
 // sizes), families "moe:q4k_mmq" and "moe:q6k_mmq". DESIGN.md 3d.
 //
 // Two launches on the caller's stream, no allocation, no synchronisation, the host never reads ids:
-//  1. moe_plan_kernel: one workgroup counting-sorts the T * n_used slots by expert id into the caller's workspace
-//     (qg_moe_prefill.hpp, MoePlanLayout): counts per bin (ids that name no expert: a bin of their own, the last),
-//     the slots and their activation rows in bin order, and one record {bin, first sorted position, rows} per tile
-//     of R = 16 TT rows with their number n_tiles. Its counters live in LDS and are zeroed by the kernel, so a
-//     replay starts clean. The order of the slots of one expert is whatever the LDS atomics give.
+//  1. moe_plan_kernel (qg_moe_plan.hip) with tiles of R = 16 TT rows: the T * n_used slots counting-sorted by expert id
+//     into the caller's workspace (qg_moe_plan.hpp, MoePlanLayout), one record {bin, first sorted position, rows} per
+//     tile with their number n_tiles.
 //  2. q4k_moe_mmq_kernel / q6k_moe_mmq_kernel<TT, RG>: the K loops of q4k_mmq_kernel / q6k_mmq_kernel (qg_q4k_mmq.hip,
 //     qg_q6k_mmq.hip: the work decomposition is described there), the same text included (qg_q4k_mmq_body.inc,
 //     qg_q6k_mmq_body.inc; text and not a function, so that the shipped code objects do not move: DESIGN.md 3c), between
 //     a prologue and a reduction of their own. What differs:
 //       * blockIdx.y is a tile index. The workgroup reads n_tiles and its record (uniform) and returns at once
-//         beyond n_tiles: gridDim.y is the host's upper bound moe_prefill_max_tiles.
+//         beyond n_tiles: gridDim.y is the host's upper bound moe_max_tiles.
 //       * the activation row of tile position p is rows[first + min(p, rows - 1)]: positions past the tile's rows
 //         are loaded and multiplied, never stored (the shipped kernels' rule at M - 1). Each lane loads the row
 //         indices it needs once, before the K loop; a token load takes its (wave-uniform) index with v_readlane.
@@ -39,114 +37,11 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 #define QG_MOE_PREFILL_FORM 0
 #endif
 
-// ---- the plan ---------------------------------------------------------------------------------------------------
-constexpr int PLAN_WGS = 1024;
-constexpr int PLAN_BINS = MOE_PREFILL_MAX_EXPERTS + 1;
-
-// rsh: log2 of the tile's rows
-__global__ __launch_bounds__(PLAN_WGS) void moe_plan_kernel(const MoePrefillArgs a, int rsh) {
-    __shared__ int cnt[PLAN_BINS];       // slots per bin; the scatter's cursors afterwards
-    __shared__ int poff[PLAN_BINS + 1];  // first sorted position of a bin
-    __shared__ int toff[PLAN_BINS + 1];  // first tile of a bin
-    __shared__ int scan_p[PLAN_WGS], scan_t[PLAN_WGS];
-    const int tid = threadIdx.x, E = a.n_expert, nbin = E + 1, R = 1 << rsh;
-    const MoePlanLayout L = moe_plan_layout(a.slots, E);
-    int32_t* __restrict__ ws = a.ws;
-
-    for (int b = tid; b < nbin; b += PLAN_WGS) cnt[b] = 0;
-    __syncthreads();
-    for (int s = tid; s < a.slots; s += PLAN_WGS) {
-        const int t = s / a.n_used, u = s - t * a.n_used;
-        const int e = a.ids[(long)t * a.ids_stride + u];
-        atomicAdd(&cnt[(unsigned)e < (unsigned)E ? e : E], 1);
-    }
-    __syncthreads();
-    // exclusive prefix sums of the counts and of the tiles per bin: thread i owns bins [b0, b1)
-    const int per = (nbin + PLAN_WGS - 1) / PLAN_WGS;
-    const int b0 = min(tid * per, nbin), b1 = min(b0 + per, nbin);
-    int sp = 0, stl = 0;
-    for (int b = b0; b < b1; ++b) {
-        sp += cnt[b];
-        stl += (cnt[b] + R - 1) >> rsh;
-    }
-    scan_p[tid] = sp;
-    scan_t[tid] = stl;
-    __syncthreads();
-    for (int d = 1; d < PLAN_WGS; d <<= 1) {
-        const int vp = tid >= d ? scan_p[tid - d] : 0, vt = tid >= d ? scan_t[tid - d] : 0;
-        __syncthreads();
-        scan_p[tid] += vp;
-        scan_t[tid] += vt;
-        __syncthreads();
-    }
-    {
-        int p = scan_p[tid] - sp, tl = scan_t[tid] - stl;
-        for (int b = b0; b < b1; ++b) {
-            poff[b] = p;
-            toff[b] = tl;
-            p += cnt[b];
-            tl += (cnt[b] + R - 1) >> rsh;
-        }
-        if (tid == PLAN_WGS - 1) {
-            poff[nbin] = scan_p[tid];
-            toff[nbin] = scan_t[tid];
-        }
-    }
-    __syncthreads();
-    const int n_tiles = toff[nbin];
-    if (tid == 0) *reinterpret_cast<int4*>(ws) = make_int4(n_tiles, poff[E], R, 0);
-    for (int b = tid; b < nbin; b += PLAN_WGS) ws[L.counts + b] = cnt[b];
-    // tile j belongs to the bin b with toff[b] <= j < toff[b + 1] (empty bins have no such j)
-    for (int j = tid; j < n_tiles; j += PLAN_WGS) {
-        int lo = 0, hi = nbin;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (toff[mid] <= j) lo = mid;
-            else hi = mid;
-        }
-        const int i = j - toff[lo];
-        reinterpret_cast<int4*>(ws + L.tiles)[j] = make_int4(lo, poff[lo] + (i << rsh), min(R, cnt[lo] - (i << rsh)), 0);
-    }
-    __syncthreads();
-    for (int b = tid; b < nbin; b += PLAN_WGS) cnt[b] = poff[b];
-    __syncthreads();
-    for (int s = tid; s < a.slots; s += PLAN_WGS) {
-        const int t = s / a.n_used, u = s - t * a.n_used;
-        const int e = a.ids[(long)t * a.ids_stride + u];
-        const int p = atomicAdd(&cnt[(unsigned)e < (unsigned)E ? e : E], 1);
-        ws[L.sorted + p] = s;
-        // a_rows is 1 (the token's one row) or n_used (a row per slot): u % a_rows
-        ws[L.rows + p] = t * a.a_rows + (a.a_rows > 1 ? u : 0);
-    }
-}
-
 // ---- what the two gathered kernels share --------------------------------------------------------------------------
 constexpr int MMQ_WAVES = 8;
 constexpr int MMQ_WGS = 64 * MMQ_WAVES;
 constexpr int TOK_DW = Q4K_TOK_DW;  // one token's 8 blocks of a super-block: the gathered loads serve both types
 static_assert(Q6K_TOK_DW == TOK_DW, "one activation staging layout");
-
-// The tile of this workgroup. false: blockIdx.y is beyond n_tiles.
-struct MoeTile {
-    int e, first, rows;        // bin, first sorted position, rows (1 .. 16 TT)
-    const int32_t* sorted;     // + first: the tile's slots
-    const int32_t* arows;      // + first: their activation rows
-};
-__device__ __forceinline__ bool moe_tile_lookup(const MoePrefillArgs& a, MoeTile& t) {
-    const int32_t* __restrict__ ws = a.ws;
-    const MoePlanLayout L = moe_plan_layout(a.slots, a.n_expert);
-    // both loads at once (the record's place is inside the workspace for every blockIdx.y of the grid, whatever it
-    // holds beyond n_tiles): one round trip to memory before the workgroup knows its work, not two
-    const int n_tiles = ws[0];
-    const int4 rec = reinterpret_cast<const int4*>(ws + L.tiles)[blockIdx.y];
-    if ((int)blockIdx.y >= __builtin_amdgcn_readfirstlane(n_tiles)) return false;
-    t.e = __builtin_amdgcn_readfirstlane(rec.x);
-    t.first = __builtin_amdgcn_readfirstlane(rec.y);
-    t.rows = __builtin_amdgcn_readfirstlane(rec.z);
-    t.sorted = ws + L.sorted + t.first;
-    t.arows = ws + L.rows + t.first;
-    return true;
-}
 
 // The activation rows this lane needs, loaded once: rowv[t] that of position 16 t + (lane & 15) (a token load reads
 // position p's from lane p & 15), tailv[t][b] that of the lane's tail load b. Positions past the tile's rows take
@@ -192,7 +87,7 @@ __device__ __forceinline__ void moe_store_tile(const uint32_t (&src)[16 / RG + (
 }
 
 // A tile of the invalid bin: +0.0f to this workgroup's 16 RG rows of the tile's slots.
-template <int TT, int RG> __device__ __forceinline__ void moe_zero_tile(const MoePrefillArgs& a, const MoeTile& tl, int tile) {
+template <int TT, int RG> __device__ __forceinline__ void moe_zero_tile(const MoePlanArgs& a, const MoeTile& tl, int tile) {
     constexpr int PT = TT * 256;
     for (int idx = threadIdx.x; idx < RG * PT; idx += MMQ_WGS) {
         const int g = idx / PT, o = idx - g * PT;
@@ -205,7 +100,7 @@ template <int TT, int RG> __device__ __forceinline__ void moe_zero_tile(const Mo
 // has read its last tile), lane (c, q) writes rows 4q .. 4q + 3 of token c (one 16-B store); then each output is the
 // sum of its KS partials in slice order, stored to its slot's row.
 template <int TT, int RG>
-__device__ __forceinline__ void moe_reduce_store(const MoePrefillArgs& a, const MoeTile& tl, uint32_t* smem,
+__device__ __forceinline__ void moe_reduce_store(const MoePlanArgs& a, const MoeTile& tl, uint32_t* smem,
                                                  const float (&acc)[TT][4], int ks, int rg, int r16, int q, int tile) {
     constexpr int KS = MMQ_WAVES / RG, PT = TT * 256;  // outputs per (slice, row group)
     __syncthreads();
@@ -226,7 +121,7 @@ __device__ __forceinline__ void moe_reduce_store(const MoePrefillArgs& a, const 
 }
 
 // ---- Q4_K: q4k_mmq_kernel (qg_q4k_mmq.hip) on a tile of gathered rows ----------------------------------------------
-template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq_kernel(const MoePrefillArgs a) {
+template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq_kernel(const MoePlanArgs a) {
     static_assert(RG == 1 || RG == 4, "row groups per workgroup");
     constexpr int W = MMQ_WAVES, KS = W / RG;
     constexpr int NBUF = RG > 1 ? 2 : 1;
@@ -240,6 +135,7 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int rg = wave % RG, ks = wave / RG;
     const int r16 = lane & 15, q = lane >> 4;
+    // xcd_tile_x() (qg_common.hpp), written out: through the function these kernels' code objects move
     const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     if (mt.e >= a.n_expert) {
         moe_zero_tile<TT, RG>(a, mt, tile);
@@ -271,7 +167,7 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q4k_moe_mmq
 }
 
 // ---- Q6_K: q6k_mmq_kernel (qg_q6k_mmq.hip) on a tile of gathered rows ----------------------------------------------
-template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq_kernel(const MoePrefillArgs a) {
+template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq_kernel(const MoePlanArgs a) {
     static_assert(RG == 1 || RG == 4, "row groups per workgroup");
     constexpr int W = MMQ_WAVES, KS = W / RG;
     constexpr int NBUF = RG > 1 ? 2 : 1;
@@ -285,6 +181,7 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int rg = wave % RG, ks = wave / RG;
     const int r16 = lane & 15, q = lane >> 4;
+    // xcd_tile_x() (qg_common.hpp), written out: through the function these kernels' code objects move
     const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     if (mt.e >= a.n_expert) {
         moe_zero_tile<TT, RG>(a, mt, tile);
@@ -327,7 +224,7 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq
 struct MoeForm {
     int tt, rg;
 };
-MoeForm moe_prefill_form(const MoePrefillArgs& a, int wtype) {
+MoeForm moe_prefill_form(const MoePlanArgs& a, int wtype) {
     constexpr MoeForm forms[] = {{1, 1}, {2, 1}, {4, 1}, {4, 4}};
     if (QG_MOE_PREFILL_FORM) return forms[QG_MOE_PREFILL_FORM - 1];
     if (wtype == QG_TYPE_Q6_K && a.K <= 4 * SB_ELEMS) return forms[3];
@@ -339,13 +236,11 @@ MoeForm moe_prefill_form(const MoePrefillArgs& a, int wtype) {
 }
 
 template <int WT, int TT, int RG>
-hipError_t moe_prefill_k(const MoePrefillArgs& a, hipStream_t st, char* describe, size_t describe_len) {
-    const int gx = (a.N + 16 * RG - 1) / (16 * RG), gy = (int)moe_prefill_max_tiles(a.slots, a.n_expert, 16 * TT);
+hipError_t moe_prefill_k(const MoePlanArgs& a, hipStream_t st, char* describe, size_t describe_len) {
+    const int gx = (a.N + 16 * RG - 1) / (16 * RG), gy = (int)moe_max_tiles(a.slots, a.n_expert, 16 * TT);
     if (describe) {
-        GemmArgs g;
-        g.describe = describe; g.describe_len = describe_len;
-        describe_kernel(g, "moe:%s TT=%d RG=%d KS=%d R=%d grid=%dx%d", WT == QG_TYPE_Q4_K ? "q4k_mmq" : "q6k_mmq", TT, RG,
-                        MMQ_WAVES / RG, 16 * TT, gx, gy);
+        describe_line(describe, describe_len, "moe:%s TT=%d RG=%d KS=%d R=%d grid=%dx%d", WT == QG_TYPE_Q4_K ? "q4k_mmq" : "q6k_mmq",
+                      TT, RG, MMQ_WAVES / RG, 16 * TT, gx, gy);
         return hipSuccess;
     }
     const hipError_t e = launch_moe_plan(a, TT, st);
@@ -355,7 +250,7 @@ hipError_t moe_prefill_k(const MoePrefillArgs& a, hipStream_t st, char* describe
     return hipGetLastError();
 }
 
-template <int WT> hipError_t moe_prefill_t(const MoePrefillArgs& a, hipStream_t st, char* describe, size_t describe_len) {
+template <int WT> hipError_t moe_prefill_t(const MoePlanArgs& a, hipStream_t st, char* describe, size_t describe_len) {
     const MoeForm f = moe_prefill_form(a, WT);
     if (f.rg == 4) return moe_prefill_k<WT, 4, 4>(a, st, describe, describe_len);
     if (f.tt == 4) return moe_prefill_k<WT, 4, 1>(a, st, describe, describe_len);
@@ -365,18 +260,13 @@ template <int WT> hipError_t moe_prefill_t(const MoePrefillArgs& a, hipStream_t 
 
 }  // namespace
 
-int moe_prefill_tt(const MoePrefillArgs& a, int wtype) { return moe_prefill_form(a, wtype).tt; }
+int moe_prefill_tt(const MoePlanArgs& a, int wtype) { return moe_prefill_form(a, wtype).tt; }
 
-hipError_t launch_moe_plan_rows(const MoePrefillArgs& a, int rsh, hipStream_t st) {
-    hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(PLAN_WGS), 0, st, a, rsh);
-    return hipGetLastError();
-}
-
-hipError_t launch_moe_plan(const MoePrefillArgs& a, int tt, hipStream_t st) {
+hipError_t launch_moe_plan(const MoePlanArgs& a, int tt, hipStream_t st) {
     return launch_moe_plan_rows(a, tt == 4 ? 6 : tt == 2 ? 5 : 4, st);
 }
 
-hipError_t launch_moe_prefill(const MoePrefillArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+hipError_t launch_moe_prefill(const MoePlanArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
     if (wtype == QG_TYPE_Q4_K) return moe_prefill_t<QG_TYPE_Q4_K>(a, st, describe, describe_len);
     if (wtype == QG_TYPE_Q6_K) return moe_prefill_t<QG_TYPE_Q6_K>(a, st, describe, describe_len);
     return hipErrorInvalidValue;

@@ -225,20 +225,9 @@ def gemm_w4a8_grouped(activations_q, weights_q, Ns, M: int, K: int, wtype: int =
     return res
 
 
-def gemm_w4a8_moe(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor, T: int, n_used: int, N: int,
-                  K: int, wtype: int = Q4_0, a_rows: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
-    """ggml's mul_mat_id for a decode step in ONE launch, the expert ids read on the device (qg_gemm_w4a8_moe):
-    C[t, u, :] = experts_q[ids[t, u]] . activation_q[t, u % a_rows], float32 [T, n_used, N].
-
-    ``activation_q``: Q8_1 [T, a_rows, K/32, 36], a_rows 1 (one row per token) or n_used (one per slot).
-    ``experts_q``: [n_expert, N, K/bs, block bytes] of ``wtype`` (any of GEMM_WEIGHT_TYPES), dense.
-    ``ids``: int32 CUDA tensor [T, n_used]; a view with a row stride is fine (``ids.stride(1) == 1``). Never copied
-    to the host: a captured graph follows the ids each replay finds. An id outside [0, n_expert) gives zeros.
-    ``out``: optional float32 [T, n_used, N] with ``out.stride(2) == 1``, ``out.stride(1) >= N`` floats between
-    slots and ``out.stride(0) == n_used * out.stride(1)``.
-    Each slot is bit-identical to ``gemm_w4a8`` on its row and expert. Shapes the expert-indexed GEMV does not
-    serve (odd K/32, more than 65535 slots, ...) raise."""
-    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
+def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: int, wtype: int, a_rows: int, out):
+    """What the three mul_mat_id wrappers check alike, after the weight type: the contiguous operands, n_expert,
+    ids_stride, ``out`` (allocated unless given) and its ldc."""
     be = block_elems(wtype)
     _require(K % be == 0, f"K must be divisible by {be}, got {K}")
     _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
@@ -262,6 +251,41 @@ def gemm_w4a8_moe(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torc
         _require(N <= 1 or out.stride(2) == 1, "bad out tensor: rows must be dense")
     ldc = out.stride(1) if n_used > 1 else out.stride(0) if T > 1 else N
     _require(ldc >= N and (T <= 1 or n_used <= 1 or out.stride(0) == n_used * ldc), "bad out tensor: slots must be evenly spaced")
+    return a, w, n_expert, ids_stride, out, ldc
+
+
+def _moe_workspace(workspace, nbytes: int, dev: torch.device) -> torch.Tensor:
+    """The caller's workspace checked, or one of nbytes allocated."""
+    if workspace is None:
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _require(workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
+             "workspace must be a contiguous CUDA uint8 tensor")
+    _require(workspace.device == dev, "workspace must be on the experts' device")
+    return workspace
+
+
+def _config(sym: str, *args) -> str:
+    """The config line a qg_*_config symbol writes for args."""
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(getattr(_lib.load(), sym)(*args, buf, 256), sym[3:])
+    return buf.value.decode()
+
+
+def gemm_w4a8_moe(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor, T: int, n_used: int, N: int,
+                  K: int, wtype: int = Q4_0, a_rows: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ggml's mul_mat_id for a decode step in ONE launch, the expert ids read on the device (qg_gemm_w4a8_moe):
+    C[t, u, :] = experts_q[ids[t, u]] . activation_q[t, u % a_rows], float32 [T, n_used, N].
+
+    ``activation_q``: Q8_1 [T, a_rows, K/32, 36], a_rows 1 (one row per token) or n_used (one per slot).
+    ``experts_q``: [n_expert, N, K/bs, block bytes] of ``wtype`` (any of GEMM_WEIGHT_TYPES), dense.
+    ``ids``: int32 CUDA tensor [T, n_used]; a view with a row stride is fine (``ids.stride(1) == 1``). Never copied
+    to the host: a captured graph follows the ids each replay finds. An id outside [0, n_expert) gives zeros.
+    ``out``: optional float32 [T, n_used, N] with ``out.stride(2) == 1``, ``out.stride(1) >= N`` floats between
+    slots and ``out.stride(0) == n_used * out.stride(1)``.
+    Each slot is bit-identical to ``gemm_w4a8`` on its row and expert. Shapes the expert-indexed GEMV does not
+    serve (odd K/32, more than 65535 slots, ...) raise."""
+    _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, a_rows, out)
     with torch.cuda.device(w.device):
         _lib.check(_lib.load().qg_gemm_w4a8_moe(_ptr(a), a_rows, _ptr(w), n_expert, _ptr(ids), ids_stride, _ptr(out), ldc,
                                                 T, n_used, N, K, wtype, _stream(w.device)), "gemm_w4a8_moe")
@@ -271,9 +295,7 @@ def gemm_w4a8_moe(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torc
 def moe_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_0) -> str:
     """The kernel ``gemm_w4a8_moe`` launches for this shape ("moe:<family> ..." with the family and the LPR / BPL /
     ONE(U) of ``debug_config(1, N, K, wtype)``); nothing is launched. Raises where the shape is not served."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_moe_config(T, n_used, N, K, wtype, buf, 256), "moe_config")
-    return buf.value.decode()
+    return _config("qg_moe_config", T, n_used, N, K, wtype)
 
 
 def moe_prefill_workspace_size(T: int, n_used: int, n_expert: int) -> int:
@@ -293,34 +315,8 @@ def gemm_w4a8_moe_prefill(activation_q: torch.Tensor, experts_q: torch.Tensor, i
     16-B aligned, its content arbitrary; allocated here when None. Calls on one stream may share one.
     The ids are never copied to the host: a captured graph follows the ids each replay finds."""
     _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the expert-grouped prefill takes Q4_K and Q6_K")
-    _require(K % 256 == 0, f"K must be divisible by 256, got {K}")
-    _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
-    _check_blocks(activation_q, "Activation", T * a_rows, K, 36)
-    _require(experts_q.is_cuda and experts_q.dtype == torch.uint8, "Experts must be a CUDA uint8 tensor")
-    per = N * (K // 256) * BLOCK_BYTES[wtype]
-    _require(per > 0 and experts_q.numel() % per == 0 and experts_q.numel() >= per,
-             f"Experts shape mismatch: {experts_q.numel()} bytes is no multiple of {per}")
-    n_expert = experts_q.numel() // per
-    _require(ids.is_cuda and ids.dtype == torch.int32 and ids.device == experts_q.device, "ids must be an int32 tensor on the experts' device")
-    _require(ids.dim() == 2 and tuple(ids.shape) == (T, n_used) and (n_used <= 1 or ids.stride(1) == 1),
-             "ids must be [T, n_used] with unit column stride")
-    ids_stride = ids.stride(0) if T > 1 else n_used
-    _require(ids_stride >= n_used, "ids row stride below n_used")
-    a, w = activation_q.contiguous(), experts_q.contiguous()
-    if out is None:
-        out = torch.empty((T, n_used, N), dtype=torch.float32, device=w.device)
-    else:
-        _require(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, n_used, N), "bad out tensor")
-        _require(out.device == w.device, "out must be on the experts' device")
-        _require(N <= 1 or out.stride(2) == 1, "bad out tensor: rows must be dense")
-    ldc = out.stride(1) if n_used > 1 else out.stride(0) if T > 1 else N
-    _require(ldc >= N and (T <= 1 or n_used <= 1 or out.stride(0) == n_used * ldc), "bad out tensor: slots must be evenly spaced")
-    if workspace is None:
-        workspace = torch.empty(max(moe_prefill_workspace_size(T, n_used, n_expert), 16), dtype=torch.uint8, device=w.device)
-    else:
-        _require(workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
-                 "workspace must be a contiguous CUDA uint8 tensor")
-        _require(workspace.device == w.device, "workspace must be on the experts' device")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, a_rows, out)
+    workspace = _moe_workspace(workspace, moe_prefill_workspace_size(T, n_used, n_expert), w.device)
     with torch.cuda.device(w.device):
         _lib.check(_lib.load().qg_gemm_w4a8_moe_prefill(_ptr(a), a_rows, _ptr(w), n_expert, _ptr(ids), ids_stride, _ptr(out),
                                                         ldc, T, n_used, N, K, wtype, _ptr(workspace), workspace.numel(),
@@ -331,9 +327,7 @@ def gemm_w4a8_moe_prefill(activation_q: torch.Tensor, experts_q: torch.Tensor, i
 def moe_prefill_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = Q4_K) -> str:
     """The launch ``gemm_w4a8_moe_prefill`` makes for this shape ("moe:q4k_mmq TT=.. RG=.. KS=.. R=.. grid=XxY", Y the
     host's upper bound on the tiles); nothing is launched. Raises where the shape is not served."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_moe_prefill_config(T, n_used, n_expert, N, K, wtype, buf, 256), "moe_prefill_config")
-    return buf.value.decode()
+    return _config("qg_moe_prefill_config", T, n_used, n_expert, N, K, wtype)
 
 
 def debug_moe_prefill_plan(ids: torch.Tensor, n_expert: int, N: int, K: int, wtype: int = Q4_K, a_rows: int = 1,
@@ -372,34 +366,8 @@ def gemm_w4a8_moe_batch(activation_q: torch.Tensor, experts_q: torch.Tensor, ids
     16-B aligned, its content arbitrary; allocated here when None. Calls on one stream may share one.
     The ids are never copied to the host: a captured graph follows the ids each replay finds."""
     _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the expert-grouped decode GEMV takes Q4_K and Q6_K")
-    _require(K % 256 == 0, f"K must be divisible by 256, got {K}")
-    _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
-    _check_blocks(activation_q, "Activation", T * a_rows, K, 36)
-    _require(experts_q.is_cuda and experts_q.dtype == torch.uint8, "Experts must be a CUDA uint8 tensor")
-    per = N * (K // 256) * BLOCK_BYTES[wtype]
-    _require(per > 0 and experts_q.numel() % per == 0 and experts_q.numel() >= per,
-             f"Experts shape mismatch: {experts_q.numel()} bytes is no multiple of {per}")
-    n_expert = experts_q.numel() // per
-    _require(ids.is_cuda and ids.dtype == torch.int32 and ids.device == experts_q.device, "ids must be an int32 tensor on the experts' device")
-    _require(ids.dim() == 2 and tuple(ids.shape) == (T, n_used) and (n_used <= 1 or ids.stride(1) == 1),
-             "ids must be [T, n_used] with unit column stride")
-    ids_stride = ids.stride(0) if T > 1 else n_used
-    _require(ids_stride >= n_used, "ids row stride below n_used")
-    a, w = activation_q.contiguous(), experts_q.contiguous()
-    if out is None:
-        out = torch.empty((T, n_used, N), dtype=torch.float32, device=w.device)
-    else:
-        _require(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, n_used, N), "bad out tensor")
-        _require(out.device == w.device, "out must be on the experts' device")
-        _require(N <= 1 or out.stride(2) == 1, "bad out tensor: rows must be dense")
-    ldc = out.stride(1) if n_used > 1 else out.stride(0) if T > 1 else N
-    _require(ldc >= N and (T <= 1 or n_used <= 1 or out.stride(0) == n_used * ldc), "bad out tensor: slots must be evenly spaced")
-    if workspace is None:
-        workspace = torch.empty(max(moe_batch_workspace_size(T, n_used, n_expert), 16), dtype=torch.uint8, device=w.device)
-    else:
-        _require(workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
-                 "workspace must be a contiguous CUDA uint8 tensor")
-        _require(workspace.device == w.device, "workspace must be on the experts' device")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, a_rows, out)
+    workspace = _moe_workspace(workspace, moe_batch_workspace_size(T, n_used, n_expert), w.device)
     with torch.cuda.device(w.device):
         _lib.check(_lib.load().qg_gemm_w4a8_moe_batch(_ptr(a), a_rows, _ptr(w), n_expert, _ptr(ids), ids_stride, _ptr(out),
                                                       ldc, T, n_used, N, K, wtype, _ptr(workspace), workspace.numel(),
@@ -410,9 +378,7 @@ def gemm_w4a8_moe_batch(activation_q: torch.Tensor, experts_q: torch.Tensor, ids
 def moe_batch_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = Q4_K) -> str:
     """The launch ``gemm_w4a8_moe_batch`` makes for this shape ("moeb:q4k_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=..",
     R the rows per tile, Y the host's upper bound on the tiles); nothing is launched. Raises where the shape is not served."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_moe_batch_config(T, n_used, n_expert, N, K, wtype, buf, 256), "moe_batch_config")
-    return buf.value.decode()
+    return _config("qg_moe_batch_config", T, n_used, n_expert, N, K, wtype)
 
 
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
@@ -717,9 +683,7 @@ def debug_sumi(activation_q: torch.Tensor, weight_q: torch.Tensor, M: int, N: in
 def debug_config(M: int, N: int, K: int, wtype: int = Q4_0, algo: int = ALGO_AUTO, sumi: bool = False) -> str:
     """The kernel instantiation ``gemm_w4a8`` (or ``debug_sumi`` with sumi=True) launches for this
     shape on aligned buffers (family, template parameters, grid); nothing is launched."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_debug_config(M, N, K, wtype, algo, int(sumi), buf, 256), "debug_config")
-    return buf.value.decode()
+    return _config("qg_debug_config", M, N, K, wtype, algo, int(sumi))
 
 
 def debug_sumi_tiled(activation_q: torch.Tensor, weight_tiled: torch.Tensor, M: int, N: int, K: int,
@@ -751,16 +715,12 @@ def debug_sumi_tiled_act(activation_tiled: torch.Tensor, weight_tiled: torch.Ten
 
 def debug_config_tiled_act(M: int, N: int, K: int, wtype: int = Q4_0, sumi: bool = False) -> str:
     """The instantiation gemm_w4a8_tiled_act (or debug_sumi_tiled_act) launches; nothing runs."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_debug_config_tiled_act(M, N, K, wtype, int(sumi), buf, 256), "debug_config_tiled_act")
-    return buf.value.decode()
+    return _config("qg_debug_config_tiled_act", M, N, K, wtype, int(sumi))
 
 
 def debug_config_tiled(M: int, N: int, K: int, wtype: int = Q4_0, sumi: bool = False) -> str:
     """The instantiation gemm_w4a8_tiled (or debug_sumi_tiled with sumi=True) launches; nothing runs."""
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().qg_debug_config_tiled(M, N, K, wtype, int(sumi), buf, 256), "debug_config_tiled")
-    return buf.value.decode()
+    return _config("qg_debug_config_tiled", M, N, K, wtype, int(sumi))
 
 
 def select_algo(M: int, N: int, K: int, wtype: int = Q4_0) -> int:

@@ -65,12 +65,22 @@ def gemm_fp32_from_ggml(act: TensorView, w: TensorView, out: TensorView, kernel_
     _call("qg_gemm_fp32_from_view", act, w, out, kernel_type)
 
 
+def _mul_mat_id(sym: str, experts: TensorView, act: TensorView, ids: TensorView, out: TensorView,
+                workspace: torch.Tensor | None = None) -> None:
+    ws = ()
+    if workspace is not None:
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
+        ws = (ctypes.c_void_p(workspace.data_ptr()), workspace.numel())
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(getattr(_lib.load(), sym)(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids), ctypes.byref(out),
+                                         *ws, st), sym)
+
+
 def mul_mat_id_from_ggml(experts: TensorView, act: TensorView, ids: TensorView, out: TensorView) -> None:
     """ggml_mul_mat_id on views (qg_mul_mat_id_from_view): experts [K, N, n_expert], Q8_1 act [K, a_rows, T], I32
     ids [n_used, T] on the device (a strided top-k view is fine), F32 out [N, n_used, T]."""
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(_lib.load().qg_mul_mat_id_from_view(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
-                                                   ctypes.byref(out), st), "qg_mul_mat_id_from_view")
+    _mul_mat_id("qg_mul_mat_id_from_view", experts, act, ids, out)
 
 
 def mul_mat_id_from_ggml_ws(experts: TensorView, act: TensorView, ids: TensorView, out: TensorView,
@@ -78,12 +88,7 @@ def mul_mat_id_from_ggml_ws(experts: TensorView, act: TensorView, ids: TensorVie
     """The same views through the expert-grouped MFMA prefill (qg_mul_mat_id_from_view_ws): Q4_K / Q6_K experts at
     prompt sizes. ``workspace``: a CUDA uint8 tensor of quant_gemm.moe_prefill_workspace_size(T, n_used, n_expert)
     bytes or more."""
-    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(_lib.load().qg_mul_mat_id_from_view_ws(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
-                                                      ctypes.byref(out), ctypes.c_void_p(workspace.data_ptr()),
-                                                      workspace.numel(), st), "qg_mul_mat_id_from_view_ws")
+    _mul_mat_id("qg_mul_mat_id_from_view_ws", experts, act, ids, out, workspace)
 
 
 def mul_mat_id_from_ggml_batch(experts: TensorView, act: TensorView, ids: TensorView, out: TensorView,
@@ -91,12 +96,7 @@ def mul_mat_id_from_ggml_batch(experts: TensorView, act: TensorView, ids: Tensor
     """The same views through the expert-grouped decode GEMV (qg_mul_mat_id_from_view_batch): Q4_K / Q6_K experts for
     batched decode. ``workspace``: a CUDA uint8 tensor of quant_gemm.moe_batch_workspace_size(T, n_used, n_expert)
     bytes or more."""
-    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(_lib.load().qg_mul_mat_id_from_view_batch(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
-                                                         ctypes.byref(out), ctypes.c_void_p(workspace.data_ptr()),
-                                                         workspace.numel(), st), "qg_mul_mat_id_from_view_batch")
+    _mul_mat_id("qg_mul_mat_id_from_view_batch", experts, act, ids, out, workspace)
 
 
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:

@@ -3,16 +3,17 @@
 
     python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe and qg_moe_prefill by their name and integer / bool template
-arguments, and compares the instruction text from each kernel's label to its end (symbol names, labels' function
-numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file and every pair
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch and qg_moe_plan by their name and
+integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
+does not have is skipped there), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
+numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file of the result and every pair
 that differs: REGS where the instruction sequence and the remarks are the parent's and only register numbers moved,
 DIFF otherwise. Exit status 1 if any pair differs."""
 import re
 import sys
 from pathlib import Path
 
-FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill"]
+FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_plan"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
@@ -66,25 +67,33 @@ def resources(txt):
 
 
 def main(parent, result):
+    side = []
+    for d in (Path(parent), Path(result)):
+        side.append({})
+        for f in FILES:
+            asm = d / f"{f}-hip-amdgcn-amd-amdhsa-gfx950.s"
+            if not asm.exists():
+                continue
+            k, r = kernels(asm), resources(d / f"{f}.hip.resource.txt")
+            for s in k:
+                assert key(s) not in side[-1], (f, s, "two kernels with one key")
+                side[-1][key(s)] = (f, s, k[s], r[s])
+    assert side[0].keys() == side[1].keys(), sorted(side[0].keys() ^ side[1].keys())
     bad = 0
     for f in FILES:
-        side = []
-        for d in (Path(parent), Path(result)):
-            k = kernels(d / f"{f}-hip-amdgcn-amd-amdhsa-gfx950.s")
-            r = resources(d / f"{f}.hip.resource.txt")
-            side.append({key(s): (s, k[s], r[s]) for s in k})
-            assert len(side[-1]) == len(k), (f, "two kernels with one key")
-        assert side[0].keys() == side[1].keys(), (f, sorted(side[0].keys() ^ side[1].keys()))
+        keys = sorted(kk for kk in side[1] if side[1][kk][0] == f)
         same = 0
-        for kk in sorted(side[0]):
-            (sa, ia, ra), (sb, ib, rb) = side[0][kk], side[1][kk]
+        for kk in keys:
+            (fa, sa, ia, ra), (fb, sb, ib, rb) = side[0][kk], side[1][kk]
+            if fa != fb:
+                print(f"  MOVED {sb}: {fa} -> {fb}")
             if ia == ib and ra == rb:
                 same += 1
                 continue
             bad += 1
             tag = "REGS" if ra == rb and masked(ia) == masked(ib) else "DIFF"
             print(f"  {tag} {sb}\n    parent {len(ia)} instr {ra}\n    result {len(ib)} instr {rb}")
-        print(f"{f}: {len(side[0])} pairs, {same} identical")
+        print(f"{f}: {len(keys)} pairs, {same} identical")
     return 1 if bad else 0
 
 
