@@ -311,6 +311,24 @@ typedef struct {
 } qg_gemv_item;
 int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, qg_stream_t stream);
 
+/* Affine groups. A group of two or more items that share N and ldc and whose A, B and C pointers each advance
+ * by one constant byte stride from item to item (zero or negative strides included; the A stride a multiple
+ * of 4 bytes, the B stride of 16) is a strided batch, and is launched as qg_gemm_w4a8_strided_batched would
+ * launch it: same kernel body, same bits, no per-item descriptor in front of the weight stream. This holds
+ * for qg_gemm_w4a8_grouped and for the grouped nodes of the capture-time merge (a merged node follows the
+ * calls: the strided form while they keep the progression, the general grouped kernel from the first call
+ * that breaks it). mode: 0 off, 1 the shape classes measured faster (the default), 2 every class. The
+ * default is read once from the environment variable QG_GROUP_AFFINE (0, 1 or 2). */
+void qg_set_group_affine(int mode);
+
+/* The route qg_gemm_w4a8_grouped(items, count, M, K, wtype) would take for its first launch, written to buf
+ * (NUL-terminated, truncated to len) like qg_debug_config; nothing is enqueued and no pointer is
+ * dereferenced. "gemvg ..." the grouped kernel, "gemvb ..." the strided batch's kernel (an affine group),
+ * each with its template parameters and grid; "items: ..." when the items are enqueued one by one; "none"
+ * when there is nothing to launch. Returns what qg_gemm_w4a8_grouped would return for the same arguments
+ * before launching. */
+int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtype, char* buf, size_t len);
+
 /* ---- expert-indexed decode GEMV: ggml_mul_mat_id for a decode step, ids read on the device ----
  * Slot s = t * n_used + u (t < T, u < n_used):
  *   e = ids[t * ids_stride + u]

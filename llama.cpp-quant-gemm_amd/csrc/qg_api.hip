@@ -830,13 +830,15 @@ int qg_debug_config_tiled_act(int M, int N, int K, int wtype, int sumi, char* bu
     return describe_product(LAY_TILED_ACT, M, N, K, wtype, QG_ALGO_AUTO, sumi, buf, len);
 }
 
-int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, qg_stream_t stream) {
+// qg_gemm_w4a8_grouped and qg_group_config: the items are validated alike, then launched or described
+// (describe != nullptr: the route of the first launch is written there and nothing is enqueued).
+static int run_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, hipStream_t st, char* describe,
+                       size_t describe_len) {
     // by hand: the items pointer is checked with the sizes, and M == 0 is a no-op only after every item's sizes
     // and pointers have been checked (below)
     if (count < 0 || M < 0 || (count > 0 && !items)) return QG_ERR_INVALID_ARG;
     if (K <= 0 || K % 32 != 0) return QG_ERR_BAD_K;
     if (!is_weight_type(wtype)) return QG_ERR_UNSUPPORTED;
-    const hipStream_t st = (hipStream_t)stream;
     auto item_args = [&](const qg_gemv_item& it) {
         GemmArgs g = product_args(it.A_q8_1, it.B, it.C, M, it.N, K, wtype);
         if (it.ldc) g.ldc_m = it.ldc;
@@ -853,8 +855,15 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
         const GemmArgs g = item_args(it);
         one_launch = one_launch && select_algo(g) == QG_ALGO_GEMV && gemv_eligible(g);
     }
-    if (M == 0) return QG_OK;
+    if (M == 0) {
+        describe_line(describe, describe_len, "%s", "none");
+        return QG_OK;
+    }
     if (!one_launch) {
+        if (describe) {
+            describe_line(describe, describe_len, "%s", "items: one qg_gemm_w4a8 launch per item");
+            return QG_OK;
+        }
         for (int i = 0; i < count; ++i) {
             if (items[i].N == 0) continue;
             GemmArgs g = item_args(items[i]);
@@ -863,6 +872,7 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
         }
         return QG_OK;
     }
+    describe_line(describe, describe_len, "%s", "none");
     for (int i0 = 0; i0 < count;) {
         GemvGroup grp = {};
         grp.M = M; grp.K = K;
@@ -872,11 +882,26 @@ int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int
             grp.it[grp.count++] = GemvItemDesc{it.A_q8_1, it.B, it.C, it.N, it.ldc ? it.ldc : it.N};
         }
         if (grp.count == 0) break;
-        const int rc = hip_status(launch_gemv(group_args(grp, wtype), st));
-        if (rc != QG_OK) return rc;
+        GemmArgs q = group_args(grp, wtype);
+        q.describe = describe;
+        q.describe_len = describe_len;
+        const int rc = hip_status(launch_gemv(q, st));
+        if (rc != QG_OK || describe) return rc;
     }
     return QG_OK;
 }
+
+int qg_gemm_w4a8_grouped(const qg_gemv_item* items, int count, int M, int K, int wtype, qg_stream_t stream) {
+    return run_grouped(items, count, M, K, wtype, (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    return run_grouped(items, count, M, K, wtype, nullptr, buf, len);
+}
+
+void qg_set_group_affine(int mode) { set_group_affine(mode); }
 
 int qg_gemm_w4a8(const void* A, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream) {
     return qg_gemm_w4a8_ex(A, B, C, M, N, K, wtype, QG_ALGO_AUTO, stream);

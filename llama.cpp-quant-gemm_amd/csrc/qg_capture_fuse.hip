@@ -43,6 +43,7 @@ struct FuseRecord {
     int wtype = 0;
     GemvGroup grp = {};
     fuse::Group spans;
+    bool no_affine = false;  // the node refused the strided batch's kernel once: grouped from then on
 };
 thread_local FuseRecord t_fuse;
 
@@ -101,10 +102,24 @@ hipError_t capture_gemv(const GemmArgs& g, hipStream_t st) {
         GemvNodeFill nf;
         GemmArgs q = group_args(grp, g.wtype);
         q.node_fill = &nf;
+        if (r.no_affine) q.affine = -1;
         nf.p = hipKernelNodeParams{};
         hipError_t e = launch_gemv(q, st);  // launches nothing: the grouped launch's kernel, grid, block, LDS
         if (e == hipSuccess && !(nf.p.func && fuse_class_enabled(nf, g.M, mode))) e = hipErrorNotSupported;
-        if (e == hipSuccess) e = hipGraphKernelNodeSetParams(r.node, &nf.p);
+        if (e == hipSuccess) {
+            e = hipGraphKernelNodeSetParams(r.node, &nf.p);
+            // The runtime refuses some changes of a node's kernel (seen: hipErrorLaunchFailure for the strided
+            // batch's 512-thread kernel on a node that held a 256-thread gemvg_kernel, Q5_0 / Q5_1 at N = 4096).
+            // The node is unchanged then: it takes the grouped kernel, for this call and the node's later ones.
+            if (e != hipSuccess && nf.affine) {
+                (void)hipGetLastError();
+                r.no_affine = true;
+                q.affine = -1;
+                e = launch_gemv(q, st);
+                if (e == hipSuccess && !nf.p.func) e = hipErrorNotSupported;
+                if (e == hipSuccess) e = hipGraphKernelNodeSetParams(r.node, &nf.p);
+            }
+        }
         if (e == hipSuccess) {
             r.grp = grp;
             fuse::join(r.spans, sp);
@@ -123,6 +138,7 @@ hipError_t capture_gemv(const GemmArgs& g, hipStream_t st) {
         r.id = id;
         r.node = deps[0];
         r.wtype = g.wtype;
+        r.no_affine = false;
         r.grp = GemvGroup{};
         r.grp.count = 1; r.grp.M = g.M; r.grp.K = g.K;
         r.grp.it[0] = GemvItemDesc{g.A, g.B, g.C, g.N, (int)g.ldc_m};

@@ -42,7 +42,10 @@
 //  * NT: the weight stream is loaded with the nontemporal hint (read once per launch).
 // Tuning record (probes, per-wave timelines, rejected designs): profiles/r01_tuning/README.md.
 #pragma once
+#include <assert.h>
+
 #include "qg_common.hpp"
+#include "qg_group_affine.hpp"
 #include "qg_kernels.hpp"
 #include "qg_quant_block.hpp"
 
@@ -50,6 +53,9 @@ namespace qg {
 
 constexpr uint32_t ACC_BIAS = 0x4B400000u;  // bits of 12582912.0f = 1.5 * 2^23
 constexpr float ACC_BIAS_F = 12582912.0f;
+
+// row tiles of a launch: N rows at rpw rows per workgroup (host: grid.x; device: the XCD-order test)
+__host__ __device__ constexpr int gemv_tiles(int N, int rpw) { return (int)(((unsigned)N + (unsigned)rpw - 1u) / (unsigned)rpw); }
 
 template <int F, int BPL> struct gemv_geom {
     static constexpr int BB = wfmt<F>::BB;
@@ -267,6 +273,12 @@ template <int AIN> __device__ __forceinline__ void load_act_block(const uint8_t*
 
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x8_a16 __attribute__((ext_vector_type(8), aligned(16)));
+// a device-memory pointer from its two dwords
+template <class T> __device__ __forceinline__ T* global_ptr(uint32_t lo, uint32_t hi) {
+    typedef T __attribute__((address_space(1))) * G;
+    return (T*)(G)((uint64_t)lo | (uint64_t)hi << 32);
+}
 
 // PRE: read the unit's LDS records into registers right after the staging barrier, before the
 // first weight byte is used, so the LDS latency overlaps the weight stream and only VALU work
@@ -326,7 +338,11 @@ __device__ __forceinline__ void gemv_body(const uint32_t* __restrict__ A, const 
     // profiles/r02_tuning/ab_xcd.txt: M=1 3.33 -> 3.29 us, M=2 3.66 -> 3.58). Larger grids keep
     // the linear order (N=32000: 12.55 us linear, 13.28 remapped).
     // (a grouped launch passes the workgroup's tile within its item, tile_in >= 0)
-    const int tile = tile_in >= 0 ? tile_in : gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    // The grid's tile count is derived from N, which is preloaded, not read from gridDim.x: in the strided
+    // batch that hidden argument lies past the preloaded dwords and cost a scalar-memory round trip ahead
+    // of the first load. gemv_launch asserts grid.x == gemv_tiles(N, rows per workgroup) at every launch.
+    const int ntile = gemv_tiles(N, RPB * TPW);
+    const int tile = tile_in >= 0 ? tile_in : ntile <= 512 ? xcd_tile(blockIdx.x, ntile) : (int)blockIdx.x;
     int rows[TPW];
     bool rows_ok[TPW];
     const uint8_t* wrows[TPW];
@@ -540,7 +556,7 @@ __global__ __launch_bounds__(WGS) void gemv1_kernel(const uint32_t* __restrict__
 
 // Grouped GEMV (qg_gemm_w4a8_grouped): up to GEMV_GROUP_MAX independent products with their own A,
 // B, C and N (and output row stride), one M and K, in ONE launch — e.g. a decoder layer's Q / K / V
-// or gate / up projections. The descriptor travels by value in the kernel arguments (GemvGroup in
+// or gate / up projections. The item table travels by value in the kernel arguments (GemvItems in
 // qg_kernels.hpp: no device allocation, capture-safe); blockIdx.y is the item, blockIdx.x its row
 // tile, and workgroups past an item's rows exit at once (grid.x = the largest item's tiles). The
 // item's pointers are ONE scalar load (32-B record); the outputs are bit-identical to the single
@@ -576,18 +592,32 @@ __global__ __launch_bounds__(WGS) void gemv1_kernel(const uint32_t* __restrict__
 #ifndef QG_GEMVG_WDIV
 #define QG_GEMVG_WDIV 2  // grouped launch workgroup size = the single launch's / QG_GEMVG_WDIV (below)
 #endif
+// The front end: M, K, the flags (GEMVG_FULL, GEMVG_XCD) and the launch's tile count (= grid.x) are leading
+// scalars, preloaded into SGPRs by the dispatch, and the item's 32-B record is the kernel's first
+// instruction, so ONE scalar-memory round trip precedes the first vector load. (With the whole GemvGroup as
+// the only argument nothing was preloaded and three dependent round trips did: the hidden gridDim.x for the
+// tile order, then full and N for the early exit, then the pointers with M and K —
+// profiles/group_front/README.md.)
 template <int F, int MT, int BPL, int LPR, int WGS, bool PRE, int ONEU, int TPW = 1>
-__global__ __launch_bounds__(WGS) void gemvg_kernel(const GemvGroup grp) {
+__global__ __launch_bounds__(WGS) void gemvg_kernel(int M, int K, int flags, int tiles, const GemvItems items) {
     constexpr int RPB = (WGS / 64) * (64 / LPR) * TPW;  // rows per workgroup
-    const int item = blockIdx.y;
+    // the record as ONE 8-dword load (field by field, the compiler fetched N for the early exit first and
+    // the pointers in a second round trip behind the branch)
+    static_assert(sizeof(GemvItemDesc) == 32 && offsetof(GemvItemDesc, N) == 24 && offsetof(GemvItemDesc, ldc) == 28, "");
+    const u32x8_a16 r = *reinterpret_cast<const u32x8_a16*>(&items.it[blockIdx.y]);
+    GemvItemDesc d;  // (pointers rebuilt in the global address space: from a plain integer they would be flat)
+    d.A = global_ptr<const void>(r[0], r[1]);
+    d.B = global_ptr<const void>(r[2], r[3]);
+    d.C = global_ptr<float>(r[4], r[5]);
+    d.N = (int)r[6];
+    d.ldc = (int)r[7];
     // the single launch's XCD-aware tile order (gemv_body) within the item: with grid.x a multiple of 8 the
     // workgroup's XCD is blockIdx.x % 8, so each XCD takes a contiguous range of its tiles
-    const int tile = gridDim.x <= 512 ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const GemvItemDesc d = grp.it[item];
-    if (!grp.full && tile * RPB >= d.N) return;  // past this item's rows (uniform)
+    const int tile = (flags & GEMVG_XCD) ? xcd_tile(blockIdx.x, tiles) : (int)blockIdx.x;
+    if (!(flags & GEMVG_FULL) && tile * RPB >= d.N) return;  // past this item's rows (uniform)
     gemv_body<F, MT, BPL, LPR, WGS, false, AIN_Q8_1, false, PRE, ONEU, TPW>(
-        reinterpret_cast<const uint32_t*>(d.A), reinterpret_cast<const uint8_t*>(d.B), 0, 0, grp.M, d.N, grp.K,
-        d.C, 0, d.ldc, 1, nullptr, tile);
+        reinterpret_cast<const uint32_t*>(d.A), reinterpret_cast<const uint8_t*>(d.B), 0, 0, M, d.N, K,
+        d.C, 0, d.ldc, 1, nullptr, tile & INT32_MAX);  // (the mask: known >= 0, so the body's own tile order folds away)
 }
 
 // Loop-free multi-unit single launches (ONEU = 2 / 4, above): 1 = on, 0 = the unit loop (A/B builds).
@@ -618,11 +648,40 @@ inline bool gemv_shape_ok(const GemmArgs& g) {
     return true;
 }
 
+// Shape classes whose affine groups take the strided batch's kernel (group_affine_mode() == 1; 2: every class),
+// by measurement: tools/ab_group_front.py (64 products per step on distinct weight copies in grouped launches
+// of `count` items, mode 0 vs mode 2 in one process, interleaved rounds of 100 replays after one uncounted;
+// us per GEMV, grouped -> affine), profiles/group_front/ab_group_front*.txt. Enabled where affine beats grouped
+// by more than the grouped arm's run-to-run spread (0.1 .. 0.9 % of its median; 2 - 3 % at K <= 2048):
+//  * the loop-free one-unit form at M = 1, items of at most 16 rows per compute unit (small_n: N <= 4096 on a
+//    whole MI355X, what was measured), 8 items or more. N = K = 4096 x 64: Q4_0 1.515 -> 1.475, Q4_1 1.676 -> 1.662, Q5_0 1.831
+//    -> 1.798, Q5_1 2.009 -> 1.971, Q8_0 2.760 -> 2.751; x 32: Q4_0 1.533 -> 1.489, Q5_1 2.023 -> 1.995; x 16:
+//    Q4_0 1.595 -> 1.565, Q8_0 2.896 -> 2.830; x 8: Q4_0 1.765 -> 1.715, Q4_1 1.942 -> 1.872, Q8_0 3.099 ->
+//    2.964. N = 1024 x 64 0.424 -> 0.420, N = 2048 x 16 0.922 -> 0.876, K = 256 x 64 0.195 -> 0.183, K = 2048
+//    x 8 1.033 -> 1.019, Q8_0 K = 2048 x 64 1.454 -> 1.440. One point of the class is a tie: Q4_0 K = 2048 x
+//    64, 0.747 -> 0.741 inside a 2.9 % spread. (The strided kernel takes ONE row tile per workgroup where the
+//    grouped one takes two, so its grid has twice the workgroups.)
+// Not enabled:
+//  * fewer than 8 items of that class: the sign follows how the two grids fill the last dispatch round (Q4_0
+//    N = K = 4096 x 2 1.020x, x 3 0.971x, x 4 1.006x, x 5 1.003x, x 6 1.020x; Q8_0 x 3 1.050x);
+//  * M >= 2 in the one-unit form (both kernels: 256 threads, two tiles): Q4_0 N = K = 4096 x 64 M = 2 0.992x,
+//    M = 4 1.000x, x 8 M = 2 0.982x, x 3 0.983x; Q8_0 M = 2 1.019x;
+//  * larger items: N = 14336 x 2 1.065x (M = 2 1.177x, M = 4 1.032x, Q8_0 1.150x), x 8
+//    1.049x, N = 11008 x 2 1.065x, N = 32000 x 2 1.029x, but N = 8192 x 2 0.972x, N = 14336 x 64 0.989x, N =
+//    32000 x 64 0.996x — mixed, so the class stays off;
+//  * the unit loop: M = 1 ties (K = 8192 0.998x, K = 14336 1.006x, Q8_0 1.000x). M >= 2 gains where the grouped
+//    kernel runs its 256-thread workgroups, Q4_0 only (N = 4096 x 64: K = 8192 M = 2 1.063x, M = 4 2.076x, K =
+//    11008 M = 2 1.259x, K = 14336 M = 2 1.460x, M = 3 2.264x, M = 4 2.906x; Q8_0 M = 2 1.000x, Q5_1 M = 4 1.003x,
+//    N = 8192 0.993x): left off here, with the merge's own gate for that class (fuse_class_enabled).
+inline bool group_affine_class_enabled(bool one, int MT, bool small_n, int count, int mode) {
+    if (mode == 2) return true;
+    return one && MT == 1 && small_n && count >= 8;
+}
+
 template <int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN = AIN_Q8_1, bool NT = false, bool PRE = (MT <= 2)>
 hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
     constexpr int RPB = (WGS / 64) * (64 / LPR);
     const size_t lds = gemv_lds_bytes<F, BPL>(g.M, g.K);
-    const int grid = (g.N + RPB - 1) / RPB;
     const bool one = g.K / QK / BPL <= LPR;
     // units per lane of the loop-free multi-unit form: Q4_0 M = 1 single launches only (0: the unit loop).
     // profiles/r05_tuning/r5zd_ab.txt, unit loop -> multi-unit: Q4_0 M = 1 K = 14336 7.69 -> 7.46 us, K = 11008
@@ -638,7 +697,27 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
     // NU_OK && MT > 1, otherwise its loop (ONEU 0) or the one-unit form
     const int oneu = m1 ? nu : shrt ? ((nu > 1 && !(NU_OK && MT > 1)) ? 0 : nu) : (int)one;
     if (g.group && (SUMI || AIN != AIN_Q8_1 || NT || MT > 4)) return hipErrorInvalidValue;  // no grouped form here
-    if (g.describe) {  // qg_debug_config: name the instantiation instead of launching it
+    // the kernel derives its tile count from N (gemv_body): the grid must be exactly that
+    auto grid_x = [&](int rpw) {
+        const int gx = (g.N + rpw - 1) / rpw;
+        assert(gx == gemv_tiles(g.N, rpw));
+        return gx;
+    };
+    const int grid = grid_x(RPB);
+    // the strided batch standing for an affine group (below): the launch as a graph node's parameters
+    auto fill_batch = [&](const void* fn, dim3 grd, int block) {
+        GemvNodeFill* nf = g.node_fill;
+        nf->p = hipKernelNodeParams{};
+        nf->set_batch(g);
+        nf->one = one ? 1 : 0;
+        nf->p.func = const_cast<void*>(fn);
+        nf->p.gridDim = grd;
+        nf->p.blockDim = dim3(block);
+        nf->p.sharedMemBytes = (unsigned)lds;
+        nf->p.kernelParams = nf->argv;
+        return hipSuccess;
+    };
+    if (g.describe && !g.group && !g.affine) {  // qg_debug_config: name the instantiation instead of launching it
         describe_kernel(g, "gemv F=%d MT=%d BPL=%d LPR=%d WGS=%d AIN=%d NT=%d PRE=%d ONEU=%d SIG=%s grid=%dx%d", F, MT, BPL,
                         LPR, WGS, AIN, (int)NT, (int)(one ? PRE : (PRE && MT <= (shrt && !oneu ? gemv_pre_mt<F> : 2))), oneu,
                         m1 ? "m1" : shrt ? "short" : "full",
@@ -648,16 +727,38 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
     if constexpr (!SUMI && AIN == AIN_Q8_1 && !NT && MT <= 4) {  // (AUTO sends only M <= 4 to the GEMV)
         if (g.group) {  // grouped launch (qg_gemm_w4a8_grouped): blockIdx.y = item
             const GemvGroup& grp0 = *static_cast<const GemvGroup*>(g.group);
+            // An affine group (qg_group_affine.hpp) is a strided batch: it takes the kernel and grid
+            // qg_gemm_w4a8_strided_batched launches for the same items (below), whose arguments all sit in
+            // SGPRs — no descriptor load ahead of the weight stream. Same body, same bits.
+            affine::Strides as;
+            const int amode = group_affine_mode();
+            if (amode && g.affine >= 0 && grp0.count >= 2 && group_affine_class_enabled(one, MT, g.N <= 16 * device_cus(), grp0.count, amode) &&
+                affine::group_affine(grp0.it, grp0.count, 3, 15, &as)) {
+                GemmArgs b = g;
+                b.group = nullptr;
+                b.affine = 1;
+                b.A = grp0.it[0].A; b.B = grp0.it[0].B; b.C = grp0.it[0].C;
+                b.N = grp0.it[0].N; b.ldc_m = grp0.it[0].ldc; b.ldc_n = 1;
+                b.batch = grp0.count;
+                b.sA = (long)as.a; b.sB = (long)as.b; b.sC = (long)(as.c / 4);
+                return gemv_launch<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE>(b, st);
+            }
             auto go = [&](auto GWc, auto TPc) -> hipError_t {
                 constexpr int GW = decltype(GWc)::value, TP = decltype(TPc)::value;
-                GemvGroup grp = grp0;
                 constexpr int RPBG = (GW / 64) * (64 / LPR);
                 const int rpw = one ? RPBG * TP : RPBG;  // rows per workgroup
                 int tiles = 0, tmin = INT32_MAX;
-                for (int i = 0; i < grp.count; ++i) {
-                    const int t = (grp.it[i].N + rpw - 1) / rpw;
+                for (int i = 0; i < grp0.count; ++i) {
+                    const int t = (grp0.it[i].N + rpw - 1) / rpw;
                     tiles = std::max(tiles, t);
                     tmin = std::min(tmin, t);
+                }
+                const int full = tiles == tmin ? 1 : 0;
+                if (g.describe) {  // qg_group_config: name the instantiation instead of launching it
+                    describe_kernel(g, "gemvg F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=%d TPW=%d full=%d grid=%dx%d", F, MT,
+                                    BPL, LPR, GW, (int)(one ? PRE : PRE && MT <= 2), (int)one, one ? TP : 1, full, tiles,
+                                    grp0.count);
+                    return hipSuccess;
                 }
                 auto kg = one ? gemvg_kernel<F, MT, BPL, LPR, GW, PRE, true, TP>
                               : gemvg_kernel<F, MT, BPL, LPR, GW, PRE && (MT <= 2), false>;
@@ -666,21 +767,26 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
                     if (e != hipSuccess) return e;
                 }
                 if (g.node_fill) g.node_fill->p = hipKernelNodeParams{};  // func == nullptr: nothing to launch
-                if (tiles == 0 || grp.count == 0) return hipSuccess;
-                grp.full = tiles == tmin ? 1 : 0;
-                if (GemvNodeFill* nf = g.node_fill) {  // capture-time merge: the same launch as a node's parameters
-                    nf->grp = grp;
-                    nf->argv[0] = &nf->grp;
-                    nf->one = one ? 1 : 0;
-                    nf->p.func = (void*)kg;
-                    nf->p.gridDim = dim3(tiles, grp.count);
-                    nf->p.blockDim = dim3(GW);
-                    nf->p.sharedMemBytes = (unsigned)lds;
-                    nf->p.kernelParams = nf->argv;
-                    return hipSuccess;
-                }
-                hipLaunchKernelGGL(kg, dim3(tiles, grp.count), dim3(GW), lds, st, grp);
-                return hipGetLastError();
+                if (tiles == 0 || grp0.count == 0) return hipSuccess;
+                // the launch as a graph node's parameters (the capture-time merge), or launched from them here
+                GemvNodeFill local;
+                GemvNodeFill* nf = g.node_fill ? g.node_fill : &local;
+                nf->p = hipKernelNodeParams{};
+                nf->grp = grp0;
+                nf->grp.full = full;
+                nf->flags = (full ? GEMVG_FULL : 0) | (tiles <= 512 ? GEMVG_XCD : 0);
+                nf->tiles = tiles;
+                nf->argv[0] = &nf->grp.M; nf->argv[1] = &nf->grp.K; nf->argv[2] = &nf->flags; nf->argv[3] = &nf->tiles;
+                nf->argv[4] = nf->grp.it;
+                nf->one = one ? 1 : 0;
+                nf->affine = 0;
+                nf->p.func = (void*)kg;
+                nf->p.gridDim = dim3(tiles, grp0.count);
+                nf->p.blockDim = dim3(GW);
+                nf->p.sharedMemBytes = (unsigned)lds;
+                nf->p.kernelParams = nf->argv;
+                if (g.node_fill) return hipSuccess;
+                return hipLaunchKernel(nf->p.func, nf->p.gridDim, nf->p.blockDim, nf->argv, lds, st);
             };
             // workgroups of WGS / QG_GEMVG_WDIV threads while the largest item's rows fit one round of
             // full-size workgroups (<= 256): twice as many resident per CU, so one workgroup's descriptor
@@ -747,18 +853,30 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
     if constexpr (GWB < WGS && GWB >= 64 && !SUMI && !NT) {
         constexpr int GW = GWB, RPBB = (GW / 64) * (64 / LPR) * TPB;
         if (one && g.batch > 1 && grid <= device_cus()) {
+            if (g.describe) {  // (an affine group: qg_group_config)
+                describe_kernel(g, "gemvb F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=1 TPW=%d grid=%dx%d", F, MT, BPL, LPR, GW,
+                                (int)PRE, TPB, grid_x(RPBB), g.batch);
+                return hipSuccess;
+            }
             auto kb = gemv_kernel<F, MT, BPL, LPR, GW, SUMI, AIN, NT, PRE, true, TPB>;
             if (lds > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(kb, dim3((g.N + RPBB - 1) / RPBB, g.batch), dim3(GW), lds, st, (const uint32_t*)g.A,
+            if (g.affine && g.node_fill) return fill_batch((const void*)kb, dim3(grid_x(RPBB), g.batch), GW);
+            hipLaunchKernelGGL(kb, dim3(grid_x(RPBB), g.batch), dim3(GW), lds, st, (const uint32_t*)g.A,
                                (const uint8_t*)g.B, g.sA, g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, g.sumi);
             return hipGetLastError();
         }
     }
     constexpr bool tpw_ok = !SUMI && !NT && QG_GEMV_TPW > 1;
     const bool multi = tpw_ok && one && g.batch > 1;
+    const int gx = multi ? grid_x(RPB * QG_GEMV_TPW) : grid;
+    if (g.describe) {  // (an affine group: qg_group_config)
+        describe_kernel(g, "gemvb F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=%d TPW=%d grid=%dx%d", F, MT, BPL, LPR, WGS,
+                        (int)(one ? PRE : PRE && MT <= 2), (int)one, multi ? QG_GEMV_TPW : 1, gx, g.batch);
+        return hipSuccess;
+    }
     auto kfn = multi ? gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE, true, tpw_ok ? QG_GEMV_TPW : 1>
              : one   ? gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE, true>
                      : gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE && (MT <= 2), false>;
@@ -766,7 +884,7 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
         hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const int gx = multi ? (g.N + RPB * QG_GEMV_TPW - 1) / (RPB * QG_GEMV_TPW) : grid;
+    if (g.affine && g.node_fill) return fill_batch((const void*)kfn, dim3(gx, g.batch), WGS);
     hipLaunchKernelGGL(kfn, dim3(gx, g.batch), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.sA,
                        g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, g.sumi);
     return hipGetLastError();

@@ -46,9 +46,13 @@ struct GemmArgs {
     size_t describe_len = 0;     // launch here (family + template parameters) and launches nothing
     struct GemvNodeFill* node_fill = nullptr;  // with `group`: the grouped launcher fills this (kernel, grid,
                                  // block, LDS, argument) and launches nothing — the capture-time merge
+    int affine = 0;              // 1, set by the grouped launcher: this strided batch stands for an affine group
+                                 // (qg_group_affine.hpp); it may fill node_fill, and describe names the batch kernel.
+                                 // -1, with `group`: keep the grouped kernel even for an affine group
 };
 
-// Descriptor of a grouped GEMV launch (qg_gemm_w4a8_grouped), passed by value as the kernel argument.
+// Host-side descriptor of a grouped GEMV launch (qg_gemm_w4a8_grouped). gemvg_kernel takes M, K, a flags word
+// and the launch's tile count as leading scalars (preloaded into SGPRs) and the item table `it` by value.
 constexpr int GEMV_GROUP_MAX = 64;
 struct GemvItemDesc {  // 32 B: one s_load_dwordx8 in the kernel
     const void* A;
@@ -56,11 +60,17 @@ struct GemvItemDesc {  // 32 B: one s_load_dwordx8 in the kernel
     float* C;
     int N, ldc;
 };
+struct GemvItems {  // the kernel's by-value item table: the bytes of GemvGroup::it
+    GemvItemDesc it[GEMV_GROUP_MAX];
+};
 struct GemvGroup {
     // full: every item has the launch's row-tile count (no workgroup exits early) — gemvg_kernel
     int count, M, K, full;
     GemvItemDesc it[GEMV_GROUP_MAX];
 };
+static_assert(sizeof(GemvItems) == sizeof(GemvGroup::it), "the kernel argument is read from GemvGroup::it");
+// gemvg_kernel's flags word
+enum : int { GEMVG_FULL = 1, GEMVG_XCD = 2 };  // no early exit; the XCD tile order (tiles <= 512)
 // The grouped launch's arguments (qg_gemm_w4a8_grouped and the capture-time merge): the first item's pointers,
 // N = the largest item's, `group` pointing at grp (which must outlive the launch call).
 inline GemmArgs group_args(const GemvGroup& grp, int wtype) {
@@ -75,10 +85,27 @@ inline GemmArgs group_args(const GemvGroup& grp, int wtype) {
 // node: the capture-time merge (qg_capture_fuse.hip) installs them with hipGraphKernelNodeSetParams.
 struct GemvNodeFill {
     hipKernelNodeParams p;  // p.func == nullptr: nothing to launch; p.kernelParams = argv
-    GemvGroup grp;          // the kernel's argument, `full` set for the launch's grid
-    void* argv[1];
+    GemvGroup grp;          // the group, `full` set for the launch's grid; gemvg_kernel's item table is grp.it
+    int flags, tiles;       // gemvg_kernel(M, K, flags, tiles, items): grp.M, grp.K, these, grp.it
+    // an affine group (qg_group_affine.hpp): gemv_kernel(A, B, sA, sB, M, N, K, C, sC, ldc_m, ldc_n, sumi)
+    struct Batch {
+        const uint32_t* A; const uint8_t* B; long sA, sB; int M, N, K; float* C; long sC, ldc_m, ldc_n; int32_t* sumi;
+    } sb;
+    void* argv[12];
     int one;                // the loop-free one-unit form (K/32 units fit the row's lanes)
+    int affine;             // the launch is the strided batch's kernel
+    // argv for gemv_kernel from the batch's GemmArgs
+    void set_batch(const GemmArgs& g) {
+        sb = Batch{(const uint32_t*)g.A, (const uint8_t*)g.B, g.sA, g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, nullptr};
+        void* a[12] = {&sb.A, &sb.B, &sb.sA, &sb.sB, &sb.M, &sb.N, &sb.K, &sb.C, &sb.sC, &sb.ldc_m, &sb.ldc_n, &sb.sumi};
+        for (int i = 0; i < 12; ++i) argv[i] = a[i];
+        affine = 1;
+    }
 };
+
+// The affine route of grouped launches (qg_set_group_affine): 0 off, 1 the measured classes, 2 every class.
+int group_affine_mode();
+void set_group_affine(int mode);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device): `done`
 // is that instantiation's atomic device bitmask (a process may drive several GPUs from

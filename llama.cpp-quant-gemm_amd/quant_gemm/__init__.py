@@ -733,6 +733,23 @@ def set_capture_fusion(on) -> None:
     _lib.load().qg_set_capture_fusion(int(on))
 
 
+def set_group_affine(mode) -> None:
+    """Affine grouped launches as the strided batch (qg.h at qg_set_group_affine): 0 off, 1 the measured
+    shape classes (default), 2 every class."""
+    _lib.load().qg_set_group_affine(int(mode))
+
+
+def group_config(items, M: int, K: int, wtype: int = Q4_0) -> str:
+    """The route gemm_w4a8_grouped would take for items = [(A_ptr, B_ptr, C_ptr, N, ldc), ...] (device addresses
+    as ints, ldc 0 = N): "gemvg ..." the grouped kernel, "gemvb ..." the strided batch's kernel (an affine
+    group). Nothing runs and no pointer is dereferenced (qg_group_config)."""
+    n = len(items)
+    arr = (_GemvItem * max(n, 1))(*[_GemvItem(*it) for it in items])
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().qg_group_config(arr, n, M, K, wtype, buf, len(buf)), "group_config")
+    return buf.value.decode()
+
+
 def capture_fusion_stats() -> "tuple[int, int]":
     """(merged, nodes): captured GEMV calls merged into an existing graph node, and GEMV nodes started."""
     merged, nodes = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -756,7 +773,7 @@ __all__ = [
     "tile_weights", "gemm_w4a8_tiled", "debug_sumi_tiled", "debug_config_tiled",
     "quantize_q8_1_tiled", "tile_activations", "gemm_w4a8_tiled_act", "debug_sumi_tiled_act", "debug_config_tiled_act",
     "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "Q6_K", "block_elems",
-    "set_capture_fusion", "capture_fusion_stats",
+    "set_capture_fusion", "capture_fusion_stats", "set_group_affine", "group_config",
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",

@@ -30,6 +30,8 @@ SIGNATURES = {
     "qg_debug_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_strided_batched": ([P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
     "qg_gemm_w4a8_grouped": ([P, I, I, I, I, P], I),
+    "qg_group_config": ([P, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_set_group_affine": ([I], None),
     "qg_gemm_w4a8_moe": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, P], I),
     "qg_moe_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_prefill_workspace_size": ([I, I, I], SZ),
