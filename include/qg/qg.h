@@ -364,6 +364,7 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  * Prefill-size T of Q4_K / Q6_K experts: qg_gemm_w4a8_moe_prefill below (this entry streams the slot's whole
  * expert matrix for every slot); slots of different tokens sharing one pass over an expert they both chose, at decode
  * sizes: qg_gemm_w4a8_moe_batch below.
+ * The gate and the up product of a Q4_K / Q6_K FFN block with their GLU in one launch: qg_gemm_w4a8_moe_glu below.
  * Not built: prefill-size T and shared passes for the five 32-element types, tiled-layout experts,
  * FP32 activations. */
 int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
@@ -474,6 +475,45 @@ int qg_gemm_w4a8_moe_batch(const void* A_q8_1, int a_rows, const void* B_experts
                            int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                            void* workspace, size_t workspace_bytes, qg_stream_t stream);
 int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- fused gate / up mul_mat_id with its GLU: the first half of an MoE FFN block in one launch ----
+ * down(act(gate(x)) * up(x)) starts with two mul_mat_id on the same ids, the same activation row and the same shape,
+ * and an elementwise GLU on their results. This entry replaces those three kernels (qg_gemm_w4a8_moe on the gate
+ * experts, qg_gemm_w4a8_moe on the up experts, the caller's activation kernel) for Q4_K / Q6_K experts.
+ * Slot s = t * n_used + u (t < T, u < n_used), e = ids[t * ids_stride + u]:
+ *   g = sum_k B_gate[e][n][k] * A[t][k],   u = sum_k B_up[e][n][k] * A[t][k]
+ *   C[s * ldc + n] = QG_GLU_REGLU:  (g > 0 ? g : 0.0f) * u
+ *                    QG_GLU_SWIGLU: (g / (1.0f + expf(-g))) * u                         (n < N)
+ * A: block_q8_1 [T][K/32], one row per token (there is no a_rows: gate and up always share the token's row).
+ * B_gate, B_up: n_expert dense matrices [N][K/256] each, both of `wtype`, QG_TYPE_Q4_K or QG_TYPE_Q6_K; they may alias.
+ * ids, ids_stride, C and ldc (0 = N) are those of qg_gemm_w4a8_moe.
+ * Bits: g and u are the values qg_gemm_w4a8_moe gives for the slot on B_gate and on B_up, bit for bit (the kernel runs
+ * the same decode GEMV body twice, at the same LPR, WGS and ONE); each operation of the op is then one rounded fp32
+ * operation (no contraction), the division correctly rounded, expf the device library's (within 1 ulp; for g < -88.72
+ * it overflows and the result is +-0 where the true |value| is below 2^-121). Two launches give identical bits.
+ * A slot whose id is outside [0, n_expert) reads no weight byte and writes N times +0.0f, for either op.
+ * ONE launch, a single kernel node when captured. The host never reads ids; no device allocation, no synchronisation:
+ * capture-safe, and a replayed graph follows the ids it finds in the buffer.
+ * Validation: the order of qg_gemm_w4a8_moe: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive multiple
+ * of 256 (32 where wtype is no super-block type) -> QG_ERR_BAD_K; wtype other than Q4_K / Q6_K (the five 32-element
+ * types among them) -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched; a null pointer ->
+ * QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A and ids 4 B; B_gate and B_up alike 16 B for Q4_K, 2 B for Q6_K).
+ * Then ids_stride < n_used, n_expert < 1, ldc < 0 or 0 < ldc < N -> QG_ERR_INVALID_ARG; then more than 65535 slots or an
+ * expert stride off the weight alignment -> QG_ERR_UNSUPPORTED; then the entry's own refusals, QG_ERR_UNSUPPORTED with
+ * nothing launched: a glu_op other than QG_GLU_REGLU / QG_GLU_SWIGLU, a shape that QG_ALGO_AUTO at M = 1 does not send
+ * to the type's decode GEMV (LDS records beyond 160 KiB: Q4_K K > 124672, Q6_K K > 137728).
+ * qg_moe_glu_config names the launch ("moe_glu:q4k_gemv" / "moe_glu:q6k_gemv", LPR, WGS, ONE, grid, lds: those of
+ * qg_moe_config for the same N, K and type; the op is no part of the launch's shape), launch-free; the same status
+ * codes for the shape.
+ * Standing against the three-kernel sequence (MI355X, uniform router): DESIGN.md 3f, profiles/moe_glu/.
+ * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, a Q8_1-quantized output for the down
+ * product, the weighted sum over experts after down, fused forms of the prefill and batch entries. */
+#define QG_GLU_REGLU  0   /* numbered as ggml's enum ggml_glu_op */
+#define QG_GLU_SWIGLU 2
+int qg_gemm_w4a8_moe_glu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                         int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op,
+                         qg_stream_t stream);
+int qg_moe_glu_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -586,6 +626,12 @@ int qg_mul_mat_id_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* b
  * qg_gemm_w4a8_moe_batch_workspace_size(T, n_used, n_expert) bytes): the entry for batched decode. */
 int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                   qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+/* The fused gate / up pair of an MoE FFN block on views, mapped onto qg_gemm_w4a8_moe_glu: out = glu_op(as_gate x b)
+ * * (as_up x b), both ggml_mul_mat_id on the same b and ids. The views and the refusals of qg_mul_mat_id_from_view, and
+ * two more, both QG_ERR_UNSUPPORTED: b with ne[1] != 1 (gate and up take the token's one row), as_up differing from
+ * as_gate in type, ne or nb. */
+int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
+                                const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

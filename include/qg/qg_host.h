@@ -54,6 +54,16 @@ int qg_gemm_w4a8_moe_cpu(const void* A_q8_1, int a_rows, const void* B_experts, 
                          int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                          int threads);
 
+/* Host twin of qg_gemm_w4a8_moe_glu (qg.h): the same arguments with `ids` in host memory, and `threads` as above.
+ * g and u of a slot have the bits of qg_gemm_w4a8_moe_cpu on B_gate and on B_up (a_rows = 1); the op is the same two
+ * formulas, one rounded fp32 operation each, with libm's expf: QG_GLU_REGLU (g > 0 ? g : 0.0f) * u, QG_GLU_SWIGLU
+ * (g / (1.0f + expf(-g))) * u. An id outside [0, n_expert) gives N times +0.0f. The same validation codes (wtype other
+ * than Q4_K / Q6_K and a glu_op other than these two are QG_ERR_UNSUPPORTED; no alignment is asked); no shape is
+ * unsupported. */
+int qg_gemm_w4a8_moe_glu_cpu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                             int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                             int glu_op, int threads);
+
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */
 int qg_gemm_fp32_cpu(const float* A, const float* B, float* C, int M, int N, int K);
 

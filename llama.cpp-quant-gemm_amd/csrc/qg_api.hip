@@ -11,6 +11,7 @@
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
 #include "qg_moe_batch.hpp"
+#include "qg_moe_glu.hpp"
 #include "qg_moe_prefill.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
@@ -391,9 +392,10 @@ int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
     return QG_ERR_UNSUPPORTED;
 }
 
-// ---- mul_mat_id: the three expert entries -------------------------------------------------------------------
-// A call of qg_gemm_w4a8_moe, _moe_prefill or _moe_batch under the names of qg.h (ws: the entries with a plan), a
-// qg_moe*_config query of one (describe: name the launch there and launch nothing), and what moe_front adds.
+// ---- mul_mat_id: the three expert entries and the fused gate / up entry ---------------------------------------
+// A call of qg_gemm_w4a8_moe, _moe_prefill, _moe_batch or _moe_glu under the names of qg.h (ws: the entries with a
+// plan; B_up, glu_op: _moe_glu, whose B is B_gate), a qg_moe*_config query of one (describe: name the launch there and
+// launch nothing), and what moe_front adds.
 struct MoeCall {
     const void* A; int a_rows;
     const void* B; int n_expert;
@@ -405,6 +407,7 @@ struct MoeCall {
     char* describe; size_t describe_len;
     long estride;  // moe_front: bytes between experts
     int slots;     // moe_front: T * n_used
+    const void* B_up; int glu_op;
 };
 
 // Bytes of a plan's workspace whose tile region is sized for tiles of min_r rows (qg_moe_plan.hpp).
@@ -413,19 +416,20 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
     return (size_t)moe_plan_layout((long)(T * n_used), (long)n_expert, min_r).total * sizeof(int32_t);
 }
 
-// What the three entries check alike, in the order qg.h documents. rows_ok: the entry takes the 32-element types
+// What the entries check alike, in the order qg.h documents. rows_ok: the entry takes the 32-element types
 // (otherwise one of them is a type it does not take, checked at the 32-element granule as in run_product). min_r: 0,
-// or the entry runs a plan in a workspace sized for tiles of min_r rows.
+// or the entry runs a plan in a workspace sized for tiles of min_r rows. up: the entry has a second weights pointer,
+// B_up, checked beside B with the same mask.
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
 //   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
 //   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
-int moe_front(MoeCall& c, bool rows_ok, int min_r) {
+int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false) {
     const bool ksb = is_sb_type(c.wtype);
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? 256 : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
-                            {{c.A, 3}, {c.B, wmask}, {c.ids, 3}, {c.C, 0}});
+                            {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3}, {c.C, 0}});
     if (rc != QG_GO) return rc;
     if ((c.a_rows != 1 && c.a_rows != c.n_used) || c.ids_stride < c.n_used || c.n_expert < 1 || c.ldc < 0 ||
         (c.ldc > 0 && c.ldc < c.N))
@@ -496,6 +500,19 @@ int run_moe_batch(MoeCall& c) {
     return hip_status(launch_moe_batch(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
+// qg_gemm_w4a8_moe_glu, qg_moe_glu_config: Q4_K / Q6_K. Its own refusals: a glu_op it does not have, a shape off the
+// decode GEMV (the bound on the LDS records is part of that route for the super-block types).
+int run_moe_glu(MoeCall& c) {
+    const int rc = moe_front(c, false, 0, true);
+    if (rc != QG_GO) return rc;
+    if ((c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU) || !moe_gemv_route(c)) return QG_ERR_UNSUPPORTED;
+    MoeGluArgs a;
+    a.A = c.A; a.B_gate = c.B; a.B_up = c.B_up; a.ids = c.ids; a.C = c.C;
+    a.ids_stride = (long)c.ids_stride; a.ldc = (long)c.ldc; a.estride = c.estride; a.arow = (long)(c.K / 32) * 36;
+    a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots; a.glu_op = c.glu_op;
+    return hip_status(launch_moe_glu(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
 // qg_moe*_config: the shape alone, as qg_debug_config: 256-B aligned stand-in pointers (a workspace of any size among
 // them), one activation row per token.
 int moe_config(int (*run)(MoeCall&), int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
@@ -503,6 +520,7 @@ int moe_config(int (*run)(MoeCall&), int T, int n_used, int n_expert, int N, int
     buf[0] = 0;
     MoeCall c{(const void*)256, 1, (const void*)256, n_expert, (const int32_t*)256, n_used, (float*)256, 0, T, n_used, N, K,
               wtype, (void*)256, SIZE_MAX, nullptr, buf, len};
+    c.B_up = c.B;
     return run(c);
 }
 
@@ -626,6 +644,32 @@ int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype
 int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                   qg_tensor_view* out, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
     return mul_mat_id_from_view(run_moe_batch, as, b, ids, out, workspace, workspace_bytes, stream);
+}
+
+int qg_gemm_w4a8_moe_glu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                         int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op,
+                         qg_stream_t stream) {
+    MoeCall c{A_q8_1, 1, B_gate, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, nullptr, 0, (hipStream_t)stream};
+    c.B_up = B_up; c.glu_op = glu_op;
+    return run_moe_glu(c);
+}
+
+int qg_moe_glu_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_glu, T, n_used, 1, N, K, wtype, buf, len);
+}
+
+int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
+                                const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, qg_stream_t stream) {
+    if (!as_up) return QG_ERR_INVALID_ARG;
+    MoeCall c;
+    const int rc = mul_mat_id_view(as_gate, b, ids, out, c);
+    if (rc != QG_GO) return rc;
+    if (c.a_rows != 1 || as_up->type != as_gate->type || memcmp(as_up->ne, as_gate->ne, sizeof as_up->ne) != 0 ||
+        memcmp(as_up->nb, as_gate->nb, sizeof as_up->nb) != 0)
+        return QG_ERR_UNSUPPORTED;
+    c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
+    c.B_up = as_up->data; c.glu_op = glu_op;
+    return run_moe_glu(c);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -1,0 +1,181 @@
+// qg_moe_glu.hip — the fused gate / up mul_mat_id with its GLU (qg_gemm_w4a8_moe_glu), families "moe_glu:q4k_gemv",
+// "moe_glu:q6k_gemv": the first half of an MoE FFN block, act(gate(x)) * up(x), in one launch.
+//
+// The grid is the decode entry's (qg_moe.hip): blockIdx.y is the slot s = t * n_used + u, blockIdx.x its row tile, the
+// expert id one scalar load, an id outside [0, n_expert) a workgroup-uniform branch that stores +0.0f and returns
+// before any weight address is formed. A workgroup then runs the Q4_K / Q6_K decode GEMV body twice on the token's
+// activation row, at the single call's LPR, WGS and ONE: once on expert e of B_gate, once on expert e of B_up. The body
+// is the very text the shipped kernel and the decode entry include (qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc) with its
+// output bound to a register, so g and u carry the bits of qg_gemm_w4a8_moe on either operand. The lane that holds the
+// reduced sums applies the op and makes the slot's one store per row: the two slots x N intermediate floats of the
+// three-kernel sequence are never written.
+// The gate pass stages the activation row into the LDS records (the body's own prologue, with its barrier); the up pass
+// includes the body with QG_KQ_A_STAGED and reads the same records: no second staging and no barrier between the
+// passes, so a wave starts its up units as soon as its own gate sum is reduced. profiles/moe_glu/README.md: against
+// staging in both passes (QG_MOE_GLU_STAGE_ONCE=0, the form the entry started from), captured, it takes 0.83 - 0.96 of
+// the time in seven of the eight measured classes and the same time in one (Mixtral Q4_K at 16 slots), with the same bits.
+// The arguments travel by value (no device allocation, capture-safe); the host never reads ids.
+#include "../../include/qg/qg.h"
+#include "qg_kq_launch.hpp"
+#include "qg_moe_glu.hpp"
+#include "qg_q4k.hpp"
+#include "qg_q6k.hpp"
+
+namespace qg {
+
+// One decode GEMV product at one activation row, returned in the lane that holds the row's reduced sum (row < N and
+// lane % LPR == LPR - 1; 0.0f in every other lane): the body's four constants as the single call passes them at M = 1.
+#define QG_KQ_DECLARE_TILE  // tile is a parameter here
+#define QG_KQ_ABLK(g) A + (long)g * 9
+#define QG_KQ_OUT(m) (*((void)C, &res))
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ float q4k_glu_product(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                                 const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    void* const out = nullptr;
+    float res = 0.0f;
+#include "qg_q4k_gemv_body.inc"
+    return res;
+}
+
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ float q6k_glu_product(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                                 const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    void* const out = nullptr;
+    float res = 0.0f;
+#include "qg_q6k_gemv_body.inc"
+    return res;
+}
+
+// The same with the activation row already in the LDS records (QG_KQ_A_STAGED: the up pass after the gate pass).
+#define QG_KQ_A_STAGED
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ float q4k_glu_product_staged(const uint8_t* __restrict__ B, int N, int K, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    void* const out = nullptr;
+    float res = 0.0f;
+#include "qg_q4k_gemv_body.inc"
+    return res;
+}
+
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ float q6k_glu_product_staged(const uint8_t* __restrict__ B, int N, int K, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    void* const out = nullptr;
+    float res = 0.0f;
+#include "qg_q6k_gemv_body.inc"
+    return res;
+}
+#undef QG_KQ_A_STAGED
+#undef QG_KQ_OUT
+#undef QG_KQ_ABLK
+#undef QG_KQ_DECLARE_TILE
+
+// 1: the up pass reads the records the gate pass staged; 0: both passes stage, a barrier between them (A/B builds).
+#ifndef QG_MOE_GLU_STAGE_ONCE
+#define QG_MOE_GLU_STAGE_ONCE 1
+#endif
+
+namespace {
+
+constexpr size_t MOE_GLU_LDS_MAX = 160 * 1024;
+
+// Each operation one rounded fp32 operation (the build has contraction off and the correctly rounded division).
+__device__ __forceinline__ float glu(float g, float u, int op) {
+    if (op == QG_GLU_REGLU) return (g > 0.0f ? g : 0.0f) * u;
+    return (g / (1.0f + expf(-g))) * u;
+}
+
+template <int WT, int LPR, int WGS, bool ONE>
+__global__ __launch_bounds__(WGS) void kq_moe_glu_kernel(const MoeGluArgs a) {
+    constexpr int RPW = 64 / LPR, RPB = (WGS / 64) * RPW;
+    const int tile = xcd_tile_x();  // the single launch's order within the slot
+    const int slot = blockIdx.y;
+    const int t = slot / a.n_used, us = slot - t * a.n_used;
+    const int e = a.ids[(long)t * a.ids_stride + us];
+    float* C = a.C + (long)slot * a.ldc;
+    if ((unsigned)e >= (unsigned)a.n_expert) {
+        const int r1 = min(a.N, (tile + 1) * RPB);
+        for (int r = tile * RPB + (int)threadIdx.x; r < r1; r += WGS) C[r] = 0.0f;
+        return;
+    }
+    const uint32_t* A = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.A) + (long)t * a.arow);
+    const long eoff = (long)e * a.estride;
+    const uint8_t* Bg = static_cast<const uint8_t*>(a.B_gate) + eoff;
+    const uint8_t* Bu = static_cast<const uint8_t*>(a.B_up) + eoff;
+    float g, u;
+    if constexpr (WT == QG_TYPE_Q4_K) {
+        g = q4k_glu_product<LPR, WGS, ONE>(A, Bg, a.N, a.K, tile);
+#if QG_MOE_GLU_STAGE_ONCE
+        u = q4k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, tile);
+#else
+        __syncthreads();
+        u = q4k_glu_product<LPR, WGS, ONE>(A, Bu, a.N, a.K, tile);
+#endif
+    } else {
+        g = q6k_glu_product<LPR, WGS, ONE>(A, Bg, a.N, a.K, tile);
+#if QG_MOE_GLU_STAGE_ONCE
+        u = q6k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, tile);
+#else
+        __syncthreads();
+        u = q6k_glu_product<LPR, WGS, ONE>(A, Bu, a.N, a.K, tile);
+#endif
+    }
+    // the body's row of this lane, and its holder of the reduced sum
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int row = tile * RPB + (tid >> 6) * RPW + lane / LPR;
+    if (row < a.N && lane % LPR == LPR - 1) C[row] = glu(g, u, a.glu_op);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------
+struct MoeGluLaunch {
+    const MoeGluArgs& a;
+    hipStream_t st;
+    char* describe;  // qg_moe_glu_config: name the kernel here, launch nothing
+    size_t describe_len;
+};
+
+template <int WT, int LPR, int WGS, bool ONE> hipError_t moe_glu_k(const MoeGluLaunch& L) {
+    constexpr int RPB = (WGS / 64) * (64 / LPR);
+    const size_t lds = (size_t)(L.a.K / SB_ELEMS) * (WT == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4;
+    const int grid = (L.a.N + RPB - 1) / RPB;
+    if (L.describe) {
+        describe_line(L.describe, L.describe_len, "moe_glu:%s LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
+                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", LPR, WGS, (int)ONE, grid, L.a.slots, lds);
+        return hipSuccess;
+    }
+    auto k = kq_moe_glu_kernel<WT, LPR, WGS, ONE>;
+    if (lds > 64 * 1024) {
+        static std::atomic<unsigned long long> done;
+        const hipError_t e = set_max_lds_once((const void*)k, (int)MOE_GLU_LDS_MAX, done);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k, dim3(grid, L.a.slots), dim3(WGS), lds, L.st, L.a);
+    return hipGetLastError();
+}
+
+// kq_gemv_launch_lpr / kq_gemv_launch_cfg at MT = 1 (qg_kq_launch.hpp), as the decode entry (qg_moe.hip, moe_kq)
+template <int WT> hipError_t moe_glu_kq(const MoeGluLaunch& L) {
+    const int U = L.a.K / 64;
+    if (U >= 64) return U <= 64 ? moe_glu_k<WT, 64, 1024, true>(L) : moe_glu_k<WT, 64, 1024, false>(L);
+    if (U >= 16) return U <= 16 ? moe_glu_k<WT, 16, 512, true>(L) : moe_glu_k<WT, 16, 512, false>(L);
+    return U <= 4 ? moe_glu_k<WT, 4, 256, true>(L) : moe_glu_k<WT, 4, 256, false>(L);
+}
+
+}  // namespace
+
+hipError_t launch_moe_glu(const MoeGluArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    const MoeGluLaunch L{a, st, describe, describe_len};
+    switch (wtype) {
+        case QG_TYPE_Q4_K: return moe_glu_kq<QG_TYPE_Q4_K>(L);
+        case QG_TYPE_Q6_K: return moe_glu_kq<QG_TYPE_Q6_K>(L);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace qg

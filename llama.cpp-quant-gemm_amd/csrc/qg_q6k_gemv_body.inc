@@ -1,13 +1,17 @@
 // qg_q6k_gemv_body.inc — the body of the Q6_K decode GEMV, included as text into q6k_gemv_kernel (qg_q6k_gemv.hip,
 // where the work decomposition is described) and q6k_moe_body (qg_moe.hip) and
-// q6k_moeb_kernel (qg_moe_batch.hip). Text and not a function they call: the
-// compiler sees the same tokens in the same function as before, so the shipped code objects do not move (DESIGN.md 3c).
+// q6k_moeb_kernel (qg_moe_batch.hip) and q6k_glu_product[_staged] (qg_moe_glu.hip). Text and not a function they
+// call: the compiler sees the same tokens in the same function as before, so the shipped code objects do not move
+// (DESIGN.md 3c).
 // Expects in scope: A, B (the operands), M, N, K, out, ldc, the template parameters or constants MT, LPR, WGS, SUMI,
 // ONE, and three macros, the lines in which the includers differ:
 //   QG_KQ_DECLARE_TILE  the declaration of `const int tile` in the kernel, nothing where tile is a parameter
 //   QG_KQ_ABLK(g)       the address of activation block g = m * K/32 + b in staging: `A + (long)g * 9` for dense rows,
 //                       the gathered row of tile position m in the expert-grouped GEMV (qg_moe_batch.hip)
 //   QG_KQ_OUT(m)        the output of token m at this lane's row: `C[m * ldc + row]`, the slot's row there
+// and one the shipped includers leave undefined:
+//   QG_KQ_A_STAGED      defined: the LDS records already hold the activation row (an earlier pass of the same
+//                       workgroup staged it and a barrier has passed); the body loads its first unit and goes on
     constexpr int RPW = 64 / LPR;
     constexpr int RPB = (WGS / 64) * RPW;  // rows per workgroup
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -38,6 +42,10 @@
         dst[21] = d1[0];
     };
 
+#ifdef QG_KQ_A_STAGED
+    uint32_t cur[Q6K_UNIT_DW];
+    load_unit(cur, lir);
+#else
     // 1) this thread's first activation block, 2) the lane's first unit, 3) the LDS records
     const int totb = M * nb;
     auto load_ablk = [&](int g, uint32_t (&d)[9]) {
@@ -72,6 +80,7 @@
         put_ablk(g, ab);
     }
     __syncthreads();
+#endif
 
     float acc[MT];
 #pragma unroll

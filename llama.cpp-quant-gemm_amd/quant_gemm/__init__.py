@@ -35,6 +35,7 @@ Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 2, 3, 6, 7, 8, 9
 Q4_K = 12  # 256-element super-blocks of 144 bytes (qg.h "Q4_K weights")
 Q6_K = 14  # 256-element super-blocks of 210 bytes (qg.h "Q6_K weights")
 BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210}
+GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* (numbered as ggml_glu_op): the ops of gemm_w4a8_moe_glu
 ALGO_AUTO, ALGO_GEMV, ALGO_MFMA, ALGO_GENERIC, ALGO_RAGGED = 0, 1, 2, 3, 4
 WEIGHT_TYPES = (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0)
 # what gemm_w4a8 / gemm_w4a8_f32 / debug_sumi take; the layout entries (tiled, repacked, grouped, batched) keep
@@ -379,6 +380,36 @@ def moe_batch_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: 
     """The launch ``gemm_w4a8_moe_batch`` makes for this shape ("moeb:q4k_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=..",
     R the rows per tile, Y the host's upper bound on the tiles); nothing is launched. Raises where the shape is not served."""
     return _config("qg_moe_batch_config", T, n_used, n_expert, N, K, wtype)
+
+
+def gemm_w4a8_moe_glu(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor, ids: torch.Tensor, T: int,
+                      n_used: int, N: int, K: int, wtype: int = Q4_K, glu_op: int = GLU_SWIGLU,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """The first half of an MoE FFN block in ONE launch (qg_gemm_w4a8_moe_glu): C[t, u, :] = glu_op(g) * u with
+    g = gate_q[ids[t, u]] . activation_q[t] and u = up_q[ids[t, u]] . activation_q[t], float32 [T, n_used, N]. It
+    replaces two ``gemm_w4a8_moe`` calls and the activation kernel between them and the down product.
+
+    ``activation_q``: Q8_1 [T, K/32, 36], one row per token. ``gate_q``, ``up_q``: [n_expert, N, K/256, block bytes]
+    of ``wtype``, Q4_K or Q6_K, dense, of one size; they may be the same tensor. ``ids`` and ``out``: as ``gemm_w4a8_moe``.
+    ``glu_op``: GLU_SWIGLU, (g / (1 + expf(-g))) * u, or GLU_REGLU, max(g, 0) * u. g and u have the bits ``gemm_w4a8_moe``
+    gives on either tensor. Shapes the decode GEMV does not serve raise."""
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the fused gate / up entry takes Q4_K and Q6_K")
+    _require(glu_op in (GLU_REGLU, GLU_SWIGLU), f"unsupported glu_op {glu_op}")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, gate_q, ids, T, n_used, N, K, wtype, 1, out)
+    _require(up_q.is_cuda and up_q.dtype == torch.uint8 and up_q.device == w.device and up_q.numel() == w.numel(),
+             "Up experts must be a CUDA uint8 tensor of the gate experts' size, on their device")
+    up = up_q.contiguous()
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_glu(_ptr(a), _ptr(w), _ptr(up), n_expert, _ptr(ids), ids_stride, _ptr(out),
+                                                    ldc, T, n_used, N, K, wtype, glu_op, _stream(w.device)),
+                   "gemm_w4a8_moe_glu")
+    return out
+
+
+def moe_glu_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_glu`` makes for this shape ("moe_glu:q4k_gemv LPR=.. WGS=.. ONE=.. grid=XxY lds=..", the
+    LPR / WGS / ONE of ``moe_config``); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_glu_config", T, n_used, N, K, wtype)
 
 
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
@@ -777,4 +808,5 @@ __all__ = [
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
+    "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU",
 ]

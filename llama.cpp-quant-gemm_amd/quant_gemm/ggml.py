@@ -99,6 +99,17 @@ def mul_mat_id_from_ggml_batch(experts: TensorView, act: TensorView, ids: Tensor
     _mul_mat_id("qg_mul_mat_id_from_view_batch", experts, act, ids, out, workspace)
 
 
+def mul_mat_id_glu_from_ggml(gate: TensorView, up: TensorView, act: TensorView, ids: TensorView, out: TensorView,
+                             glu_op: int = 2) -> None:
+    """The fused gate / up pair of an MoE FFN block on views (qg_mul_mat_id_glu_from_view): out = glu_op(gate x act) *
+    (up x act), the views of ``mul_mat_id_from_ggml`` with Q4_K / Q6_K experts, act [K, 1, T] and ``up`` matching
+    ``gate`` in type, ne and nb. ``glu_op``: 2 SwiGLU, 0 ReGLU (ggml_glu_op's numbers)."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().qg_mul_mat_id_glu_from_view(ctypes.byref(gate), ctypes.byref(up), ctypes.byref(act),
+                                                       ctypes.byref(ids), ctypes.byref(out), glu_op, st),
+               "qg_mul_mat_id_glu_from_view")
+
+
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:
     """include/llama_adapter.h:110-117."""
     return bool(_lib.load().qg_validate_view_types(ctypes.byref(act), ctypes.byref(w), ctypes.byref(out), ea, ew, eo))

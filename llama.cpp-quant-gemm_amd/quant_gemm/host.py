@@ -20,6 +20,7 @@ SIGNATURES = {
     "qg_gemm_w8a8_cpu": ([P, P, P, I, I, I], I),
     "qg_gemm_w4a8_cpu_mt": ([P, P, P, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_glu_cpu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, I], I),
     "qg_gemm_fp32_cpu": ([P, P, P, I, I, I], I),
     "qg_quantize_row_q8_1_cpu": ([P, P, I64], I),
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
@@ -27,6 +28,7 @@ SIGNATURES = {
 }
 # 12: Q4_K, 14: Q6_K, 256-element super-blocks
 BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210}
+GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* of qg.h
 _lib = None
 
 
@@ -98,6 +100,25 @@ def gemm_w4a8_moe(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, t: in
     c = np.empty((t, n_used, n), np.float32)
     _ok(load().qg_gemm_w4a8_moe_cpu(_p(a_q), a_rows, _p(experts_q), n_expert, _p(ids), ids_stride, _p(c), n, t, n_used, n,
                                     k, wtype, threads), "gemm_w4a8_moe_cpu")
+    return c
+
+
+def gemm_w4a8_moe_glu(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, ids: np.ndarray, t: int, n_used: int, n: int,
+                      k: int, wtype: int = 12, glu_op: int = GLU_SWIGLU, threads: int = 1,
+                      ids_stride: int | None = None) -> np.ndarray:
+    """C[t, n_used, n] of qg_gemm_w4a8_moe_glu_cpu: slot (t, u) = glu_op(g) * u with g, u the products of activation
+    row t with expert ids[t, u] of ``gate_q`` and of ``up_q`` (n_expert Q4_K / Q6_K matrices each). ``ids``: int32
+    [t, ids_stride] (the stride defaults to the array's row length); an id outside [0, n_expert) gives zeros."""
+    a_q, gate_q, up_q = np.ascontiguousarray(a_q), np.ascontiguousarray(gate_q), np.ascontiguousarray(up_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    if gate_q.size != up_q.size:
+        raise RuntimeError("gemm_w4a8_moe_glu_cpu: gate and up experts differ in size")
+    n_expert = gate_q.size // (n * (k // 256) * BLOCK_BYTES[wtype])
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    c = np.empty((t, n_used, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_glu_cpu(_p(a_q), _p(gate_q), _p(up_q), n_expert, _p(ids), ids_stride, _p(c), n, t, n_used, n,
+                                        k, wtype, glu_op, threads), "gemm_w4a8_moe_glu_cpu")
     return c
 
 
