@@ -1,6 +1,7 @@
 // qg_gemv_impl.hpp — the GEMV dispatch templates (configuration per shape), instantiated once per
 // weight format in qg_gemv_<fmt>.hip so the formats compile in parallel; qg_gemv.hip holds the
-// format switch (gemv_eligible, launch_gemv).
+// format switch (gemv_eligible, launch_gemv). The choice itself is gemv_form below, which the
+// expert-indexed launch (qg_moe.hip) visits too.
 #pragma once
 #include "qg_gemv_kernel.hpp"
 
@@ -37,9 +38,13 @@ constexpr int gemvm_wgs = QG_GEMVM_WGS ? QG_GEMVM_WGS : (F == FMT_Q5_0 || F == F
 // 12.64 -> 12.36), 1024 for the rest (Q4_0 / Q4_1 +3 %, Q5_x equal at 512)
 template <int F> constexpr int gemv1l_wgs = QG_GEMV1L_WGS ? QG_GEMV1L_WGS : F == FMT_Q8_0 ? 512 : 1024;
 
-template <int F, int MT, bool SUMI, int AIN>
-hipError_t launch_staged(const GemmArgs& g, hipStream_t st) {
-    const int nb = g.K / QK;
+// The row GEMV's instantiation for (F, MT, AIN, K), chosen here and nowhere else: fn(BPL, LPR, WGS, PRE) as
+// std::integral_constant / bool_constant (NT is false in every form). launch_staged launches what it is handed; the
+// expert-indexed launch (qg_moe.hip) visits with MT = 1 and NRULE off: by K alone, and no form it cannot get is built.
+template <int F, int MT, int AIN, bool NRULE, class Fn> auto gemv_form(int N, int K, Fn&& fn) {
+    const int nb = K / QK;
+    constexpr std::true_type pre{};
+    constexpr std::bool_constant<(MT <= 2)> pre_mt{};  // gemv_launch's default
     // 2-block units, one row per wave, 1024-thread workgroups (512 for a single row of activations
     // over N >= 16384 rows): profiles/r01_tuning/gemv_probe_focus.txt, gemv_probe_focus2.txt —
     // M=1 Q4_0 3.67 -> 3.60 us, Q5_0 / Q5_1 -6 %, M=2 -4 %, M=4 -11 % against 4-block units x 32
@@ -49,32 +54,38 @@ hipError_t launch_staged(const GemmArgs& g, hipStream_t st) {
     // with the same per-row summation order)
     if constexpr (MT <= 4) {
         if (nb % 2 == 0 && nb / 2 >= 64) {
-            if (MT == 1 && AIN == AIN_Q8_1 && g.N >= 16384 && g.K < 8192)
-                return gemv_launch<F, 1, 2, 64, QG_GEMVBIG_WGS, SUMI, AIN>(g, st);
+            if constexpr (NRULE && MT == 1 && AIN == AIN_Q8_1)
+                if (N >= 16384 && K < 8192) return fn(ic<2>{}, ic<64>{}, ic<QG_GEMVBIG_WGS>{}, pre_mt);
             // activation records preloaded into registers for M <= 4 (profiles/tools_archive/gemv_pre_probe.hip,
             // profiles/r01_tuning/gemv_pre_probe.txt: M=3 4.76 -> 4.52 us, M=4 5.16 -> 5.04 us)
             // Q5_0 / Q5_1: 512-thread workgroups (profiles/r03_tuning/r03_ab_wgs.txt: M=1 3.82 -> 3.78 /
             // 3.93 -> 3.88 us; Q4_0 / Q8_0 are faster at 1024, Q4_1 equal)
             constexpr int W1 = (F == FMT_Q5_0 || F == FMT_Q5_1) ? 512 : QG_GEMV1_WGS;
-            if constexpr (MT == 1) if (nb / 2 <= 64) return gemv_launch<F, MT, 2, 64, W1, SUMI, AIN, false, true>(g, st);
+            if constexpr (MT == 1) if (nb / 2 <= 64) return fn(ic<2>{}, ic<64>{}, ic<W1>{}, pre);
 #if QG_GEMVM_LPR != 64  // (A/B builds) M >= 2: fewer lanes per row, the same rows per workgroup
-            if constexpr (MT >= 2)
-                return gemv_launch<F, MT, 2, QG_GEMVM_LPR, gemvm_wgs<F> * QG_GEMVM_LPR / 64, SUMI, AIN, false, true>(g, st);
+            if constexpr (MT >= 2) return fn(ic<2>{}, ic<QG_GEMVM_LPR>{}, ic<gemvm_wgs<F> * QG_GEMVM_LPR / 64>{}, pre);
 #endif
-            return gemv_launch<F, MT, 2, 64, MT == 1 ? gemv1l_wgs<F> : gemvm_wgs<F>, SUMI, AIN, false, true>(g, st);
+            return fn(ic<2>{}, ic<64>{}, ic<(MT == 1 ? gemv1l_wgs<F> : gemvm_wgs<F>)>{}, pre);
         }
     }
     if constexpr (QG_GEMV_SMALLK && MT <= 4) {
         // K < 4096: 2-block units, 32 / 16 lanes per row, 16 rows per workgroup (256 workgroups at
         // N = 4096) instead of 64-row workgroups of 4-lane rows
-        if (nb % 2 == 0 && nb / 2 >= 32) return gemv_launch<F, MT, 2, 32, 512, SUMI, AIN, false, true>(g, st);
-        if (nb % 2 == 0 && nb / 2 >= 16) return gemv_launch<F, MT, 2, 16, 256, SUMI, AIN, false, true>(g, st);
+        if (nb % 2 == 0 && nb / 2 >= 32) return fn(ic<2>{}, ic<32>{}, ic<512>{}, pre);
+        if (nb % 2 == 0 && nb / 2 >= 16) return fn(ic<2>{}, ic<16>{}, ic<256>{}, pre);
     }
     if (nb % 4 == 0) {
-        if (nb / 4 >= 32) return gemv_launch<F, MT, 4, 32, 512, SUMI, AIN>(g, st);
-        return gemv_launch<F, MT, 4, 4, 256, SUMI, AIN>(g, st);
+        // 4-block units on 32 lanes need K / 32 >= 128, which M <= 4 has sent to the 2-block units above
+        if constexpr (MT > 4) if (nb / 4 >= 32) return fn(ic<4>{}, ic<32>{}, ic<512>{}, pre_mt);
+        return fn(ic<4>{}, ic<4>{}, ic<256>{}, pre_mt);
     }
-    return gemv_launch<F, MT, 2, 8, 256, SUMI, AIN>(g, st);
+    return fn(ic<2>{}, ic<8>{}, ic<256>{}, pre_mt);
+}
+
+template <int F, int MT, bool SUMI, int AIN> hipError_t launch_staged(const GemmArgs& g, hipStream_t st) {
+    return gemv_form<F, MT, AIN, true>(g.N, g.K, [&](auto bpl, auto lpr, auto wgs, auto pre) {
+        return gemv_launch<F, MT, bpl, lpr, wgs, SUMI, AIN, false, pre>(g, st);
+    });
 }
 
 // The sumi parity hook (SUMI = true) runs the very instantiation the product dispatch picks for

@@ -678,18 +678,35 @@ inline bool group_affine_class_enabled(bool one, int MT, bool small_n, int count
     return one && MT == 1 && small_n && count >= 8;
 }
 
+// gemv_body's ONEU for rows of `units` units on `lpr` lanes: 1, one unit per lane; 2 / 4, the loop-free multi-unit form
+// of Q4_0 M = 1 single launches; 0, the unit loop. gemv_launch and the expert-indexed launch (qg_moe.hip) both ask here.
+// profiles/r05_tuning/r5zd_ab.txt, unit loop -> multi-unit: Q4_0 M = 1 K = 14336 7.69 -> 7.46 us, K = 11008
+// 6.32 -> 6.17, K = 8192 5.02 -> 4.78; slower for M = 2..4 (8.93 -> 9.45 at M = 2), Q4_1 (8.02 -> 9.50) and
+// Q8_0 (12.37 -> 12.53), which keep the loop
+template <int F, int MT> constexpr bool gemv_nu_ok = QG_GEMV_NU && MT <= QG_GEMV_NU_MT && F == FMT_Q4_0;
+template <int F, int MT> inline int gemv_unit_form(int units, int lpr) {
+    if (units <= lpr) return 1;
+    const int per_lane = (units + lpr - 1) / lpr;
+    return !gemv_nu_ok<F, MT> ? 0 : per_lane <= 2 ? 2 : per_lane <= 4 ? 4 : 0;
+}
+
+// The smaller workgroups of many-product launches (grouped, strided batch, expert slots) whose rows fit one round of
+// full-size ones: (threads, row tiles) = (wgs / wdiv, tpw) at M = 1, the caller's knobs, and (QG_GEMV_MTGW, QG_GEMV_MTTPW)
+// at M >= 2; wgs == 0: no such form. Whether the rows fit the round (device_cus()) is the caller's test.
+struct GemvSmallWg { int wgs, tpw; };
+constexpr GemvSmallWg gemv_small_wg(int wgs, int mt, int wdiv, int tpw) {
+    const bool mtw = QG_GEMV_MTGW > 0 && mt >= 2;
+    const GemvSmallWg s = mtw ? GemvSmallWg{QG_GEMV_MTGW < wgs ? QG_GEMV_MTGW : wgs, QG_GEMV_MTTPW} : GemvSmallWg{wgs / wdiv, tpw};
+    return s.wgs < wgs && s.wgs >= 64 ? s : GemvSmallWg{0, 0};
+}
+
 template <int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN = AIN_Q8_1, bool NT = false, bool PRE = (MT <= 2)>
 hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
     constexpr int RPB = (WGS / 64) * (64 / LPR);
+    constexpr bool NU_OK = gemv_nu_ok<F, MT>;
     const size_t lds = gemv_lds_bytes<F, BPL>(g.M, g.K);
-    const bool one = g.K / QK / BPL <= LPR;
-    // units per lane of the loop-free multi-unit form: Q4_0 M = 1 single launches only (0: the unit loop).
-    // profiles/r05_tuning/r5zd_ab.txt, unit loop -> multi-unit: Q4_0 M = 1 K = 14336 7.69 -> 7.46 us, K = 11008
-    // 6.32 -> 6.17, K = 8192 5.02 -> 4.78; slower for M = 2..4 (8.93 -> 9.45 at M = 2), Q4_1 (8.02 -> 9.50) and
-    // Q8_0 (12.37 -> 12.53), which keep the loop
-    constexpr bool NU_OK = QG_GEMV_NU && MT <= QG_GEMV_NU_MT && F == FMT_Q4_0;
-    const int nu_all = (g.K / QK / BPL + LPR - 1) / LPR;
-    const int nu = one ? 1 : !NU_OK ? 0 : nu_all <= 2 ? 2 : nu_all <= 4 ? 4 : 0;
+    const int nu = gemv_unit_form<F, MT>(g.K / QK / BPL, LPR);
+    const bool one = nu == 1;
     // M = 1, one product, unit output stride: the minimal-argument entry (gemv1_kernel)
     const bool m1 = MT == 1 && PRE && !NT && g.M == 1 && g.batch == 1 && g.ldc_n == 1;
     const bool shrt = !m1 && !NT && g.batch == 1 && g.ldc_m <= INT32_MAX && g.ldc_n <= INT32_MAX;
@@ -794,21 +811,19 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
             // ab_grouped_wgs_r4g2.txt, 64 items per launch, N = K = 4096: Q4_0 M = 1 1.541 -> 1.509 us per
             // GEMV, M = 2 1.853 -> 1.688, M = 4 2.705 -> 2.494, Q8_0 2.885 -> 2.767; N = 11008 (344 tiles)
             // 3.92 -> 4.01 with them, so larger items keep full-size workgroups)
-            constexpr bool MTW = QG_GEMV_MTGW > 0 && MT >= 2;
-            constexpr int GWH = MTW ? (QG_GEMV_MTGW < WGS ? QG_GEMV_MTGW : WGS) : WGS / QG_GEMVG_WDIV;
-            constexpr int TPH = MTW ? QG_GEMV_MTTPW : QG_GEMVG_TPW;
-            if constexpr (GWH < WGS && GWH >= 64) {
+            constexpr GemvSmallWg SG = gemv_small_wg(WGS, MT, QG_GEMVG_WDIV, QG_GEMVG_TPW);
+            if constexpr (SG.wgs > 0) {
                 const int rpw_full = one ? RPB * QG_GEMVG_TPW : RPB;
                 int nmax = 0;
                 for (int i = 0; i < grp0.count; ++i) nmax = std::max(nmax, grp0.it[i].N);
                 if ((nmax + rpw_full - 1) / rpw_full <= device_cus())
-                    return go(std::integral_constant<int, GWH>{}, std::integral_constant<int, TPH>{});
+                    return go(std::integral_constant<int, SG.wgs>{}, std::integral_constant<int, SG.tpw>{});
             }
             return go(std::integral_constant<int, WGS>{}, std::integral_constant<int, QG_GEMVG_TPW>{});
         }
     }
-    if (m1) {
-        auto k1 = nu == 1 ? gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 1> : gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 0>;
+    if constexpr (MT == 1 && PRE && !NT) if (m1) {  // (no gemv1_kernel from the M tiles that cannot launch it)
+        auto k1 =nu == 1 ? gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 1> : gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 0>;
         if constexpr (NU_OK) {
             if (nu == 2) k1 = gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 2>;
             if (nu == 4) k1 = gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 4>;
@@ -847,11 +862,9 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
 #ifndef QG_GEMVB_WDIV
 #define QG_GEMVB_WDIV 2
 #endif
-    constexpr bool MTB = QG_GEMV_MTGW > 0 && MT >= 2;
-    constexpr int GWB = MTB ? (QG_GEMV_MTGW < WGS ? QG_GEMV_MTGW : WGS) : WGS / QG_GEMVB_WDIV;
-    constexpr int TPB = MTB ? QG_GEMV_MTTPW : QG_GEMV_TPW;
-    if constexpr (GWB < WGS && GWB >= 64 && !SUMI && !NT) {
-        constexpr int GW = GWB, RPBB = (GW / 64) * (64 / LPR) * TPB;
+    constexpr GemvSmallWg SB = gemv_small_wg(WGS, MT, QG_GEMVB_WDIV, QG_GEMV_TPW);
+    if constexpr (SB.wgs > 0 && !SUMI && !NT) {
+        constexpr int GW = SB.wgs, TPB = SB.tpw, RPBB = (GW / 64) * (64 / LPR) * TPB;
         if (one && g.batch > 1 && grid <= device_cus()) {
             if (g.describe) {  // (an affine group: qg_group_config)
                 describe_kernel(g, "gemvb F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=1 TPW=%d grid=%dx%d", F, MT, BPL, LPR, GW,

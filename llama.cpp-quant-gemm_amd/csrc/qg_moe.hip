@@ -5,14 +5,14 @@
 // blockIdx.x its row tile. The workgroup reads its expert id e = ids[t * ids_stride + u] from device memory with one
 // scalar load (the slot is uniform over the workgroup), forms the slot's activation row, expert matrix and output
 // row from 64-bit offsets and then runs the very body the single M = 1 product runs for this (type, K):
-//   * Q4_0 .. Q8_0: gemv_body<F, 1, BPL, LPR, ...> (qg_gemv_kernel.hpp) with the BPL / LPR / ONEU that launch_staged
-//     and gemv_launch pick for the single call (moe_row_k below restates that choice; tests/test_moe_cpu.py holds
-//     qg_moe_config against qg_debug_config). The workgroup size and the row tiles per workgroup are the grouped
-//     launch's: half-size workgroups of two tiles while N fits one round of full-size ones, full-size ones beyond
-//     (of one tile for Q8_0, moe_big_tpw). Neither changes a row's arithmetic.
+//   * Q4_0 .. Q8_0: gemv_body<F, 1, BPL, LPR, ...> (qg_gemv_kernel.hpp) with the BPL / LPR / ONEU of the single call:
+//     the launcher visits the single call's own choice, gemv_form (qg_gemv_impl.hpp) and gemv_unit_form
+//     (qg_gemv_kernel.hpp). The workgroup size and the row tiles per workgroup are the grouped launch's
+//     (gemv_small_wg): half-size workgroups of two tiles while N fits one round of full-size ones, full-size ones
+//     beyond (of one tile for Q8_0, moe_big_tpw). Neither changes a row's arithmetic.
 //   * Q4_K / Q6_K: q4k_moe_body / q6k_moe_body<LPR, WGS, ONE> (below: the shipped kernels' bodies at one activation
 //     row, the same text included: qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc), the single call's LPR, WGS and ONE
-//     (kq_gemv_launch_lpr).
+//     (kq_gemv_form, qg_kq_launch.hpp).
 // So every slot's outputs are bit-identical to the eager qg_gemm_w4a8 on that slot's operands.
 // An id outside [0, n_expert) is a workgroup-uniform branch taken before any weight address is formed: the
 // workgroup stores +0.0f to its rows of the slot and returns.
@@ -53,7 +53,6 @@ __device__ __forceinline__ void q6k_moe_body(const uint32_t* __restrict__ A, con
 
 namespace {
 
-constexpr size_t MOE_LDS_MAX = 160 * 1024;
 // Row tiles per full-size workgroup of the loop-free row form once N exceeds one round (0: per format; A/B builds
 // force 1 or 2). profiles/moe/ab_moe_tpw.txt, N = 14336, K = 4096, us per slot at 2 / 8 / 16 slots, two tiles -> one:
 // Q8_0 13.91 -> 12.21, 10.26 -> 9.55, 9.56 -> 8.93 (at 2 slots two tiles lose to one kernel node per slot, 12.8);
@@ -108,24 +107,9 @@ __global__ __launch_bounds__(WGS) void kq_moe_kernel(const MoeArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-struct MoeLaunch {
-    const MoeArgs& a;
-    hipStream_t st;
-    char* describe;  // qg_moe_config: name the kernel here, launch nothing
-    size_t describe_len;
-};
+using Launch = MoeLaunch<MoeArgs>;
 
-template <class Kern>
-hipError_t moe_enqueue(Kern k, const MoeLaunch& L, int rpb, int wgs, size_t lds, std::atomic<unsigned long long>& done) {
-    if (lds > 64 * 1024) {
-        const hipError_t e = set_max_lds_once((const void*)k, (int)MOE_LDS_MAX, done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3((L.a.N + rpb - 1) / rpb, L.a.slots), dim3(wgs), lds, L.st, L.a);
-    return hipGetLastError();
-}
-
-template <int F, int BPL, int LPR, int WGS, int ONEU, int TPW> hipError_t moe_row_k(const MoeLaunch& L) {
+template <int F, int BPL, int LPR, int WGS, int ONEU, int TPW> hipError_t moe_row_k(const Launch& L) {
     constexpr int RPB = (WGS / 64) * (64 / LPR) * TPW;
     const size_t lds = gemv_lds_bytes<F, BPL>(1, L.a.K);
     if (L.describe) {
@@ -134,63 +118,48 @@ template <int F, int BPL, int LPR, int WGS, int ONEU, int TPW> hipError_t moe_ro
         return hipSuccess;
     }
     static std::atomic<unsigned long long> done;
-    return moe_enqueue(gemv_moe_kernel<F, BPL, LPR, WGS, ONEU, TPW>, L, RPB, WGS, lds, done);
+    return moe_enqueue(gemv_moe_kernel<F, BPL, LPR, WGS, ONEU, TPW>, L, RPB, L.a.slots, WGS, lds, done);
 }
 
-// The loop form of gemv_launch's M = 1 entry for (BPL, LPR): one unit per lane (ONEU 1), Q4_0's loop-free 2 / 4
-// units, else the unit loop (0). WGS is the single launch's; the one-unit form takes the grouped launch's
-// workgroups (gemv_launch, "workgroups of WGS / QG_GEMVG_WDIV threads ...").
-template <int F, int BPL, int LPR, int WGS> hipError_t moe_row_cfg(const MoeLaunch& L) {
-    const int U = L.a.K / QK / BPL;
-    if (U <= LPR) {
-        constexpr int RPBF = (WGS / 64) * (64 / LPR) * 2;
-        if constexpr (WGS / 2 >= 64)
-            if ((L.a.N + RPBF - 1) / RPBF <= device_cus()) return moe_row_k<F, BPL, LPR, WGS / 2, 1, 2>(L);
+// The single M = 1 call's (BPL, LPR, WGS) and unit form (gemv_form, gemv_unit_form). This launch's own: the one-unit
+// form takes the grouped launch's workgroups (gemv_small_wg: half-size ones of two row tiles while N fits one round of
+// full-size ones) and moe_big_tpw tiles per full-size workgroup beyond.
+template <int F, int BPL, int LPR, int WGS> hipError_t moe_row_cfg(const Launch& L) {
+    const int nu = gemv_unit_form<F, 1>(L.a.K / QK / BPL, LPR);
+    if (nu == 1) {
+        constexpr GemvSmallWg S = gemv_small_wg(WGS, 1, QG_GEMVG_WDIV, QG_GEMVG_TPW);
+        if constexpr (S.wgs > 0) {
+            constexpr int RPBF = (WGS / 64) * (64 / LPR) * QG_GEMVG_TPW;
+            if ((L.a.N + RPBF - 1) / RPBF <= device_cus()) return moe_row_k<F, BPL, LPR, S.wgs, 1, S.tpw>(L);
+        }
         return moe_row_k<F, BPL, LPR, WGS, 1, moe_big_tpw<F>>(L);
     }
-    if constexpr (QG_GEMV_NU && QG_GEMV_NU_MT >= 1 && F == FMT_Q4_0) {
-        const int nu_all = (U + LPR - 1) / LPR;
-        if (nu_all <= 2) return moe_row_k<F, BPL, LPR, WGS, 2, 1>(L);
-        if (nu_all <= 4) return moe_row_k<F, BPL, LPR, WGS, 4, 1>(L);
+    if constexpr (gemv_nu_ok<F, 1>) {
+        if (nu == 2) return moe_row_k<F, BPL, LPR, WGS, 2, 1>(L);
+        if (nu == 4) return moe_row_k<F, BPL, LPR, WGS, 4, 1>(L);
     }
     return moe_row_k<F, BPL, LPR, WGS, 0, 1>(L);
 }
 
-// launch_staged<F, 1, false, AIN_Q8_1> (qg_gemv_impl.hpp) by K alone: its N >= 16384 rule changes the workgroup
-// size only, which is this launch's own choice anyway.
-template <int F> hipError_t moe_row(const MoeLaunch& L) {
-    const int nb = L.a.K / QK;
-    if (nb % 2 == 0 && nb / 2 >= 64) {
-        constexpr int W1 = (F == FMT_Q5_0 || F == FMT_Q5_1) ? 512 : QG_GEMV1_WGS;
-        if (nb / 2 <= 64) return moe_row_cfg<F, 2, 64, W1>(L);
-        return moe_row_cfg<F, 2, 64, gemv1l_wgs<F>>(L);
-    }
-    if (QG_GEMV_SMALLK) {
-        if (nb % 2 == 0 && nb / 2 >= 32) return moe_row_cfg<F, 2, 32, 512>(L);
-        if (nb % 2 == 0 && nb / 2 >= 16) return moe_row_cfg<F, 2, 16, 256>(L);
-    }
-    if (nb % 4 == 0) return moe_row_cfg<F, 4, 4, 256>(L);  // (its 32-lane form needs K/32 >= 128: taken above)
-    return moe_row_cfg<F, 2, 8, 256>(L);
+template <int F> hipError_t moe_row(const Launch& L) {
+    return gemv_form<F, 1, AIN_Q8_1, false>(L.a.N, L.a.K, [&](auto bpl, auto lpr, auto wgs, auto pre) {
+        static_assert(decltype(pre)::value, "gemv_moe_kernel passes PRE = true");
+        return moe_row_cfg<F, bpl, lpr, wgs>(L);
+    });
 }
 
-template <int WT, int LPR, int WGS, bool ONE> hipError_t moe_kq_k(const MoeLaunch& L) {
-    constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const size_t lds = (size_t)(L.a.K / SB_ELEMS) * (WT == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4;
-    if (L.describe) {
-        describe_line(L.describe, L.describe_len, "moe:%s LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
-                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", LPR, WGS, (int)ONE, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
-        return hipSuccess;
-    }
-    static std::atomic<unsigned long long> done;
-    return moe_enqueue(kq_moe_kernel<WT, LPR, WGS, ONE>, L, RPB, WGS, lds, done);
-}
-
-// kq_gemv_launch_lpr / kq_gemv_launch_cfg at MT = 1 (qg_kq_launch.hpp)
-template <int WT> hipError_t moe_kq(const MoeLaunch& L) {
-    const int U = L.a.K / 64;
-    if (U >= 64) return U <= 64 ? moe_kq_k<WT, 64, 1024, true>(L) : moe_kq_k<WT, 64, 1024, false>(L);
-    if (U >= 16) return U <= 16 ? moe_kq_k<WT, 16, 512, true>(L) : moe_kq_k<WT, 16, 512, false>(L);
-    return U <= 4 ? moe_kq_k<WT, 4, 256, true>(L) : moe_kq_k<WT, 4, 256, false>(L);
+template <int WT> hipError_t moe_kq_launch(const Launch& L) {
+    return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+        constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
+        const size_t lds = (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        if (L.describe) {
+            describe_line(L.describe, L.describe_len, "moe:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), LPR, WGS,
+                          (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
+            return hipSuccess;
+        }
+        static std::atomic<unsigned long long> done;
+        return moe_enqueue(kq_moe_kernel<WT, LPR, WGS, one>, L, RPB, L.a.slots, WGS, lds, done);
+    });
 }
 
 }  // namespace
@@ -199,19 +168,19 @@ template <int WT> hipError_t moe_kq(const MoeLaunch& L) {
 // in the launch instead); the super-block types' bound is their gemv_eligible.
 bool moe_lds_ok(int wtype, int K) {
     if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K) return true;
-    return gemv_lds_bytes<FMT_Q4_0, 2>(1, K) <= MOE_LDS_MAX;  // (2-block units: the record size is the formats' common one)
+    return gemv_lds_bytes<FMT_Q4_0, 2>(1, K) <= MAX_LDS_BYTES;  // (2-block units: the record size is the formats' common one)
 }
 
 hipError_t launch_moe(const MoeArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
-    const MoeLaunch L{a, st, describe, describe_len};
+    const Launch L{a, st, describe, describe_len};
     switch (wtype) {
         case FMT_Q4_0: return moe_row<FMT_Q4_0>(L);
         case FMT_Q4_1: return moe_row<FMT_Q4_1>(L);
         case FMT_Q5_0: return moe_row<FMT_Q5_0>(L);
         case FMT_Q5_1: return moe_row<FMT_Q5_1>(L);
         case FMT_Q8_0: return moe_row<FMT_Q8_0>(L);
-        case QG_TYPE_Q4_K: return moe_kq<QG_TYPE_Q4_K>(L);
-        case QG_TYPE_Q6_K: return moe_kq<QG_TYPE_Q6_K>(L);
+        case QG_TYPE_Q4_K: return moe_kq_launch<QG_TYPE_Q4_K>(L);
+        case QG_TYPE_Q6_K: return moe_kq_launch<QG_TYPE_Q6_K>(L);
     }
     return hipErrorInvalidValue;
 }

@@ -7,7 +7,7 @@
 //  2. q4k_moeb_kernel / q6k_moeb_kernel<MT = R, LPR, WGS, ONE>: the body of q4k_gemv_kernel / q6k_gemv_kernel
 //     (qg_q4k_gemv.hip, qg_q6k_gemv.hip: the work decomposition is described there), the same text included
 //     (qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc), at the LPR, WGS and ONE the single M = 1 call takes for this K
-//     (kq_gemv_launch_lpr). What differs, all of it in the prologue and in the body's two hooks:
+//     (kq_gemv_form, qg_kq_launch.hpp). What differs, all of it in the prologue and in the body's two hooks:
 //       * blockIdx.y is a tile index. The workgroup reads n_tiles and its record (uniform) and returns at once
 //         beyond n_tiles: gridDim.y is the host's upper bound moe_max_tiles.
 //       * activation block g = m * K/32 + b of the staging is block b of row rows[first + m] (QG_KQ_ABLK): the R
@@ -75,55 +75,40 @@ template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) 
 #undef QG_KQ_DECLARE_TILE
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-constexpr size_t moeb_rec_bytes(int wtype) { return (wtype == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4; }
+using Launch = MoeLaunch<MoePlanArgs>;
 
-struct MoebLaunch {
-    const MoePlanArgs& a;
-    hipStream_t st;
-    char* describe;
-    size_t describe_len;
-};
-
-template <int WT, int MT, int LPR, int WGS, bool ONE> hipError_t moeb_k(const MoebLaunch& L) {
-    constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const MoePlanArgs& a = L.a;
-    const size_t lds = (size_t)MT * (a.K / SB_ELEMS) * moeb_rec_bytes(WT);
-    const int gx = (a.N + RPB - 1) / RPB, gy = (int)moe_max_tiles(a.slots, a.n_expert, MT);
-    if (L.describe) {
-        describe_line(L.describe, L.describe_len, "moeb:%s R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
-                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", MT, LPR, WGS, (int)ONE, gx, gy, lds);
-        return hipSuccess;
-    }
-    auto k = [] {
-        if constexpr (WT == QG_TYPE_Q4_K) return q4k_moeb_kernel<MT, LPR, WGS, ONE>;
-        else return q6k_moeb_kernel<MT, LPR, WGS, ONE>;
-    }();
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> done;
-        const hipError_t e = set_max_lds_once((const void*)k, (int)MOE_BATCH_LDS_MAX, done);
+// The plan for tiles of MT rows, then the product at the single M = 1 call's LPR, WGS and ONE (kq_gemv_form,
+// qg_kq_launch.hpp), which depend on K alone.
+template <int WT, int MT> hipError_t moeb_mt(const Launch& L) {
+    return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+        constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
+        constexpr bool ONE = one;
+        const MoePlanArgs& a = L.a;
+        const size_t lds = (size_t)MT * (a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const int gy = (int)moe_max_tiles(a.slots, a.n_expert, MT);
+        if (L.describe) {
+            describe_line(L.describe, L.describe_len, "moeb:%s_gemv R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), MT,
+                          LPR, WGS, (int)ONE, (a.N + RPB - 1) / RPB, gy, lds);
+            return hipSuccess;
+        }
+        int rsh = 0;
+        while ((1 << rsh) < MT) ++rsh;
+        const hipError_t e = launch_moe_plan_rows(a, rsh, L.st);
         if (e != hipSuccess) return e;
-    }
-    int rsh = 0;
-    while ((1 << rsh) < MT) ++rsh;
-    const hipError_t e = launch_moe_plan_rows(a, rsh, L.st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(gx, gy), dim3(WGS), lds, L.st, a);
-    return hipGetLastError();
+        auto k = [] {
+            if constexpr (WT == QG_TYPE_Q4_K) return q4k_moeb_kernel<MT, LPR, WGS, ONE>;
+            else return q6k_moeb_kernel<MT, LPR, WGS, ONE>;
+        }();
+        static std::atomic<unsigned long long> done;
+        return moe_enqueue(k, L, RPB, gy, WGS, lds, done);
+    });
 }
 
-// kq_gemv_launch_lpr / kq_gemv_launch_cfg (qg_kq_launch.hpp) by K alone, as moe_kq (qg_moe.hip)
-template <int WT, int MT> hipError_t moeb_lpr(const MoebLaunch& L) {
-    const int U = L.a.K / 64;
-    if (U >= 64) return U <= 64 ? moeb_k<WT, MT, 64, 1024, true>(L) : moeb_k<WT, MT, 64, 1024, false>(L);
-    if (U >= 16) return U <= 16 ? moeb_k<WT, MT, 16, 512, true>(L) : moeb_k<WT, MT, 16, 512, false>(L);
-    return U <= 4 ? moeb_k<WT, MT, 4, 256, true>(L) : moeb_k<WT, MT, 4, 256, false>(L);
-}
-
-template <int WT> hipError_t moeb_r(const MoebLaunch& L) {
+template <int WT> hipError_t moeb_r(const Launch& L) {
     switch (moe_batch_rows(L.a.slots, L.a.n_expert, L.a.K, WT)) {
-        case 2: return moeb_lpr<WT, 2>(L);
-        case 4: return moeb_lpr<WT, 4>(L);
-        case 8: return moeb_lpr<WT, 8>(L);
+        case 2: return moeb_mt<WT, 2>(L);
+        case 4: return moeb_mt<WT, 4>(L);
+        case 8: return moeb_mt<WT, 8>(L);
     }
     return hipErrorInvalidValue;
 }
@@ -138,13 +123,13 @@ template <int WT> hipError_t moeb_r(const MoebLaunch& L) {
 int moe_batch_rows(long slots, int n_expert, int K, int wtype) {
     const long per = (slots + n_expert - 1) / n_expert;
     int r = per <= 2 ? 2 : per <= 4 ? 4 : 8;
-    const size_t row = (size_t)(K / SB_ELEMS) * moeb_rec_bytes(wtype);
+    const size_t row = (size_t)(K / SB_ELEMS) * kq_gemv_rec_dw(wtype) * 4;
     while (r >= MOE_BATCH_MIN_R && r * row > MOE_BATCH_LDS_MAX) r >>= 1;
     return r >= MOE_BATCH_MIN_R ? r : 0;
 }
 
 hipError_t launch_moe_batch(const MoePlanArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
-    const MoebLaunch L{a, st, describe, describe_len};
+    const Launch L{a, st, describe, describe_len};
     if (wtype == QG_TYPE_Q4_K) return moeb_r<QG_TYPE_Q4_K>(L);
     if (wtype == QG_TYPE_Q6_K) return moeb_r<QG_TYPE_Q6_K>(L);
     return hipErrorInvalidValue;

@@ -83,8 +83,6 @@ __device__ __forceinline__ float q6k_glu_product_staged(const uint8_t* __restric
 
 namespace {
 
-constexpr size_t MOE_GLU_LDS_MAX = 160 * 1024;
-
 // Each operation one rounded fp32 operation (the build has contraction off and the correctly rounded division).
 __device__ __forceinline__ float glu(float g, float u, int op) {
     if (op == QG_GLU_REGLU) return (g > 0.0f ? g : 0.0f) * u;
@@ -133,47 +131,28 @@ __global__ __launch_bounds__(WGS) void kq_moe_glu_kernel(const MoeGluArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-struct MoeGluLaunch {
-    const MoeGluArgs& a;
-    hipStream_t st;
-    char* describe;  // qg_moe_glu_config: name the kernel here, launch nothing
-    size_t describe_len;
-};
-
-template <int WT, int LPR, int WGS, bool ONE> hipError_t moe_glu_k(const MoeGluLaunch& L) {
-    constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const size_t lds = (size_t)(L.a.K / SB_ELEMS) * (WT == QG_TYPE_Q4_K ? Q4K_REC_DW : Q6K_REC_DW) * 4;
-    const int grid = (L.a.N + RPB - 1) / RPB;
-    if (L.describe) {
-        describe_line(L.describe, L.describe_len, "moe_glu:%s LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
-                      WT == QG_TYPE_Q4_K ? "q4k_gemv" : "q6k_gemv", LPR, WGS, (int)ONE, grid, L.a.slots, lds);
-        return hipSuccess;
-    }
-    auto k = kq_moe_glu_kernel<WT, LPR, WGS, ONE>;
-    if (lds > 64 * 1024) {
+// The single M = 1 call's LPR, WGS and ONE (kq_gemv_form, qg_kq_launch.hpp), on the decode entry's grid.
+template <int WT> hipError_t moe_glu_launch_t(const MoeLaunch<MoeGluArgs>& L) {
+    return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+        constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
+        const size_t lds = (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        if (L.describe) {
+            describe_line(L.describe, L.describe_len, "moe_glu:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), LPR,
+                          WGS, (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
+            return hipSuccess;
+        }
         static std::atomic<unsigned long long> done;
-        const hipError_t e = set_max_lds_once((const void*)k, (int)MOE_GLU_LDS_MAX, done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(grid, L.a.slots), dim3(WGS), lds, L.st, L.a);
-    return hipGetLastError();
-}
-
-// kq_gemv_launch_lpr / kq_gemv_launch_cfg at MT = 1 (qg_kq_launch.hpp), as the decode entry (qg_moe.hip, moe_kq)
-template <int WT> hipError_t moe_glu_kq(const MoeGluLaunch& L) {
-    const int U = L.a.K / 64;
-    if (U >= 64) return U <= 64 ? moe_glu_k<WT, 64, 1024, true>(L) : moe_glu_k<WT, 64, 1024, false>(L);
-    if (U >= 16) return U <= 16 ? moe_glu_k<WT, 16, 512, true>(L) : moe_glu_k<WT, 16, 512, false>(L);
-    return U <= 4 ? moe_glu_k<WT, 4, 256, true>(L) : moe_glu_k<WT, 4, 256, false>(L);
+        return moe_enqueue(kq_moe_glu_kernel<WT, LPR, WGS, one>, L, RPB, L.a.slots, WGS, lds, done);
+    });
 }
 
 }  // namespace
 
 hipError_t launch_moe_glu(const MoeGluArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
-    const MoeGluLaunch L{a, st, describe, describe_len};
+    const MoeLaunch<MoeGluArgs> L{a, st, describe, describe_len};
     switch (wtype) {
-        case QG_TYPE_Q4_K: return moe_glu_kq<QG_TYPE_Q4_K>(L);
-        case QG_TYPE_Q6_K: return moe_glu_kq<QG_TYPE_Q6_K>(L);
+        case QG_TYPE_Q4_K: return moe_glu_launch_t<QG_TYPE_Q4_K>(L);
+        case QG_TYPE_Q6_K: return moe_glu_launch_t<QG_TYPE_Q6_K>(L);
     }
     return hipErrorInvalidValue;
 }

@@ -235,27 +235,29 @@ MoeForm moe_prefill_form(const MoePlanArgs& a, int wtype) {
     return forms[2];
 }
 
-template <int WT, int TT, int RG>
-hipError_t moe_prefill_k(const MoePlanArgs& a, hipStream_t st, char* describe, size_t describe_len) {
+using Launch = MoeLaunch<MoePlanArgs>;
+
+template <int WT, int TT, int RG> hipError_t moe_prefill_k(const Launch& L) {
+    const MoePlanArgs& a = L.a;
     const int gx = (a.N + 16 * RG - 1) / (16 * RG), gy = (int)moe_max_tiles(a.slots, a.n_expert, 16 * TT);
-    if (describe) {
-        describe_line(describe, describe_len, "moe:%s TT=%d RG=%d KS=%d R=%d grid=%dx%d", WT == QG_TYPE_Q4_K ? "q4k_mmq" : "q6k_mmq",
-                      TT, RG, MMQ_WAVES / RG, 16 * TT, gx, gy);
+    if (L.describe) {
+        describe_line(L.describe, L.describe_len, "moe:%s_mmq TT=%d RG=%d KS=%d R=%d grid=%dx%d", kq_family(WT), TT, RG,
+                      MMQ_WAVES / RG, 16 * TT, gx, gy);
         return hipSuccess;
     }
-    const hipError_t e = launch_moe_plan(a, TT, st);
+    const hipError_t e = launch_moe_plan(a, TT, L.st);
     if (e != hipSuccess) return e;
-    if constexpr (WT == QG_TYPE_Q4_K) hipLaunchKernelGGL((q4k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, st, a);
-    else hipLaunchKernelGGL((q6k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, st, a);
+    if constexpr (WT == QG_TYPE_Q4_K) hipLaunchKernelGGL((q4k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, L.st, a);
+    else hipLaunchKernelGGL((q6k_moe_mmq_kernel<TT, RG>), dim3(gx, gy), dim3(MMQ_WGS), 0, L.st, a);
     return hipGetLastError();
 }
 
-template <int WT> hipError_t moe_prefill_t(const MoePlanArgs& a, hipStream_t st, char* describe, size_t describe_len) {
-    const MoeForm f = moe_prefill_form(a, WT);
-    if (f.rg == 4) return moe_prefill_k<WT, 4, 4>(a, st, describe, describe_len);
-    if (f.tt == 4) return moe_prefill_k<WT, 4, 1>(a, st, describe, describe_len);
-    if (f.tt == 2) return moe_prefill_k<WT, 2, 1>(a, st, describe, describe_len);
-    return moe_prefill_k<WT, 1, 1>(a, st, describe, describe_len);
+template <int WT> hipError_t moe_prefill_t(const Launch& L) {
+    const MoeForm f = moe_prefill_form(L.a, WT);
+    if (f.rg == 4) return moe_prefill_k<WT, 4, 4>(L);
+    if (f.tt == 4) return moe_prefill_k<WT, 4, 1>(L);
+    if (f.tt == 2) return moe_prefill_k<WT, 2, 1>(L);
+    return moe_prefill_k<WT, 1, 1>(L);
 }
 
 }  // namespace
@@ -267,8 +269,9 @@ hipError_t launch_moe_plan(const MoePlanArgs& a, int tt, hipStream_t st) {
 }
 
 hipError_t launch_moe_prefill(const MoePlanArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
-    if (wtype == QG_TYPE_Q4_K) return moe_prefill_t<QG_TYPE_Q4_K>(a, st, describe, describe_len);
-    if (wtype == QG_TYPE_Q6_K) return moe_prefill_t<QG_TYPE_Q6_K>(a, st, describe, describe_len);
+    const Launch L{a, st, describe, describe_len};
+    if (wtype == QG_TYPE_Q4_K) return moe_prefill_t<QG_TYPE_Q4_K>(L);
+    if (wtype == QG_TYPE_Q6_K) return moe_prefill_t<QG_TYPE_Q6_K>(L);
     return hipErrorInvalidValue;
 }
 

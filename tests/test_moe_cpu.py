@@ -12,7 +12,7 @@ import moe_ref as MR
 from moe_ref import ALL_TYPES, Q4_0, Q4_K, Q6_K, Q8_0, ROW_TYPES
 
 P = ctypes.c_void_p
-CONFIG_K = (256, 1024, 2304, 4096, 4352)
+CONFIG_K = (256, 512, 1024, 2304, 4096, 4352)  # 512: LPR = 4 with the unit loop (super-block types)
 
 
 @pytest.fixture(scope="module")

@@ -16,7 +16,7 @@ from moe_glu_ref import REGLU, SWIGLU, bits
 from moe_ref import Q4_K, Q6_K, ROW_TYPES
 
 P = ctypes.c_void_p
-CONFIG_K = (256, 1024, 2304, 4096, 4352)
+CONFIG_K = (256, 512, 1024, 2304, 4096, 4352)  # 512: LPR = 4 with the unit loop (super-block types)
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llama.cpp-quant-gemm_amd", "csrc")
 
 
@@ -140,6 +140,19 @@ def test_glu_config_names_the_decode_entrys_launch(so, t, k):
         f = MR.cfg_fields(cfg)[1]
         assert set(f) == {"LPR", "WGS", "ONE", "grid", "lds"} and f["grid"].endswith("x6")
         assert qg.moe_glu_config(3, 2, n, k, t) == cfg
+
+
+@pytest.mark.parametrize("t", [Q4_K, Q6_K])
+@pytest.mark.parametrize("k", CONFIG_K)
+def test_glu_config_names_the_single_calls_kernel(so, t, k):
+    """The family and LPR / ONE of qg_debug_config(1, N, K, t): each pass of a slot runs the single M = 1 call's
+    instantiation."""
+    import quant_gemm as qg
+    for n in (1, 300, 4096):
+        rc, cfg = glu_cfg(so, 3, 2, n, k, t)
+        single = qg.debug_config(1, n, k, t)
+        assert rc == 0 and MR.kernel_choice(cfg) == MR.kernel_choice(single), (cfg, single)
+        assert MR.cfg_fields(single)[1]["MT"] == "1"
 
 
 def test_glu_config_codes(so):

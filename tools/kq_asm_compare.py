@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
-"""Compare the K-quant kernels of two `make asm` outputs (csrc/Makefile), instantiation by instantiation.
+"""Compare the GEMV / K-quant / expert kernels of two `make asm` outputs (csrc/Makefile), instantiation by instantiation.
 
     python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch and qg_moe_plan by their name and
-integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_plan, qg_gemv and
+qg_gemv_q4_0 .. qg_gemv_q8_0 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
 does not have is skipped there), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
 numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file of the result and every pair
 that differs: REGS where the instruction sequence and the remarks are the parent's and only register numbers moved,
-DIFF otherwise. Exit status 1 if any pair differs."""
+DIFF otherwise; GONE <symbol> for a kernel of the parent the result no longer builds (an instantiation no shape
+reached). Exit status 1 if any pair differs; a kernel only the result has is an error."""
 import re
 import sys
 from pathlib import Path
 
-FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_plan"]
+FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_glu",
+         "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
@@ -78,9 +80,12 @@ def main(parent, result):
             for s in k:
                 assert key(s) not in side[-1], (f, s, "two kernels with one key")
                 side[-1][key(s)] = (f, s, k[s], r[s])
-    assert side[0].keys() == side[1].keys(), sorted(side[0].keys() ^ side[1].keys())
+    assert side[1].keys() <= side[0].keys(), ("only in the result", sorted(side[1].keys() - side[0].keys()))
     bad = 0
     for f in FILES:
+        for kk in sorted(side[0].keys() - side[1].keys()):
+            if side[0][kk][0] == f:
+                print(f"  GONE {side[0][kk][1]}")
         keys = sorted(kk for kk in side[1] if side[1][kk][0] == f)
         same = 0
         for kk in keys:
