@@ -1,7 +1,8 @@
 // qg_gemv_impl.hpp — the GEMV dispatch templates (configuration per shape), instantiated once per
 // weight format in qg_gemv_<fmt>.hip so the formats compile in parallel; qg_gemv.hip holds the
-// format switch (gemv_eligible, launch_gemv). The choice itself is gemv_form below, which the
-// expert-indexed launch (qg_moe.hip) visits too.
+// format switch (gemv_eligible, launch_gemv). The choice of the form (BPL, LPR, WGS, PRE) is gemv_form below, which the
+// expert-indexed launch (qg_moe.hip) visits too; the choice among the form's kernels is gemv_pick (qg_gemv_kernel.hpp),
+// whose GemvPick the untemplated gemv_run (qg_gemv.hip) describes, writes into a graph node or launches.
 #pragma once
 #include "qg_gemv_kernel.hpp"
 

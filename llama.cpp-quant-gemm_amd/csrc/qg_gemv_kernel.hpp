@@ -679,7 +679,7 @@ inline bool group_affine_class_enabled(bool one, int MT, bool small_n, int count
 }
 
 // gemv_body's ONEU for rows of `units` units on `lpr` lanes: 1, one unit per lane; 2 / 4, the loop-free multi-unit form
-// of Q4_0 M = 1 single launches; 0, the unit loop. gemv_launch and the expert-indexed launch (qg_moe.hip) both ask here.
+// of Q4_0 M = 1 single launches; 0, the unit loop. gemv_pick and the expert-indexed launch (qg_moe.hip) both ask here.
 // profiles/r05_tuning/r5zd_ab.txt, unit loop -> multi-unit: Q4_0 M = 1 K = 14336 7.69 -> 7.46 us, K = 11008
 // 6.32 -> 6.17, K = 8192 5.02 -> 4.78; slower for M = 2..4 (8.93 -> 9.45 at M = 2), Q4_1 (8.02 -> 9.50) and
 // Q8_0 (12.37 -> 12.53), which keep the loop
@@ -700,161 +700,6 @@ constexpr GemvSmallWg gemv_small_wg(int wgs, int mt, int wdiv, int tpw) {
     return s.wgs < wgs && s.wgs >= 64 ? s : GemvSmallWg{0, 0};
 }
 
-template <int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN = AIN_Q8_1, bool NT = false, bool PRE = (MT <= 2)>
-hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
-    constexpr int RPB = (WGS / 64) * (64 / LPR);
-    constexpr bool NU_OK = gemv_nu_ok<F, MT>;
-    const size_t lds = gemv_lds_bytes<F, BPL>(g.M, g.K);
-    const int nu = gemv_unit_form<F, MT>(g.K / QK / BPL, LPR);
-    const bool one = nu == 1;
-    // M = 1, one product, unit output stride: the minimal-argument entry (gemv1_kernel)
-    const bool m1 = MT == 1 && PRE && !NT && g.M == 1 && g.batch == 1 && g.ldc_n == 1;
-    const bool shrt = !m1 && !NT && g.batch == 1 && g.ldc_m <= INT32_MAX && g.ldc_n <= INT32_MAX;
-    // the ONEU the chosen entry launches: the short entry takes the multi-unit form only when
-    // NU_OK && MT > 1, otherwise its loop (ONEU 0) or the one-unit form
-    const int oneu = m1 ? nu : shrt ? ((nu > 1 && !(NU_OK && MT > 1)) ? 0 : nu) : (int)one;
-    if (g.group && (SUMI || AIN != AIN_Q8_1 || NT || MT > 4)) return hipErrorInvalidValue;  // no grouped form here
-    // the kernel derives its tile count from N (gemv_body): the grid must be exactly that
-    auto grid_x = [&](int rpw) {
-        const int gx = (g.N + rpw - 1) / rpw;
-        assert(gx == gemv_tiles(g.N, rpw));
-        return gx;
-    };
-    const int grid = grid_x(RPB);
-    // the strided batch standing for an affine group (below): the launch as a graph node's parameters
-    auto fill_batch = [&](const void* fn, dim3 grd, int block) {
-        GemvNodeFill* nf = g.node_fill;
-        nf->p = hipKernelNodeParams{};
-        nf->set_batch(g);
-        nf->one = one ? 1 : 0;
-        nf->p.func = const_cast<void*>(fn);
-        nf->p.gridDim = grd;
-        nf->p.blockDim = dim3(block);
-        nf->p.sharedMemBytes = (unsigned)lds;
-        nf->p.kernelParams = nf->argv;
-        return hipSuccess;
-    };
-    if (g.describe && !g.group && !g.affine) {  // qg_debug_config: name the instantiation instead of launching it
-        describe_kernel(g, "gemv F=%d MT=%d BPL=%d LPR=%d WGS=%d AIN=%d NT=%d PRE=%d ONEU=%d SIG=%s grid=%dx%d", F, MT, BPL,
-                        LPR, WGS, AIN, (int)NT, (int)(one ? PRE : (PRE && MT <= (shrt && !oneu ? gemv_pre_mt<F> : 2))), oneu,
-                        m1 ? "m1" : shrt ? "short" : "full",
-                        grid, g.batch);
-        return hipSuccess;
-    }
-    if constexpr (!SUMI && AIN == AIN_Q8_1 && !NT && MT <= 4) {  // (AUTO sends only M <= 4 to the GEMV)
-        if (g.group) {  // grouped launch (qg_gemm_w4a8_grouped): blockIdx.y = item
-            const GemvGroup& grp0 = *static_cast<const GemvGroup*>(g.group);
-            // An affine group (qg_group_affine.hpp) is a strided batch: it takes the kernel and grid
-            // qg_gemm_w4a8_strided_batched launches for the same items (below), whose arguments all sit in
-            // SGPRs — no descriptor load ahead of the weight stream. Same body, same bits.
-            affine::Strides as;
-            const int amode = group_affine_mode();
-            if (amode && g.affine >= 0 && grp0.count >= 2 && group_affine_class_enabled(one, MT, g.N <= 16 * device_cus(), grp0.count, amode) &&
-                affine::group_affine(grp0.it, grp0.count, 3, 15, &as)) {
-                GemmArgs b = g;
-                b.group = nullptr;
-                b.affine = 1;
-                b.A = grp0.it[0].A; b.B = grp0.it[0].B; b.C = grp0.it[0].C;
-                b.N = grp0.it[0].N; b.ldc_m = grp0.it[0].ldc; b.ldc_n = 1;
-                b.batch = grp0.count;
-                b.sA = (long)as.a; b.sB = (long)as.b; b.sC = (long)(as.c / 4);
-                return gemv_launch<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE>(b, st);
-            }
-            auto go = [&](auto GWc, auto TPc) -> hipError_t {
-                constexpr int GW = decltype(GWc)::value, TP = decltype(TPc)::value;
-                constexpr int RPBG = (GW / 64) * (64 / LPR);
-                const int rpw = one ? RPBG * TP : RPBG;  // rows per workgroup
-                int tiles = 0, tmin = INT32_MAX;
-                for (int i = 0; i < grp0.count; ++i) {
-                    const int t = (grp0.it[i].N + rpw - 1) / rpw;
-                    tiles = std::max(tiles, t);
-                    tmin = std::min(tmin, t);
-                }
-                const int full = tiles == tmin ? 1 : 0;
-                if (g.describe) {  // qg_group_config: name the instantiation instead of launching it
-                    describe_kernel(g, "gemvg F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=%d TPW=%d full=%d grid=%dx%d", F, MT,
-                                    BPL, LPR, GW, (int)(one ? PRE : PRE && MT <= 2), (int)one, one ? TP : 1, full, tiles,
-                                    grp0.count);
-                    return hipSuccess;
-                }
-                auto kg = one ? gemvg_kernel<F, MT, BPL, LPR, GW, PRE, true, TP>
-                              : gemvg_kernel<F, MT, BPL, LPR, GW, PRE && (MT <= 2), false>;
-                if (lds > 64 * 1024) {
-                    hipError_t e = hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (e != hipSuccess) return e;
-                }
-                if (g.node_fill) g.node_fill->p = hipKernelNodeParams{};  // func == nullptr: nothing to launch
-                if (tiles == 0 || grp0.count == 0) return hipSuccess;
-                // the launch as a graph node's parameters (the capture-time merge), or launched from them here
-                GemvNodeFill local;
-                GemvNodeFill* nf = g.node_fill ? g.node_fill : &local;
-                nf->p = hipKernelNodeParams{};
-                nf->grp = grp0;
-                nf->grp.full = full;
-                nf->flags = (full ? GEMVG_FULL : 0) | (tiles <= 512 ? GEMVG_XCD : 0);
-                nf->tiles = tiles;
-                nf->argv[0] = &nf->grp.M; nf->argv[1] = &nf->grp.K; nf->argv[2] = &nf->flags; nf->argv[3] = &nf->tiles;
-                nf->argv[4] = nf->grp.it;
-                nf->one = one ? 1 : 0;
-                nf->affine = 0;
-                nf->p.func = (void*)kg;
-                nf->p.gridDim = dim3(tiles, grp0.count);
-                nf->p.blockDim = dim3(GW);
-                nf->p.sharedMemBytes = (unsigned)lds;
-                nf->p.kernelParams = nf->argv;
-                if (g.node_fill) return hipSuccess;
-                return hipLaunchKernel(nf->p.func, nf->p.gridDim, nf->p.blockDim, nf->argv, lds, st);
-            };
-            // workgroups of WGS / QG_GEMVG_WDIV threads while the largest item's rows fit one round of
-            // full-size workgroups (<= 256): twice as many resident per CU, so one workgroup's descriptor
-            // load and activation staging overlap another's weight stream (profiles/r04_tuning/
-            // ab_grouped_wgs_r4g2.txt, 64 items per launch, N = K = 4096: Q4_0 M = 1 1.541 -> 1.509 us per
-            // GEMV, M = 2 1.853 -> 1.688, M = 4 2.705 -> 2.494, Q8_0 2.885 -> 2.767; N = 11008 (344 tiles)
-            // 3.92 -> 4.01 with them, so larger items keep full-size workgroups)
-            constexpr GemvSmallWg SG = gemv_small_wg(WGS, MT, QG_GEMVG_WDIV, QG_GEMVG_TPW);
-            if constexpr (SG.wgs > 0) {
-                const int rpw_full = one ? RPB * QG_GEMVG_TPW : RPB;
-                int nmax = 0;
-                for (int i = 0; i < grp0.count; ++i) nmax = std::max(nmax, grp0.it[i].N);
-                if ((nmax + rpw_full - 1) / rpw_full <= device_cus())
-                    return go(std::integral_constant<int, SG.wgs>{}, std::integral_constant<int, SG.tpw>{});
-            }
-            return go(std::integral_constant<int, WGS>{}, std::integral_constant<int, QG_GEMVG_TPW>{});
-        }
-    }
-    if constexpr (MT == 1 && PRE && !NT) if (m1) {  // (no gemv1_kernel from the M tiles that cannot launch it)
-        auto k1 =nu == 1 ? gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 1> : gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 0>;
-        if constexpr (NU_OK) {
-            if (nu == 2) k1 = gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 2>;
-            if (nu == 4) k1 = gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, 4>;
-        }
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        void* out = SUMI ? (void*)g.sumi : (void*)g.C;
-        hipLaunchKernelGGL(k1, dim3(grid), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.N, g.K, out);
-        return hipGetLastError();
-    }
-    // one product with 32-bit output strides: the short-argument entry (gemvs_kernel)
-    if (shrt) {
-        auto ks = one ? gemvs_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, PRE, 1>
-                      : gemvs_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, PRE && (MT <= gemv_pre_mt<F>), 0>;
-        if constexpr (NU_OK && MT > 1) {
-            if (nu == 2) ks = gemvs_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, PRE && (MT <= 2), 2>;
-            if (nu == 4) ks = gemvs_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, PRE && (MT <= 2), 4>;
-        }
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        void* out = SUMI ? (void*)g.sumi : (void*)g.C;
-        hipLaunchKernelGGL(ks, dim3(grid), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, out,
-                           (int)g.ldc_m, (int)g.ldc_n);
-        return hipGetLastError();
-    }
-    // PRE beyond MT = 2 only in the loop-free form (with the unit loop it spills at MT = 4); a strided
-    // batch of loop-free GEMVs takes QG_GEMV_TPW row tiles per workgroup (same per-row arithmetic)
 // A strided batch of loop-free GEMVs whose N fits one round of full-size workgroups runs half-size
 // ones, as the grouped launch (profiles/r04_tuning/ab_batched_wgs_r4b.txt, 64 products per launch,
 // N = K = 4096: Q4_0 M = 1 1.526 -> 1.478 us per GEMV, M = 2 1.772 -> 1.641, M = 4 3.32 -> 2.76,
@@ -862,45 +707,120 @@ hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
 #ifndef QG_GEMVB_WDIV
 #define QG_GEMVB_WDIV 2
 #endif
-    constexpr GemvSmallWg SB = gemv_small_wg(WGS, MT, QG_GEMVB_WDIV, QG_GEMV_TPW);
-    if constexpr (SB.wgs > 0 && !SUMI && !NT) {
-        constexpr int GW = SB.wgs, TPB = SB.tpw, RPBB = (GW / 64) * (64 / LPR) * TPB;
-        if (one && g.batch > 1 && grid <= device_cus()) {
-            if (g.describe) {  // (an affine group: qg_group_config)
-                describe_kernel(g, "gemvb F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=1 TPW=%d grid=%dx%d", F, MT, BPL, LPR, GW,
-                                (int)PRE, TPB, grid_x(RPBB), g.batch);
-                return hipSuccess;
+
+// One instantiation as a GemvPick (qg_kernels.hpp): the kernel's address next to the constants that made it, so what
+// gemv_run prints cannot differ from what it launches; `done` is this instantiation's lds_opt_in mask.
+template <int SIG, int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN, bool NT, bool PRE, int ONEU, int TPW>
+GemvPick gemv_pick_of() {
+    static_assert(SIG != GEMV_SIG_M1 || (MT == 1 && PRE), "gemv1_kernel is the M = 1 tile with PRE");
+    static std::atomic<unsigned long long> done;
+    GemvPick p = {};
+    if constexpr (SIG == GEMV_SIG_M1) p.fn = (const void*)gemv1_kernel<F, BPL, LPR, WGS, SUMI, AIN, ONEU>;
+    else if constexpr (SIG == GEMV_SIG_SHORT) p.fn = (const void*)gemvs_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, PRE, ONEU>;
+    else if constexpr (SIG == GEMV_SIG_FULL) p.fn = (const void*)gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE, ONEU, TPW>;
+    else p.fn = (const void*)gemvg_kernel<F, MT, BPL, LPR, WGS, PRE, ONEU, TPW>;
+    p.lds_done = &done; p.sig = SIG; p.family = SIG == GEMV_SIG_GROUP ? "gemvg" : "gemv";
+    p.F = F; p.MT = MT; p.BPL = BPL; p.LPR = LPR; p.WGS = WGS; p.AIN = AIN; p.NT = NT; p.PRE = PRE; p.ONEU = ONEU; p.TPW = TPW;
+    p.rpw = (WGS / 64) * (64 / LPR) * TPW;
+    return p;
+}
+
+// The row GEMV's kernel, grid and LDS for one call: every rule that chooses among the instantiations of (F, MT, BPL, LPR,
+// WGS, PRE) — gemv_form's answer, qg_gemv_impl.hpp — is here and nowhere else. gemv_run (qg_gemv.hip) describes, fills
+// or launches what it is handed.
+template <int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN, bool NT, bool PRE>
+GemvPick gemv_pick(const GemmArgs& g) {
+    constexpr int RPB = (WGS / 64) * (64 / LPR);
+    constexpr bool NU_OK = gemv_nu_ok<F, MT>;
+    // PRE beyond MT = 2 only in the loop-free forms (with the unit loop it spills at MT = 4); the short entry's loop
+    // up to gemv_pre_mt<F>
+    constexpr std::bool_constant<PRE> pre{};
+    constexpr std::bool_constant<(PRE && MT <= 2)> pre2{};
+    constexpr ic<0> i0{}; constexpr ic<1> i1{}; constexpr ic<WGS> wgs{};
+    auto k = [](auto sig, auto gw, auto pr, auto oneu, auto tpw) { return gemv_pick_of<sig, F, MT, BPL, LPR, gw, SUMI, AIN, NT, pr, oneu, tpw>(); };
+    const int nu = gemv_unit_form<F, MT>(g.K / QK / BPL, LPR);
+    const bool one = nu == 1;
+    GemvPick p = {};
+    if constexpr (!SUMI && AIN == AIN_Q8_1 && !NT && MT <= 4) {  // (AUTO sends only M <= 4 to the GEMV)
+        if (g.group) {  // grouped launch (qg_gemm_w4a8_grouped): blockIdx.y = item
+            const GemvGroup& grp = *static_cast<const GemvGroup*>(g.group);
+            // An affine group (qg_group_affine.hpp) is a strided batch: it takes the kernel and grid
+            // qg_gemm_w4a8_strided_batched launches for the same items (below), whose arguments all sit in
+            // SGPRs — no descriptor load ahead of the weight stream. Same body, same bits.
+            affine::Strides as;
+            const int amode = group_affine_mode();
+            if (amode && g.affine >= 0 && grp.count >= 2 && group_affine_class_enabled(one, MT, g.N <= 16 * device_cus(), grp.count, amode) &&
+                affine::group_affine(grp.it, grp.count, 3, 15, &as)) {
+                GemmArgs b = g;
+                b.group = nullptr; b.batch = grp.count;
+                b.A = grp.it[0].A; b.B = grp.it[0].B; b.C = grp.it[0].C;
+                b.N = grp.it[0].N; b.ldc_m = grp.it[0].ldc; b.ldc_n = 1;
+                b.sA = (long)as.a; b.sB = (long)as.b; b.sC = (long)(as.c / 4);
+                p = gemv_pick<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE>(b);
+                p.family = "gemvb"; p.affine = 1;
+                return p;
             }
-            auto kb = gemv_kernel<F, MT, BPL, LPR, GW, SUMI, AIN, NT, PRE, true, TPB>;
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
-            if (g.affine && g.node_fill) return fill_batch((const void*)kb, dim3(grid_x(RPBB), g.batch), GW);
-            hipLaunchKernelGGL(kb, dim3(grid_x(RPBB), g.batch), dim3(GW), lds, st, (const uint32_t*)g.A,
-                               (const uint8_t*)g.B, g.sA, g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, g.sumi);
-            return hipGetLastError();
+            int nmax = 0, nmin = INT32_MAX;
+            for (int i = 0; i < grp.count; ++i) nmax = std::max(nmax, grp.it[i].N), nmin = std::min(nmin, grp.it[i].N);
+            auto kg = [&](auto gw, auto tp) { return one ? k(ic<GEMV_SIG_GROUP>{}, gw, pre, i1, tp) : k(ic<GEMV_SIG_GROUP>{}, gw, pre2, i0, i1); };
+            p = kg(wgs, ic<QG_GEMVG_TPW>{});
+            // workgroups of WGS / QG_GEMVG_WDIV threads while the largest item's rows fit one round of
+            // full-size workgroups (<= 256): twice as many resident per CU, so one workgroup's descriptor
+            // load and activation staging overlap another's weight stream (profiles/r04_tuning/
+            // ab_grouped_wgs_r4g2.txt, 64 items per launch, N = K = 4096: Q4_0 M = 1 1.541 -> 1.509 us per
+            // GEMV, M = 2 1.853 -> 1.688, M = 4 2.705 -> 2.494, Q8_0 2.885 -> 2.767; N = 11008 (344 tiles)
+            // 3.92 -> 4.01 with them, so larger items keep full-size workgroups)
+            constexpr GemvSmallWg SG = gemv_small_wg(WGS, MT, QG_GEMVG_WDIV, QG_GEMVG_TPW);
+            if constexpr (SG.wgs > 0)
+                if (gemv_tiles(nmax, p.rpw) <= device_cus()) p = kg(ic<SG.wgs>{}, ic<SG.tpw>{});
+            // grid.x = the largest item's tiles; full: the smallest item has as many (an empty group: never)
+            p.grid = dim3(gemv_tiles(nmax, p.rpw), grp.count);
+            p.full = p.grid.x == (unsigned)gemv_tiles(nmin, p.rpw);
+            p.flags = (p.full ? GEMVG_FULL : 0) | (p.grid.x <= 512 ? GEMVG_XCD : 0);
         }
     }
-    constexpr bool tpw_ok = !SUMI && !NT && QG_GEMV_TPW > 1;
-    const bool multi = tpw_ok && one && g.batch > 1;
-    const int gx = multi ? grid_x(RPB * QG_GEMV_TPW) : grid;
-    if (g.describe) {  // (an affine group: qg_group_config)
-        describe_kernel(g, "gemvb F=%d MT=%d BPL=%d LPR=%d WGS=%d PRE=%d ONEU=%d TPW=%d grid=%dx%d", F, MT, BPL, LPR, WGS,
-                        (int)(one ? PRE : PRE && MT <= 2), (int)one, multi ? QG_GEMV_TPW : 1, gx, g.batch);
-        return hipSuccess;
+    // M = 1, one product, unit output stride: the minimal-argument entry (gemv1_kernel), which alone takes Q4_0's
+    // loop-free multi-unit forms (no gemv1_kernel from the M tiles that cannot launch it)
+    const bool single = !NT && g.batch == 1;
+    if constexpr (MT == 1 && PRE && !NT) if (!p.fn && g.M == 1 && single && g.ldc_n == 1) {
+        p = one ? k(ic<GEMV_SIG_M1>{}, wgs, pre, i1, i1) : k(ic<GEMV_SIG_M1>{}, wgs, pre, i0, i1);
+        if constexpr (NU_OK) {
+            if (nu == 2) p = k(ic<GEMV_SIG_M1>{}, wgs, pre, ic<2>{}, i1);
+            if (nu == 4) p = k(ic<GEMV_SIG_M1>{}, wgs, pre, ic<4>{}, i1);
+        }
     }
-    auto kfn = multi ? gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE, true, tpw_ok ? QG_GEMV_TPW : 1>
-             : one   ? gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE, true>
-                     : gemv_kernel<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE && (MT <= 2), false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+    // one product with 32-bit output strides: the short-argument entry (gemvs_kernel). It takes the multi-unit forms only
+    // when NU_OK && MT > 1, otherwise its loop or the one-unit form
+    if (!p.fn && single && g.ldc_m <= INT32_MAX && g.ldc_n <= INT32_MAX) {
+        p = one ? k(ic<GEMV_SIG_SHORT>{}, wgs, pre, i1, i1)
+                : k(ic<GEMV_SIG_SHORT>{}, wgs, std::bool_constant<(PRE && MT <= gemv_pre_mt<F>)>{}, i0, i1);
+        if constexpr (NU_OK && MT > 1) {
+            if (nu == 2) p = k(ic<GEMV_SIG_SHORT>{}, wgs, pre2, ic<2>{}, i1);
+            if (nu == 4) p = k(ic<GEMV_SIG_SHORT>{}, wgs, pre2, ic<4>{}, i1);
+        }
     }
-    if (g.affine && g.node_fill) return fill_batch((const void*)kfn, dim3(gx, g.batch), WGS);
-    hipLaunchKernelGGL(kfn, dim3(gx, g.batch), dim3(WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.sA,
-                       g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, g.sumi);
-    return hipGetLastError();
+    // the general entry (gemv_kernel): a strided batch of loop-free GEMVs takes QG_GEMV_TPW row tiles per workgroup (same
+    // per-row arithmetic), and half-size workgroups (QG_GEMVB_WDIV, above) while N fits one round of full-size ones
+    if (!p.fn) {
+        constexpr bool tpw_ok = !SUMI && !NT && QG_GEMV_TPW > 1;
+        const bool many = one && g.batch > 1;
+        p = many ? k(ic<GEMV_SIG_FULL>{}, wgs, pre, i1, ic<(tpw_ok ? QG_GEMV_TPW : 1)>{})
+          : one  ? k(ic<GEMV_SIG_FULL>{}, wgs, pre, i1, i1)
+                 : k(ic<GEMV_SIG_FULL>{}, wgs, pre2, i0, i1);
+        constexpr GemvSmallWg SB = gemv_small_wg(WGS, MT, QG_GEMVB_WDIV, QG_GEMV_TPW);
+        if constexpr (SB.wgs > 0 && !SUMI && !NT)
+            if (many && gemv_tiles(g.N, RPB) <= device_cus()) p = k(ic<GEMV_SIG_FULL>{}, ic<SB.wgs>{}, pre, i1, ic<SB.tpw>{});
+    }
+    if (p.sig != GEMV_SIG_GROUP) p.grid = dim3((g.N + p.rpw - 1) / p.rpw, g.batch);  // (gemv_run checks it: gemv_tiles)
+    p.lds = gemv_lds_bytes<F, BPL>(g.M, g.K);
+    p.one = one ? 1 : 0; p.a = g;
+    return p;
+}
+
+template <int F, int MT, int BPL, int LPR, int WGS, bool SUMI, int AIN = AIN_Q8_1, bool NT = false, bool PRE = (MT <= 2)>
+hipError_t gemv_launch(const GemmArgs& g, hipStream_t st) {
+    if (g.group && (SUMI || AIN != AIN_Q8_1 || NT || MT > 4)) return hipErrorInvalidValue;  // no grouped form here
+    return gemv_run(gemv_pick<F, MT, BPL, LPR, WGS, SUMI, AIN, NT, PRE>(g), st);
 }
 
 }  // namespace qg

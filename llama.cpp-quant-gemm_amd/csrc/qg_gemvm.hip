@@ -311,14 +311,12 @@ template <int F, int NU, int MP> hipError_t gemvm_launch(const GemmArgs& g, hipS
         describe_kernel(g, "gemvm F=%d NU=%d MP=%d W=%d TA=%d grid=%d", F, NU, MP, W, (int)ta, grid);
         return hipSuccess;
     }
-    if (W > 16 || lds > 160 * 1024) return hipErrorInvalidValue;
+    if (W > 16 || lds > MAX_LDS_BYTES) return hipErrorInvalidValue;
     auto k = g.sumi ? (ta ? gemvm_kernel<F, NU, MP, true, true> : gemvm_kernel<F, NU, MP, true, false>)
                     : (ta ? gemvm_kernel<F, NU, MP, false, true> : gemvm_kernel<F, NU, MP, false, false>);
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> done[4] = {};
-        const hipError_t e = set_max_lds_once((const void*)k, 160 * 1024, done[(g.sumi ? 1 : 0) + (ta ? 2 : 0)]);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> done[4] = {};
+    const hipError_t e = lds_opt_in((const void*)k, lds, done[(g.sumi ? 1 : 0) + (ta ? 2 : 0)]);
+    if (e != hipSuccess) return e;
     void* o = g.sumi ? (void*)g.sumi : (void*)g.C;
     hipLaunchKernelGGL(k, dim3(grid), dim3(W * 64), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, o,
                        (int)g.ldc_m, (int)g.ldc_n);

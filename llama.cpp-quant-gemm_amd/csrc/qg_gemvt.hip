@@ -224,11 +224,9 @@ template <int F, int MT, int R, int NU> hipError_t gemvt_launch(const GemmArgs& 
     if (W > 16) return hipErrorInvalidValue;
     auto k = g.sumi ? (ta ? gemvt_kernel<F, MT, R, NU, true, true> : gemvt_kernel<F, MT, R, NU, true, false>)
                     : (ta ? gemvt_kernel<F, MT, R, NU, false, true> : gemvt_kernel<F, MT, R, NU, false, false>);
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> done[4] = {};
-        const hipError_t e = set_max_lds_once((const void*)k, 160 * 1024, done[(g.sumi ? 1 : 0) + (ta ? 2 : 0)]);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> done[4] = {};
+    const hipError_t e = lds_opt_in((const void*)k, lds, done[(g.sumi ? 1 : 0) + (ta ? 2 : 0)]);
+    if (e != hipSuccess) return e;
     void* o = g.sumi ? (void*)g.sumi : (void*)g.C;
     hipLaunchKernelGGL(k, dim3(grid), dim3(W * 64), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, o,
                        (int)g.ldc_m, (int)g.ldc_n);

@@ -1,4 +1,4 @@
-// qg_group_affine.hpp — is a grouped GEMV launch a strided batch? (gemv_launch, qg_gemv_kernel.hpp)
+// qg_group_affine.hpp — is a grouped GEMV launch a strided batch? (gemv_pick, qg_gemv_kernel.hpp)
 //
 // A group (GemvGroup, qg_kernels.hpp) is AFFINE when its items share N and ldc and their A, B and C pointers
 // each advance by one constant byte stride from item to item: item i = item 0 + i * stride. Such a group is

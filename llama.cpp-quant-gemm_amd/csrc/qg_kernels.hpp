@@ -44,11 +44,10 @@ struct GemmArgs {
                                  // shared, N = the largest item's
     char* describe = nullptr;    // qg_debug_config: the leaf launcher writes the kernel it would
     size_t describe_len = 0;     // launch here (family + template parameters) and launches nothing
-    struct GemvNodeFill* node_fill = nullptr;  // with `group`: the grouped launcher fills this (kernel, grid,
-                                 // block, LDS, argument) and launches nothing — the capture-time merge
-    int affine = 0;              // 1, set by the grouped launcher: this strided batch stands for an affine group
-                                 // (qg_group_affine.hpp); it may fill node_fill, and describe names the batch kernel.
-                                 // -1, with `group`: keep the grouped kernel even for an affine group
+    struct GemvNodeFill* node_fill = nullptr;  // with `group`: gemv_run fills this (kernel, grid, block, LDS,
+                                 // arguments) and launches nothing — the capture-time merge
+    int affine = 0;              // -1, with `group`: keep the grouped kernel even for an affine group (qg_group_affine.hpp;
+                                 // the capture-time merge, after a node refused the strided batch's kernel)
 };
 
 // Host-side descriptor of a grouped GEMV launch (qg_gemm_w4a8_grouped). gemvg_kernel takes M, K, a flags word
@@ -81,27 +80,43 @@ inline GemmArgs group_args(const GemvGroup& grp, int wtype) {
     g.group = &grp;
     return g;
 }
-// What the grouped launcher would launch (GemmArgs::node_fill), as the parameters of a graph kernel
-// node: the capture-time merge (qg_capture_fuse.hip) installs them with hipGraphKernelNodeSetParams.
+// A row GEMV launch as the parameters of a graph kernel node (gemv_run's fill, qg_gemv.hip): every launch is issued
+// from one, and with GemmArgs::node_fill the capture-time merge (qg_capture_fuse.hip) gets it instead and installs it
+// with hipGraphKernelNodeSetParams.
 struct GemvNodeFill {
     hipKernelNodeParams p;  // p.func == nullptr: nothing to launch; p.kernelParams = argv
     GemvGroup grp;          // the group, `full` set for the launch's grid; gemvg_kernel's item table is grp.it
     int flags, tiles;       // gemvg_kernel(M, K, flags, tiles, items): grp.M, grp.K, these, grp.it
-    // an affine group (qg_group_affine.hpp): gemv_kernel(A, B, sA, sB, M, N, K, C, sC, ldc_m, ldc_n, sumi)
-    struct Batch {
+    // one product, a strided batch or an affine group (qg_group_affine.hpp): gemv_kernel(A, B, sA, sB, M, N, K, C, sC, ldc_m,
+    // ldc_n, sumi), gemvs_kernel(A, B, M, N, K, out, ldc_m32, ldc_n32), gemv1_kernel(A, B, N, K, out)
+    struct Rows {
         const uint32_t* A; const uint8_t* B; long sA, sB; int M, N, K; float* C; long sC, ldc_m, ldc_n; int32_t* sumi;
-    } sb;
+        void* out; int ldc_m32, ldc_n32;
+    } r;
     void* argv[12];
     int one;                // the loop-free one-unit form (K/32 units fit the row's lanes)
-    int affine;             // the launch is the strided batch's kernel
-    // argv for gemv_kernel from the batch's GemmArgs
-    void set_batch(const GemmArgs& g) {
-        sb = Batch{(const uint32_t*)g.A, (const uint8_t*)g.B, g.sA, g.sB, g.M, g.N, g.K, g.C, g.sC, g.ldc_m, g.ldc_n, nullptr};
-        void* a[12] = {&sb.A, &sb.B, &sb.sA, &sb.sB, &sb.M, &sb.N, &sb.K, &sb.C, &sb.sC, &sb.ldc_m, &sb.ldc_n, &sb.sumi};
-        for (int i = 0; i < 12; ++i) argv[i] = a[i];
-        affine = 1;
-    }
+    int affine;             // a group launched as the strided batch's kernel
 };
+
+// The row GEMV's choice for one call (gemv_pick, qg_gemv_kernel.hpp) with everything its three consumers need (gemv_run,
+// qg_gemv.hip: describe it, fill a graph node with it, launch it). WGS .. TPW are the constants that instantiated `fn`
+// (gemv_pick_of), so the line qg_debug_config / qg_group_config print names the kernel that runs.
+enum : int { GEMV_SIG_M1, GEMV_SIG_SHORT, GEMV_SIG_FULL, GEMV_SIG_GROUP };  // the arguments of gemv1_ / gemvs_ / gemv_ / gemvg_kernel
+struct GemvPick {
+    const void* fn;                              // nullptr: no rule has picked yet
+    std::atomic<unsigned long long>* lds_done;   // fn's lds_opt_in mask
+    int sig;
+    const char* family;  // "gemv" one product or a strided batch, "gemvb" the batch an affine group became, "gemvg" grouped
+    int F, MT, BPL, LPR, WGS, AIN, NT, PRE, ONEU, TPW;
+    int rpw;             // rows per workgroup
+    dim3 grid;           // x: row tiles (gemv_tiles of the largest N); y: products
+    size_t lds;
+    int full, flags;     // grouped: every item has grid.x row tiles; gemvg_kernel's flags word
+    int one, affine;     // as GemvNodeFill
+    GemmArgs a;          // the call; an affine group's: the strided batch it became
+};
+// describe (a.describe), fill (a.node_fill) or launch
+hipError_t gemv_run(const GemvPick& p, hipStream_t st);
 
 // The affine route of grouped launches (qg_set_group_affine): 0 off, 1 the measured classes, 2 every class.
 int group_affine_mode();
@@ -118,6 +133,14 @@ inline hipError_t set_max_lds_once(const void* fn, int bytes, std::atomic<unsign
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess && bit) done.fetch_or(bit, std::memory_order_acq_rel);
     return e;
+}
+
+// The dynamic LDS a gfx950 workgroup can ask for, and the opt-in a launch above 64 KiB needs. The cap is the fixed
+// maximum, not the call's size: one instantiation serves many (M, K), so "once, with the first call's size" would leave a
+// later, larger call above its kernel's cap.
+constexpr size_t MAX_LDS_BYTES = 160 * 1024;
+inline hipError_t lds_opt_in(const void* kernel, size_t lds, std::atomic<unsigned long long>& done) {
+    return lds > 64 * 1024 ? set_max_lds_once(kernel, (int)MAX_LDS_BYTES, done) : hipSuccess;
 }
 
 // Compute units of the current device (hipDeviceAttributeMultiprocessorCount, cached per device; 256 on a

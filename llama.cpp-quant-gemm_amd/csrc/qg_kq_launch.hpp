@@ -26,13 +26,6 @@ constexpr const char* kq_family(int wtype) { return wtype == QG_TYPE_Q4_K ? "q4k
 // ---- decode GEMV (M <= 8) ------------------------------------------------------------------------------------
 template <class F> inline size_t kq_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / SB_ELEMS) * F::REC_DW * 4; }
 
-// The dynamic LDS a gfx950 workgroup can ask for, and the opt-in a launch above 64 KiB needs: once per (kernel
-// instantiation, device), `done` that instantiation's mask (set_max_lds_once).
-constexpr size_t MAX_LDS_BYTES = 160 * 1024;
-inline hipError_t lds_opt_in(const void* kernel, size_t lds, std::atomic<unsigned long long>& done) {
-    return lds > 64 * 1024 ? set_max_lds_once(kernel, (int)MAX_LDS_BYTES, done) : hipSuccess;
-}
-
 // The decode GEMV's instantiation for K, chosen here and nowhere else: fn(LPR, WGS, ONE) as std::integral_constant /
 // bool_constant. The single call below and the expert entries (qg_moe{,_glu,_batch}.hip) launch what it hands them.
 // Lanes per row: the largest of 4 / 16 / 64 that the row's K / 64 units fill. K >= 4096: a wave per row, 16

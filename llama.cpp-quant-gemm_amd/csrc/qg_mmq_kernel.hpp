@@ -607,11 +607,9 @@ hipError_t mmq_launch(const GemmArgs& g, hipStream_t st) {
     if constexpr (T) k = (const void*)mmqt_kernel<F, BN, TT, W, SUMI, P16, NB, LAY, AW>;
     else if constexpr (SHORT) k = (const void*)mmq1_kernel<F, BN, TT, W, SUMI, P16, NB>;
     else k = (const void*)mmq_kernel<F, BN, TT, W, SUMI, P16, NB>;
-    if (G::LDS > 64 * 1024) {
-        static std::atomic<unsigned long long> attr_done{0};
-        const hipError_t e = set_max_lds_once(k, 160 * 1024, attr_done);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    const hipError_t e = lds_opt_in(k, G::LDS, attr_done);
+    if (e != hipSuccess) return e;
     void* out = SUMI ? (void*)g.sumi : (void*)g.C;
     if constexpr (T) {
         hipLaunchKernelGGL((mmqt_kernel<F, BN, TT, W, SUMI, P16, NB, LAY, AW>), grid, dim3(W * 64), G::LDS, st,

@@ -388,11 +388,9 @@ template <int F, int LAY, int WR, int WC, int NBUF, bool SUMI> hipError_t mmql_l
         return hipSuccess;
     }
     const void* k = (const void*)mmql_kernel<F, LAY, WR, WC, NBUF, SUMI>;
-    if (G::LDS > 64 * 1024) {
-        static std::atomic<unsigned long long> attr_done{0};
-        const hipError_t e = set_max_lds_once(k, 160 * 1024, attr_done);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    const hipError_t e = lds_opt_in(k, G::LDS, attr_done);
+    if (e != hipSuccess) return e;
     void* out = SUMI ? (void*)g.sumi : (void*)g.C;
     hipLaunchKernelGGL((mmql_kernel<F, LAY, WR, WC, NBUF, SUMI>), grid, dim3(G::W * 64), G::LDS, st, (const uint8_t*)g.A,
                        (const uint8_t*)g.B, g.M, g.N, g.K, out, (int)g.ldc_m, (int)g.ldc_n);

@@ -115,10 +115,9 @@ template <int F, int MT> hipError_t launch_mt(const GemmArgs& g, hipStream_t st)
         return hipSuccess;
     }
     auto k = g.sumi ? ragged_kernel<F, MT, true> : ragged_kernel<F, MT, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> done[2];  // (ragged_mt keeps lds within RG_LDS_MAX = the opt-in's cap)
+    const hipError_t e = lds_opt_in((const void*)k, lds, done[g.sumi ? 1 : 0]);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, grid, dim3(RG_WGS), lds, st, (const uint32_t*)g.A, (const uint8_t*)g.B, g.M, g.N, g.K, g.C,
                        g.ldc_m, g.ldc_n, g.sumi);
     return hipGetLastError();

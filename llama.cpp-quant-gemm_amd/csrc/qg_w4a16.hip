@@ -1378,19 +1378,17 @@ hipError_t w16_launch(const GemmArgs& g, hipStream_t st) {
     if constexpr (MT == 1) {
         if (g.M == 1 && g.ldc_n == 1) {
             auto k1 = w16_gemv1_kernel<F, BPL, LPR, WGS, ONEU>;
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
+            static std::atomic<unsigned long long> done1;
+            const hipError_t e = lds_opt_in((const void*)k1, lds, done1);
+            if (e != hipSuccess) return e;
             hipLaunchKernelGGL(k1, dim3(grid.x), dim3(WGS), lds, st, (const float*)g.A, (const uint8_t*)g.B, g.N, g.K, g.C);
             return hipGetLastError();
         }
     }
     auto kfn = w16_gemv_kernel<F, MT, BPL, LPR, WGS, ONEU>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> done;
+    const hipError_t e = lds_opt_in((const void*)kfn, lds, done);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kfn, grid, dim3(WGS), lds, st, (const float*)g.A, (const uint8_t*)g.B, (long)MT * g.K, g.M, g.N,
                        g.K, g.C, (long)MT * g.ldc_m, g.ldc_m, g.ldc_n);
     return hipGetLastError();

@@ -192,6 +192,42 @@ def test_gemv_multi_unit_sumi_and_output(O, qg, n, k, nu):
     assert_close_to_oracle(O, c, aq, bq, t)
 
 
+@pytest.mark.parametrize("t", [2, 8])
+@pytest.mark.parametrize("m,k,k_small,how", [(4, 9472, 8192, "single"), (4, 9472, 8192, "batch"), (4, 9472, 8192, "group"),
+                                             (8, 5120, 4608, "single")])
+def test_gemv_above_64k_lds(O, qg, t, m, k, k_small, how):
+    """Row GEMV launches whose activation records need more than 64 KiB of LDS, M * (K/32/BPL) * (12 BPL + 4) * 4 bytes
+    (M = 4, K = 9472: 2-block units, 66 304 B; M = 8 forced to the GEMV, K = 5120: 4-block units, 66 560 B), so the
+    kernel's once-per-(instantiation, device) opt-in (lds_opt_in, csrc/qg_kernels.hpp) is needed: as a single call, a
+    strided batch of 2 and a group of 2 equal items, at N = 40 (three row tiles, the last partial). Each runs twice
+    with a call of the same instantiation below 64 KiB in between, so the second takes the "already done" path."""
+    n, algo = 40, ALGOS["gemv"]
+    items = [make_case(O, m, n, k, t, seed=300 + i) for i in range(2)]
+    aqs, bqs = [it[2] for it in items], [it[3] for it in items]
+    _, _, aq_s, bq_s = make_case(O, m, n, k_small, t, seed=310)
+    cfg = qg.debug_config(m, n, k, t, algo)
+    assert cfg.startswith("gemv ") and cfg == qg.debug_config(m, n, k_small, t, algo) == qg.debug_config(m, n, k, t, algo, sumi=True)
+
+    def big():
+        if how == "single":
+            return [host(qg.gemm_w4a8(dev(aqs[0]), dev(bqs[0]), m, n, k, t, algo=algo))]
+        if how == "batch":
+            return list(host(qg.gemm_w4a8_batched(dev(np.stack(aqs)), dev(np.stack(bqs)), m, n, k, t)))
+        outs = qg.gemm_w4a8_grouped([dev(a) for a in aqs], [dev(b) for b in bqs], [n, n], m, k, t)
+        return [host(o) for o in outs]
+
+    first = big()
+    if how == "single":
+        _, want = O.gemm_w4a8(aqs[0], bqs[0], t, want_sumi=True)
+        assert np.array_equal(host(qg.debug_sumi(dev(aqs[0]), dev(bqs[0]), m, n, k, t, algo)), want)
+    small = host(qg.gemm_w4a8(dev(aq_s), dev(bq_s), m, n, k_small, t, algo=algo))
+    assert_close_to_oracle(O, small, aq_s, bq_s, t, mfma=False)
+    second = big()
+    for i, (c1, c2) in enumerate(zip(first, second)):
+        assert_close_to_oracle(O, c1, aqs[i], bqs[i], t, mfma=False)
+        assert np.array_equal(c1.view(np.uint32), c2.view(np.uint32)), f"item {i}"
+
+
 # ------------------------------------------------------------------------------- outputs
 @pytest.mark.parametrize("t", WTYPES)
 @pytest.mark.parametrize("m", [1, 2, 3, 4, 5, 8])

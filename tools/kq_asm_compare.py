@@ -3,8 +3,8 @@
 
     python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_plan, qg_gemv and
-qg_gemv_q4_0 .. qg_gemv_q8_0 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_plan, qg_gemv,
+qg_gemv_q4_0 .. qg_gemv_q8_0, qg_capture_fuse and qg_w4a16 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
 does not have is skipped there), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
 numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file of the result and every pair
 that differs: REGS where the instruction sequence and the remarks are the parent's and only register numbers moved,
@@ -15,7 +15,8 @@ import sys
 from pathlib import Path
 
 FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_glu",
-         "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0"]
+         "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0", "qg_capture_fuse",
+         "qg_w4a16"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
