@@ -281,6 +281,16 @@ int qg_gemm_w8a16_ws(const float* A, const void* B_q8_0, float* C, int M, int N,
                      size_t workspace_bytes, qg_stream_t stream);
 int qg_gemm_w4a16(const float* A, const void* B_q4_0, float* C, int M, int N, int K, qg_stream_t stream);
 int qg_gemm_w8a16(const float* A, const void* B_q8_0, float* C, int M, int N, int K, qg_stream_t stream);
+/* The kernel qg_gemm_w4a16 (wtype = QG_TYPE_Q4_0) or qg_gemm_w8a16 (QG_TYPE_Q8_0) would launch, as text like
+ * qg_debug_config's (NUL-terminated, truncated to len); nothing is launched and no pointer is dereferenced. The
+ * operands are the stand-in addresses A = 256 + a_off and B = 256 + b_off (the alignment rules are part of the
+ * dispatch), the workspace a caller's of ws_bytes bytes as the _ws forms take it (0: none can be had, as during
+ * stream capture). One line per family word — "w16d", "w16s", "w16sk", "w16mfma", "w16gemv" (SIG=m1|full: the
+ * argument list), "w16gemv1r", "w16generic" — with the kernel's template arguments, grid=XxYxZ, wg= (threads per
+ * workgroup), lds= (dynamic LDS bytes) and, for the split-K families, ks= (K slices), ns= or kbs= (stages or blocks
+ * per slice) and ws= (workspace bytes the launch needs). Returns what the call would return before launching; an
+ * empty call (M or N of 0) is QG_OK with an empty line. */
+int qg_w16_config(int M, int N, int K, int wtype, int a_off, int b_off, size_t ws_bytes, char* buf, size_t len);
 /* python/quant_gemm/csrc/gemm_ops.cu:431-466 gemm_q4_0_fp32_cuda(weight_q [N][K/32], activation
  * [M][K], M, N, K) -> out[M][N]: the same product, weight-first argument order. */
 int qg_gemm_q4_0_fp32(const void* weight_q4_0, const float* activation, float* out, int M, int N, int K,

@@ -301,11 +301,12 @@ int weight_major(int wtype, const void* W, const void* A, float* out, int M, int
 }
 
 int run_w16(int wtype, const float* A, const void* B, float* C, int M, int N, int K, hipStream_t st,
-            void* ws = nullptr, size_t ws_bytes = 0) {
+            void* ws = nullptr, size_t ws_bytes = 0, char* describe = nullptr, size_t describe_len = 0) {
     const int rc = precheck({M, N}, K, 32, true, {{A, 3}, {B, 1}, {C, 0}});
     if (rc != QG_GO) return rc;
     GemmArgs g = product_args(A, B, C, M, N, K, wtype);
     g.ws = ws; g.ws_bytes = ws_bytes;
+    g.describe = describe; g.describe_len = describe_len;
     return hip_status(launch_w16(g, st));
 }
 
@@ -694,6 +695,14 @@ int qg_gemm_w4a16_ws(const float* A, const void* B_q4_0, float* C, int M, int N,
 int qg_gemm_w8a16_ws(const float* A, const void* B_q8_0, float* C, int M, int N, int K, void* workspace,
                      size_t workspace_bytes, qg_stream_t stream) {
     return run_w16(QG_TYPE_Q8_0, A, B_q8_0, C, M, N, K, (hipStream_t)stream, workspace, workspace_bytes);
+}
+
+// The operands are stand-ins nothing dereferences: the offsets reach the alignment rules of the dispatch
+int qg_w16_config(int M, int N, int K, int wtype, int a_off, int b_off, size_t ws_bytes, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    return run_w16(wtype, (const float*)(uintptr_t)(256 + (intptr_t)a_off), (const void*)(uintptr_t)(256 + (intptr_t)b_off),
+                   (float*)256, M, N, K, nullptr, ws_bytes ? (void*)256 : nullptr, ws_bytes, buf, len);
 }
 
 int qg_gemm_q4_0_fp32(const void* weight_q4_0, const float* activation, float* out, int M, int N, int K,

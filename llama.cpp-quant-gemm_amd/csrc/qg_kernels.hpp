@@ -137,10 +137,11 @@ inline hipError_t set_max_lds_once(const void* fn, int bytes, std::atomic<unsign
 
 // The dynamic LDS a gfx950 workgroup can ask for, and the opt-in a launch above 64 KiB needs. The cap is the fixed
 // maximum, not the call's size: one instantiation serves many (M, K), so "once, with the first call's size" would leave a
-// later, larger call above its kernel's cap.
+// later, larger call above its kernel's cap. cap: for a kernel that also declares static LDS — the runtime refuses a
+// dynamic cap that, with the static bytes, exceeds the 160 KiB — the caller's own bound on its dynamic size.
 constexpr size_t MAX_LDS_BYTES = 160 * 1024;
-inline hipError_t lds_opt_in(const void* kernel, size_t lds, std::atomic<unsigned long long>& done) {
-    return lds > 64 * 1024 ? set_max_lds_once(kernel, (int)MAX_LDS_BYTES, done) : hipSuccess;
+inline hipError_t lds_opt_in(const void* kernel, size_t lds, std::atomic<unsigned long long>& done, size_t cap = MAX_LDS_BYTES) {
+    return lds > 64 * 1024 ? set_max_lds_once(kernel, (int)cap, done) : hipSuccess;
 }
 
 // Compute units of the current device (hipDeviceAttributeMultiprocessorCount, cached per device; 256 on a

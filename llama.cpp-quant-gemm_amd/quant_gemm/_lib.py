@@ -81,6 +81,7 @@ SIGNATURES = {
     "qg_gemm_w16_workspace_size": ([I, I, I], SZ),
     "qg_gemm_w4a16_ws": ([P, P, P, I, I, I, P, SZ, P], I),
     "qg_gemm_w8a16_ws": ([P, P, P, I, I, I, P, SZ, P], I),
+    "qg_w16_config": ([I, I, I, I, I, I, SZ, ctypes.c_char_p, SZ], I),
     "qg_release_workspaces": ([], None),
     "qg_quantize_q8_1": ([P, P, I64, P], I),
     "qg_quantize_q4_0": ([P, P, I64, P], I),

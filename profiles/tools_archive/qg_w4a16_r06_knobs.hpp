@@ -1,3 +1,8 @@
+// qg_w4a16_r06_knobs.hpp — csrc/qg_w4a16.hip as it stood before its tuning knobs were retired (profiles/w16_pick/README.md): the ABL
+// ablation parameter of w16_sk_kernel / w16s_kernel / w16d_kernel, QG_W16S_U128 with w16s_wfrag_u128, QG_W16D_NB, QG_W16D_ABL,
+// QG_W16_RPL and the #ifndef switches of the plans. Not built; w16_sk_probe.hip and w16s_probe.hip beside it include it (with
+// -I llama.cpp-quant-gemm_amd/csrc for qg_common.hpp and qg_kernels.hpp).
+// ---------------------------------------------------------------------------------------------------------------------
 // qg_w4a16.hip — W4A16 / W8A16: FP32 activations x Q4_0 / Q8_0 weights, fp32 arithmetic.
 //
 // C[M,N] = A_f32[M,K] . dequant(B_w[N,K])^T, activation-major, the device twin of
@@ -510,7 +515,9 @@ template <int F> __device__ __forceinline__ u32x4_t w16_wfrag(uint32_t x, uint32
     return r;
 }
 
-template <int F, int RT, int TT, int KB, int NP>
+// ABL (tuning probe only; the product uses 0): 1 = each slice stores its partial tile and exits
+// (no counter, no reduction: timing of the slice work alone).
+template <int F, int RT, int TT, int KB, int ABL = 0, int NP = 3>
 __global__ __launch_bounds__(RT * 64) void w16_sk_kernel(const float* __restrict__ A, const uint8_t* __restrict__ B,
                                                          float* __restrict__ C, int M, int N, int K, long ldc_m,
                                                          long ldc_n, int kbs, float* __restrict__ part,
@@ -677,6 +684,7 @@ __global__ __launch_bounds__(RT * 64) void w16_sk_kernel(const float* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             __hip_atomic_store(pt + blockIdx.z * TS + pidx(t, e), acc[t][e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (ABL == 1) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0)
@@ -739,9 +747,12 @@ __global__ __launch_bounds__(RT * 64) void w16_sk_kernel(const float* __restrict
 // (deterministic) with sc1 loads and re-arms the counter (MI355X_MICROARCH.md hand-off table, row 1).
 // TT: 16-token tiles per workgroup (1: 16 tokens; 2: 32 tokens, each weight fragment decoded once
 // for both token tiles).
-// (Q4_0 weight fragments as bf16 128 + q, one v_perm_b32 per two elements, measured no faster — M=16 +0.06, M=32
-// -0.29, M=64 +0.11 us, profiles/r02_tuning/ab_u128.txt: the stage is not VALU-bound once the split is shared — and
-// are archived, profiles/tools_archive/qg_w4a16_r06_knobs.hpp; the exact q - 8 products are kept.)
+#ifndef QG_W16S_U128
+#define QG_W16S_U128 0  // Q4_0 weight fragments as bf16 128 + q (w16s_wfrag_u128): measured M=16 +0.06,
+                        // M=32 -0.29, M=64 +0.11 us (profiles/r02_tuning/ab_u128.txt) — the stage is not
+                        // VALU-bound once the split is shared; off (exact q - 8 products kept)
+#endif
+
 template <int TT, int F = FMT_Q4_0, int NP = 3> struct w16s_geom {
     static constexpr int ROWS = 128;              // weight rows per workgroup (4 waves x 2 tiles of 16)
     static constexpr int TOK = 16 * TT;           // tokens per workgroup
@@ -809,6 +820,16 @@ __device__ __forceinline__ u32x4_t w16s_wfrag(uint32_t v) {
     const f32x2 v3 = f32x2{cvt_ubyte<2>(hi), cvt_ubyte<3>(hi)} + o;
     return u32x4_t{hi16_pack(__float_as_uint(v0.x), __float_as_uint(v0.y)), hi16_pack(__float_as_uint(v1.x), __float_as_uint(v1.y)),
                    hi16_pack(__float_as_uint(v2.x), __float_as_uint(v2.y)), hi16_pack(__float_as_uint(v3.x), __float_as_uint(v3.y))};
+}
+
+// The same k-slot as 8 exact bf16 of 128 + q (QG_W16S_U128): a nibble q under a 0x43 high byte is
+// the bf16 0x430q = 128 + q, so one v_perm_b32 builds two elements (7 VALU per dword instead of 19);
+// the stage subtracts 136 * (the block's activation dot with a constant-136 fragment) — the same
+// MFMA chain on the same activation planes, so a row of zero weights (q = 8) cancels exactly.
+__device__ __forceinline__ u32x4_t w16s_wfrag_u128(uint32_t v) {
+    const uint32_t lo = v & 0x0F0F0F0Fu, hi = (v >> 4) & 0x0F0F0F0Fu, c = 0x43434343u;
+    return u32x4_t{__builtin_amdgcn_perm(c, lo, 0x04010400u), __builtin_amdgcn_perm(c, lo, 0x04030402u),
+                   __builtin_amdgcn_perm(c, hi, 0x04010400u), __builtin_amdgcn_perm(c, hi, 0x04030402u)};
 }
 
 // Q8_0: k-slot q = signed qs bytes 4q..4q+3 (dword v0) and 16+4q..16+4q+3 (v1) -> 8 exact bf16.
@@ -894,6 +915,7 @@ template <int TT, int F, int SH, int NP>
 __device__ __forceinline__ void w16s_stage(const uint8_t* sb, const uint8_t* planes, int wave, int lane,
                                            f32x4_t (&acc)[2][TT]) {
     using G = w16s_geom<TT, F, NP>;
+    constexpr bool U128 = QG_W16S_U128 && F == FMT_Q4_0;
     const int r16 = lane & 15, q = lane >> 4;
     u32x4_t ap[NP][4][TT];
 #pragma unroll
@@ -920,6 +942,8 @@ __device__ __forceinline__ void w16s_stage(const uint8_t* sb, const uint8_t* pla
                 uint32_t v1 = pw[4];  // qs[16 + 4q ..]
                 if constexpr (al != 0) v1 = __builtin_amdgcn_alignbyte(pw[5], v1, al);
                 wf[b][i] = w16s_wfrag_q8(v, v1);
+            } else if constexpr (U128) {
+                wf[b][i] = w16s_wfrag_u128(v);
             } else {
                 wf[b][i] = w16s_wfrag(v);
             }
@@ -928,25 +952,36 @@ __device__ __forceinline__ void w16s_stage(const uint8_t* sb, const uint8_t* pla
     });
     __builtin_amdgcn_sched_barrier(0);
     f32x4_t c[4][2][TT];
+    f32x4_t z[4][TT];  // U128: 136 * the block's activation sum, per token (the same for every row)
+    const u32x4_t k136 = {0x43084308u, 0x43084308u, 0x43084308u, 0x43084308u};  // bf16 136
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
-        for (int t = 0; t < TT; ++t)
+        for (int t = 0; t < TT; ++t) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 c[b][i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[0][b][t]),
                                                                      __builtin_bit_cast(bf16x8_t, wf[b][i]),
                                                                      f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            if constexpr (U128)
+                z[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[0][b][t]),
+                                                                  __builtin_bit_cast(bf16x8_t, k136),
+                                                                  f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        }
 #pragma unroll
     for (int pl = 1; pl < NP; ++pl)
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
-            for (int t = 0; t < TT; ++t)
+            for (int t = 0; t < TT; ++t) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
                     c[b][i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[pl][b][t]),
                                                                          __builtin_bit_cast(bf16x8_t, wf[b][i]), c[b][i][t], 0, 0, 0);
+                if constexpr (U128)
+                    z[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap[pl][b][t]),
+                                                                      __builtin_bit_cast(bf16x8_t, k136), z[b][t], 0, 0, 0);
+            }
     // MFMA results read by the VALU behind an explicit wait (8 states needed; qg_mmq_kernel.hpp)
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
@@ -958,7 +993,10 @@ __device__ __forceinline__ void w16s_stage(const uint8_t* sb, const uint8_t* pla
 #pragma unroll
             for (int t = 0; t < TT; ++t)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][t][e] = __builtin_fmaf(dw[b][i], c[b][i][t][e], acc[i][t][e]);
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (U128) acc[i][t][e] = __builtin_fmaf(dw[b][i], c[b][i][t][e] - z[b][t][e], acc[i][t][e]);
+                    else acc[i][t][e] = __builtin_fmaf(dw[b][i], c[b][i][t][e], acc[i][t][e]);
+                }
 }
 
 // grid (ceil(N / 128), ceil(M / (16 TT)), ks); slice z = stages [z * ns, min(nst, (z + 1) * ns)) of
@@ -966,8 +1004,10 @@ __device__ __forceinline__ void w16s_stage(const uint8_t* sb, const uint8_t* pla
 // R: LDS stage slots (a ring, R - 1 stages in flight ahead of the one being computed, a slot refilled
 // right after the barrier that follows its last reader). After the raw activation planes of stage s
 // have landed, the workgroup splits them once (w16s_split) into the planes buffer, a second barrier
-// publishes it, and every wave computes the stage.
-template <int TT, int R, int F, int NP>
+// publishes it, and every wave computes the stage. ABL (tuning probes only): 1 = DMA and waits
+// without split / compute, 2 = split + compute on whatever the LDS holds, no DMA, 3 = neither (the
+// launch, barriers and the split-K hand-off alone).
+template <int TT, int R, int ABL, int F = FMT_Q4_0, int NP = 3>
 __global__ __launch_bounds__(256) void w16s_kernel(const float* __restrict__ A, const uint8_t* __restrict__ B,
                                                    float* __restrict__ C, int M, int N, int K, long ldc_m, long ldc_n,
                                                    int ns, float* __restrict__ part, unsigned* __restrict__ cnt) {
@@ -1000,6 +1040,7 @@ __global__ __launch_bounds__(256) void w16s_kernel(const float* __restrict__ A, 
     }
     auto slot = [&](int s) { return lds + (s % R) * G::SBYTES; };
     auto issue = [&](int s) {
+        if constexpr (ABL >= 2) return;
         const int h = h0 + s;
         const long dw = (long)h * G::RSB - ((h & 1) ? 8 : 0), da = (long)h * 512;
         uint8_t* dst = slot(s) + 1024 * wave;
@@ -1016,16 +1057,18 @@ __global__ __launch_bounds__(256) void w16s_kernel(const float* __restrict__ A, 
         for (int t = 0; t < TT; ++t) acc[i][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < nloc; ++s) {
         // stages issued so far: 0 .. min(nloc, s + AHEAD) - 1; wait for stage s
-        w16s_wait<G::NIW>(min(nloc, s + AHEAD) - 1 - s);
+        if constexpr (ABL < 2) w16s_wait<G::NIW>(min(nloc, s + AHEAD) - 1 - s);
         __builtin_amdgcn_s_barrier();  // stage s landed everywhere; stage s - 1 and the planes are free
         asm volatile("" ::: "memory");
         if (s + AHEAD < nloc) issue(s + AHEAD);  // into the slot of stage s - 1
-        w16s_split<TT, F, NP>(slot(s), planes, wave, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // planes of stage s published
-        asm volatile("" ::: "memory");
-        if ((h0 + s) & 1) w16s_stage<TT, F, 8, NP>(slot(s), planes, wave, lane, acc);
-        else w16s_stage<TT, F, 0, NP>(slot(s), planes, wave, lane, acc);
+        if constexpr (ABL != 1 && ABL != 3) {
+            w16s_split<TT, F, NP>(slot(s), planes, wave, lane);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();  // planes of stage s published
+            asm volatile("" ::: "memory");
+            if ((h0 + s) & 1) w16s_stage<TT, F, 8, NP>(slot(s), planes, wave, lane, acc);
+            else w16s_stage<TT, F, 0, NP>(slot(s), planes, wave, lane, acc);
+        }
     }
 
     // lane: weight rows n0 + 32 wave + 16 i + r16, tokens m0 + 16 t + 4 q + e
@@ -1116,6 +1159,9 @@ __global__ __launch_bounds__(256) void w16s_kernel(const float* __restrict__ A, 
 // waits for the DMA), its weight row's qs dword q -> 8 exact bf16 of q - 8 (w16s_wfrag), NP chained
 // v_mfma_f32_16x16x32_bf16 per (block, row tile), acc += d_w * dot. The W partial tiles are summed in
 // fixed wave order through LDS at the end: deterministic, and the only global writes are the outputs.
+#ifndef QG_W16D_NB
+#define QG_W16D_NB 0  // (tuning knob) w16d_kernel stage slots per wave; 0: the most that fit, <= 3
+#endif
 // 32 bits at byte offset (compile-time OFF) of an LDS row, from aligned dword reads
 template <int OFF> __device__ __forceinline__ uint32_t w16_lds32(const uint8_t* base) {
     const uint32_t* p = reinterpret_cast<const uint32_t*>(base + (OFF & ~3));
@@ -1141,9 +1187,9 @@ template <int F, int RT, int W, int NP, int SB_ = 2> struct w16d_geom {
     static constexpr int NI = (WP + AP + 63) / 64;         // DMA instructions per stage
     static constexpr int SBYTES = NI * 1024;
     static constexpr int AOFF = WP * 16;
-    // stage slots per wave: the most that fit, at most 3
+    // stage slots per wave: QG_W16D_NB if set, else the most that fit, at most 3
     static constexpr int NBFIT = (160 * 1024) / (W * SBYTES);
-    static constexpr int NB = NBFIT >= 3 ? 3 : NBFIT >= 1 ? NBFIT : 1;
+    static constexpr int NB = QG_W16D_NB > 0 ? QG_W16D_NB : NBFIT >= 3 ? 3 : NBFIT >= 1 ? NBFIT : 1;
     static constexpr int NACC = RT * 4;
     static constexpr size_t LDS = (size_t)W * NB * SBYTES;
     static constexpr bool FITS = LDS <= 160 * 1024 && (size_t)W * NACC * 64 * 4 <= LDS;  // asserted by the kernel
@@ -1151,7 +1197,8 @@ template <int F, int RT, int W, int NP, int SB_ = 2> struct w16d_geom {
     static_assert(RIMG % 16 == 0 && ((RSB & 15) == 0 || (RSB & 15) == G16), "windows end inside the row");
 };
 
-template <int F, int RT, int W, int NP, int SB>
+// ABL (tuning probes only; the product uses 0): 1 = DMA and waits without compute, 2 = compute without DMA.
+template <int F, int RT, int W, int NP, int SB = 2, int ABL = 0>
 __global__ __launch_bounds__(W * 64, 1) void w16d_kernel(const float* __restrict__ A, const uint8_t* __restrict__ B,
                                                          float* __restrict__ C, int M, int N, int K, int ldc_m, int ldc_n) {
     using G = w16d_geom<F, RT, W, NP, SB>;
@@ -1194,6 +1241,7 @@ __global__ __launch_bounds__(W * 64, 1) void w16d_kernel(const float* __restrict
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         (void*)Aw, (short)0, (int)min((long)(M - m0) * K * 4, 0x7FFFFFF0L), 0x00020000);
     auto issue = [&](int h, uint8_t* buf) {
+        if constexpr (ABL == 2) return;
         const int dw = h * G::RSB - ((h * G::RSB) & 15), da = h * (G::SB * QK * 4);
         static_for<G::NI>([&](auto I) {
             constexpr int i = decltype(I)::value;
@@ -1214,7 +1262,7 @@ __global__ __launch_bounds__(W * 64, 1) void w16d_kernel(const float* __restrict
     for (int k = 0; k < mine; ++k) {
         const int h = wave + k * W;
         uint8_t* buf = bufs + (k % G::NB) * G::SBYTES;
-        const int younger = min(mine - 1 - k, G::NB - 1);
+        const int younger = ABL == 2 ? 0 : min(mine - 1 - k, G::NB - 1);
         if (younger <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::NI) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G::NI) : "memory");
@@ -1237,6 +1285,10 @@ __global__ __launch_bounds__(W * 64, 1) void w16d_kernel(const float* __restrict
             }
         });
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (ABL == 1) {
+            if (k + G::NB < mine) issue(h + G::NB * W, buf);
+            continue;
+        }
         if (k + G::NB < mine) {  // every LDS read of this buffer has returned: refill it
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             issue(h + G::NB * W, buf);
@@ -1313,163 +1365,100 @@ __global__ __launch_bounds__(W * 64, 1) void w16d_kernel(const float* __restrict
 #ifndef QG_GEMV_SMALLK
 #define QG_GEMV_SMALLK 1
 #endif
+#ifndef QG_W16_RPL
+#define QG_W16_RPL 0  // weight rows per wave of the M = 1 W4A16 GEMV: 0 = by N (below), 1 = w16_gemv1_kernel
+#endif
 namespace {
 constexpr int W16_MT = 8;
+constexpr size_t W16_LDS_MAX = 160 * 1024;
 
-// ---- one call's choice, and its one consumer -------------------------------------------------------------------
-// A rule below (w16d_cand .. w16generic_cand) answers with the kernel it would run as a W16Pick, or with fn == nullptr
-// when it does not take the call. `c` holds the template arguments that instantiated fn (w16_pick<kernel<...>> with
-// W16_C of the same constants, side by side), so the line qg_w16_config prints names the kernel that runs.
-// The kernels' argument lists: (A, B, sA, M, N, K, C, sC, ldc_m, ldc_n); (A, B, N, K, C); (A, B, C, M, N, K, ldc_m,
-// ldc_n), which the split-K kernels extend by (ns | kbs, part, cnt).
-enum : int { W16_SIG_FULL, W16_SIG_M1, W16_SIG_TILE, W16_SIG_NS, W16_SIG_KBS };
-struct W16Const { const char* name; int v; };
-struct W16Pick {
-    const void* fn = nullptr;
-    std::atomic<unsigned long long>* lds_done = nullptr;  // fn's lds_opt_in mask
-    int sig = 0;
-    const char* family = "";
-    W16Const c[6] = {};  // name == nullptr: no more
-    dim3 grid;
-    int wg = 0;  // threads per workgroup
-    size_t lds = 0, lds_cap = MAX_LDS_BYTES;  // lds_opt_in's cap: less for a kernel with static LDS of its own (w16_sk_kernel)
-    int mt = 0;           // W16_SIG_FULL: activation rows per chunk (grid.y chunks)
-    int ks = 1, per = 0;   // W16_SIG_NS / _KBS: K slices (grid.z); 4-block stages (ns) or blocks (kbs) per slice
-    bool ldc32 = false;    // W16_SIG_TILE: w16d_kernel's 32-bit output strides
-    size_t ws = 0;         // workspace bytes the launch needs (ks > 1: tile counters + partial tiles), 0: none
-};
-template <auto KERNEL>
-W16Pick w16_pick(int sig, const char* family, std::initializer_list<W16Const> c, dim3 grid, int wg, size_t lds) {
-    static std::atomic<unsigned long long> done{0};  // one per instantiation
-    W16Pick p;
-    p.fn = (const void*)KERNEL; p.lds_done = &done; p.sig = sig; p.family = family;
-    p.grid = grid; p.wg = wg; p.lds = lds;
-    std::copy(c.begin(), c.end(), p.c);
-    return p;
-}
-// the constants as they stand in the kernel's template argument list on the same line
-#define W16_C(x) W16Const{#x, (int)(x)}
-
-// Workspace layout, the same for every shape: W16_CNT_BYTES of tile counters (split-K runs only
-// while the grid has < 512 tiles), then the partial tiles. A fixed counter region keeps the
-// counters zero across shapes: every launch re-arms its own counters, and no other shape's
-// partial tiles ever overlap them (ADVICE r01: a shape-dependent offset let one shape's partials
-// land in another shape's counters on a shared workspace).
-constexpr size_t W16_CNT_BYTES = 4096;
-
-// Describe the pick (qg_w16_config: nothing touches the device), or launch it on ws (nullptr: none; p.ws == 0 then)
-hipError_t w16_run(const W16Pick& p, const GemmArgs& g, void* ws, hipStream_t st) {
-    if (g.describe) {
-        char s[256];
-        int n = snprintf(s, sizeof s, "%s", p.family);
-        for (const W16Const& c : p.c)
-            if (c.name) n += snprintf(s + n, sizeof s - n, " %s=%d", c.name, c.v);
-        if (p.sig <= W16_SIG_M1 && p.mt) n += snprintf(s + n, sizeof s - n, " SIG=%s", p.sig == W16_SIG_M1 ? "m1" : "full");
-        n += snprintf(s + n, sizeof s - n, " grid=%ux%ux%u wg=%d lds=%zu", p.grid.x, p.grid.y, p.grid.z, p.wg, p.lds);
-        if (p.sig >= W16_SIG_NS)
-            snprintf(s + n, sizeof s - n, " ks=%d %s=%d ws=%zu", p.ks, p.sig == W16_SIG_NS ? "ns" : "kbs", p.per, p.ws);
-        describe_kernel(g, "%s", s);
-        return hipSuccess;
-    }
-    const hipError_t e = lds_opt_in(p.fn, p.lds, *p.lds_done, p.lds_cap);
-    if (e != hipSuccess) return e;
-    const void *A = g.A, *B = g.B;
-    float* C = g.C;
-    int M = g.M, N = g.N, K = g.K, per = p.per, ldc_m32 = (int)g.ldc_m, ldc_n32 = (int)g.ldc_n;
-    long sA = (long)p.mt * g.K, sC = (long)p.mt * g.ldc_m, ldc_m = g.ldc_m, ldc_n = g.ldc_n;
-    unsigned* cnt = (unsigned*)ws;
-    float* part = ws ? (float*)((uint8_t*)ws + W16_CNT_BYTES) : nullptr;
-    void* full[] = {&A, &B, &sA, &M, &N, &K, &C, &sC, &ldc_m, &ldc_n};
-    void* m1[] = {&A, &B, &N, &K, &C};
-    void* tile[] = {&A, &B, &C, &M, &N, &K, p.ldc32 ? (void*)&ldc_m32 : &ldc_m, p.ldc32 ? (void*)&ldc_n32 : &ldc_n, &per, &part, &cnt};
-    return hipLaunchKernel(p.fn, p.grid, dim3(p.wg), p.sig == W16_SIG_FULL ? full : p.sig == W16_SIG_M1 ? m1 : tile, p.lds, st);
-}
-
-inline bool aligned_to(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-// ---- the GEMV ladder (M <= 8: w16mfma_cand comes first beyond) --------------------------------------------------
 template <int F, int BPL> size_t w16_lds(int mt, int K) { return (size_t)mt * (K / QK / BPL) * w16_geom<F, BPL>::REC_DW * 4; }
-template <int F, int MT, int BPL, int LPR, int WGS, bool ONEU = false> W16Pick w16_gemv_pick(const GemmArgs& g) {
+
+template <int F, int MT, int BPL, int LPR, int WGS, bool ONEU = false>
+hipError_t w16_launch(const GemmArgs& g, hipStream_t st) {
     constexpr int RPB = (WGS / 64) * (64 / LPR);
-    const std::initializer_list<W16Const> c = {W16_C(F), W16_C(MT), W16_C(BPL), W16_C(LPR), W16_C(WGS), W16_C(ONEU)};
+    const int rows = g.M < MT ? g.M : MT;
+    const size_t lds = w16_lds<F, BPL>(rows, g.K);
     const dim3 grid((g.N + RPB - 1) / RPB, (g.M + MT - 1) / MT);
-    const size_t lds = w16_lds<F, BPL>(g.M < MT ? g.M : MT, g.K);
-    W16Pick p = w16_pick<w16_gemv_kernel<F, MT, BPL, LPR, WGS, ONEU>>(W16_SIG_FULL, "w16gemv", c, grid, WGS, lds);
-    if constexpr (MT == 1)
-        if (g.M == 1 && g.ldc_n == 1) p = w16_pick<w16_gemv1_kernel<F, BPL, LPR, WGS, ONEU>>(W16_SIG_M1, "w16gemv", c, grid, WGS, lds);
-    p.mt = MT;
-    return p;
+    if constexpr (MT == 1) {
+        if (g.M == 1 && g.ldc_n == 1) {
+            auto k1 = w16_gemv1_kernel<F, BPL, LPR, WGS, ONEU>;
+            static std::atomic<unsigned long long> done1;
+            const hipError_t e = lds_opt_in((const void*)k1, lds, done1);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k1, dim3(grid.x), dim3(WGS), lds, st, (const float*)g.A, (const uint8_t*)g.B, g.N, g.K, g.C);
+            return hipGetLastError();
+        }
+    }
+    auto kfn = w16_gemv_kernel<F, MT, BPL, LPR, WGS, ONEU>;
+    static std::atomic<unsigned long long> done;
+    const hipError_t e = lds_opt_in((const void*)kfn, lds, done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kfn, grid, dim3(WGS), lds, st, (const float*)g.A, (const uint8_t*)g.B, (long)MT * g.K, g.M, g.N,
+                       g.K, g.C, (long)MT * g.ldc_m, g.ldc_m, g.ldc_n);
+    return hipGetLastError();
 }
 
-// The unit form and workgroup of MT-row chunks (the 2-block forms exist for MT <= 4 only)
-template <int F, int MT> W16Pick w16_gemv_form(const GemmArgs& g) {
+template <int F, int MT> hipError_t w16_launch_mt(const GemmArgs& g, hipStream_t st) {
     const int nb = g.K / QK;
-    // 2-block units, one row per wave, 1024-thread workgroups: half the per-wave work of the 4-block shape (as qg_gemv.hip)
-    if constexpr (MT <= 4) {
-        const bool fits2 = nb % 2 == 0 && w16_lds<F, 2>(g.M < MT ? g.M : MT, g.K) <= MAX_LDS_BYTES;
-        if (fits2 && nb / 2 >= 64) {
-            // K == 4096, Q4_0: one unit per lane (M=1 4.82 -> 4.61 us; Q8_0 measured no better)
-            if constexpr (MT == 1 && F == FMT_Q4_0)
-                if (nb / 2 <= 64) {
-                    // two weight rows per wave from N = 8192 on (profiles/r03_tuning/r03_ab_rpl.txt: N = 11008
-                    // 9.01 -> 7.73 us, N = 32000 21.3 -> 18.4; N = 4096 +1 %), bit-identical
-                    if (g.N >= 8192 && g.M == 1 && g.ldc_n == 1) {
-                        constexpr int RPL = 2, WGS = 1024 / RPL, RPB = (WGS / 64) * RPL;
-                        return w16_pick<w16_gemv1r_kernel<F, WGS, RPL>>(W16_SIG_M1, "w16gemv1r", {W16_C(F), W16_C(WGS), W16_C(RPL)},
-                                                                        dim3((g.N + RPB - 1) / RPB), WGS, w16_lds<F, 2>(1, g.K));
-                    }
-                    return w16_gemv_pick<F, 1, 2, 64, 1024, true>(g);
+    // 2-block units, one row per wave, 1024-thread workgroups: half the per-wave work of the 4-block
+    // shape (as the W4A8 GEMV, qg_gemv.hip)
+    if (MT <= 4 && nb % 2 == 0 && nb / 2 >= 64 && w16_lds<F, 2>(g.M < MT ? g.M : MT, g.K) <= W16_LDS_MAX) {
+        // K == 4096, Q4_0: one unit per lane (M=1 4.82 -> 4.61 us; Q8_0 measured no better)
+        if constexpr (MT == 1 && F == FMT_Q4_0)
+            if (nb / 2 <= 64) {
+                // two weight rows per wave from N = 8192 on (profiles/r03_tuning/r03_ab_rpl.txt: N = 11008
+                // 9.01 -> 7.73 us, N = 32000 21.3 -> 18.4; N = 4096 +1 %), bit-identical
+                constexpr int RPL = QG_W16_RPL ? QG_W16_RPL : 2;
+                if (RPL > 1 && (QG_W16_RPL || g.N >= 8192) && g.M == 1 && g.ldc_n == 1) {
+                    constexpr int WG = 1024 / RPL, RPB = (WG / 64) * RPL;
+                    const size_t lds = w16_lds<F, 2>(1, g.K);
+                    hipLaunchKernelGGL((w16_gemv1r_kernel<F, WG, RPL>), dim3((g.N + RPB - 1) / RPB), dim3(WG), lds, st,
+                                       (const float*)g.A, (const uint8_t*)g.B, g.N, g.K, g.C);
+                    return hipGetLastError();
                 }
-            return w16_gemv_pick<F, MT, 2, 64, 1024>(g);
-        }
-        if (QG_GEMV_SMALLK && fits2 && nb / 2 >= 16) {
-            // K < 4096: 32 / 16 lanes per row, 16 rows per workgroup (as the W4A8 GEMV)
-            if (nb / 2 >= 32) {
-                if constexpr (MT == 1)
-                    if (nb / 2 == 32) return w16_gemv_pick<F, 1, 2, 32, 512, true>(g);
-                return w16_gemv_pick<F, MT, 2, 32, 512>(g);
+                return w16_launch<F, 1, 2, 64, 1024, true>(g, st);
             }
+        return w16_launch<F, MT, 2, 64, 1024>(g, st);
+    }
+    if (QG_GEMV_SMALLK && MT <= 4 && nb % 2 == 0 && nb / 2 >= 16 && w16_lds<F, 2>(g.M < MT ? g.M : MT, g.K) <= W16_LDS_MAX) {
+        // K < 4096: 32 / 16 lanes per row, 16 rows per workgroup (as the W4A8 GEMV)
+        if (nb / 2 >= 32) {
             if constexpr (MT == 1)
-                if (nb / 2 == 16) return w16_gemv_pick<F, 1, 2, 16, 256, true>(g);
-            return w16_gemv_pick<F, MT, 2, 16, 256>(g);
+                if (nb / 2 == 32) return w16_launch<F, 1, 2, 32, 512, true>(g, st);
+            return w16_launch<F, MT, 2, 32, 512>(g, st);
         }
+        if constexpr (MT == 1)
+            if (nb / 2 == 16) return w16_launch<F, 1, 2, 16, 256, true>(g, st);
+        return w16_launch<F, MT, 2, 16, 256>(g, st);
     }
     if (nb % 4 == 0) {
-        if (nb / 4 >= 32) return w16_gemv_pick<F, MT, 4, 32, 512>(g);
-        return w16_gemv_pick<F, MT, 4, 4, 256>(g);
+        if (nb / 4 >= 32) return w16_launch<F, MT, 4, 32, 512>(g, st);
+        return w16_launch<F, MT, 4, 4, 256>(g, st);
     }
-    return w16_gemv_pick<F, MT, 2, 8, 256>(g);
+    return w16_launch<F, MT, 2, 8, 256>(g, st);
 }
 
-// Rows per chunk: the next power of two >= M (at most 8), halved until the LDS records fit. Not taken: weights or
-// activations off the loads' alignment, odd K / 32.
-template <int F> W16Pick w16gemv_cand(const GemmArgs& g) {
+// Rows per chunk: the next power of two >= M (at most 8), halved until the LDS records fit; 0 if
+// the fast kernel does not apply (alignment, K not a multiple of 64).
+template <int F> int w16_pick_mt(const GemmArgs& g) {
     const int nb = g.K / QK;
-    if (nb % 2 != 0 || !aligned_to(g.A, 16) || !aligned_to(g.B, 4)) return {};
+    const int bpl = nb % 4 == 0 ? 4 : 2;
+    if (nb % bpl != 0) return 0;
+    if (((uintptr_t)g.A & 15) != 0 || ((uintptr_t)g.B & 3) != 0) return 0;
     for (int mt = g.M <= 1 ? 1 : g.M <= 2 ? 2 : g.M <= 4 ? 4 : W16_MT; mt >= 1; mt /= 2) {
-        const size_t lds = nb % 4 == 0 ? w16_lds<F, 4>(mt, g.K) : w16_lds<F, 2>(mt, g.K);
-        if (lds > MAX_LDS_BYTES || (g.M + mt - 1) / mt > 65535) continue;
-        return mt == 1 ? w16_gemv_form<F, 1>(g) : mt == 2 ? w16_gemv_form<F, 2>(g) : mt == 4 ? w16_gemv_form<F, 4>(g) : w16_gemv_form<F, 8>(g);
+        const size_t lds = bpl == 4 ? w16_lds<F, 4>(mt, g.K) : w16_lds<F, 2>(mt, g.K);
+        if (lds <= W16_LDS_MAX && (g.M + mt - 1) / mt <= 65535) return mt;
     }
-    return {};
+    return 0;
 }
 
-template <int F> W16Pick w16generic_cand(const GemmArgs& g) {  // any K % 32 == 0 and alignment
-    if (g.M > 65535) return {};
-    return w16_pick<w16_generic_kernel<F>>(W16_SIG_TILE, "w16generic", {W16_C(F)}, dim3((g.N + 3) / 4, g.M), 256, 0);
-}
-
-// ---- prefill (M > 8) --------------------------------------------------------------------------------------------
-// w16_mfma_kernel: 16-B aligned activations, any weight alignment; one 16-row tile per workgroup while that leaves
-// < 256 workgroups of 32 rows
-template <int F, int RT> W16Pick w16mfma_pick(const GemmArgs& g) {
-    constexpr int TT = 2, W = 16;
-    return w16_pick<w16_mfma_kernel<F, RT, TT, W>>(W16_SIG_TILE, "w16mfma", {W16_C(F), W16_C(RT), W16_C(TT), W16_C(W)},
-                                                   dim3((g.N + 16 * RT - 1) / (16 * RT), (g.M + 16 * TT - 1) / (16 * TT)), W * 64,
-                                                   (size_t)W * RT * TT * 4 * 64 * 4);
-}
-template <int F> W16Pick w16mfma_cand(const GemmArgs& g) {
-    if (g.M <= 8 || !aligned_to(g.A, 16) || (g.M + 31) / 32 > 65535) return {};
-    return (long)((g.N + 31) / 32) * ((g.M + 31) / 32) < 256 ? w16mfma_pick<F, 1>(g) : w16mfma_pick<F, 2>(g);
+template <int F, int RT, int TT, int W> hipError_t w16_mfma_launch(const GemmArgs& g, hipStream_t st) {
+    const dim3 grid((g.N + 16 * RT - 1) / (16 * RT), (g.M + 16 * TT - 1) / (16 * TT));
+    const size_t lds = (size_t)W * RT * TT * 4 * 64 * 4;
+    hipLaunchKernelGGL((w16_mfma_kernel<F, RT, TT, W>), grid, dim3(W * 64), lds, st, (const float*)g.A,
+                       (const uint8_t*)g.B, g.C, g.M, g.N, g.K, g.ldc_m, g.ldc_n);
+    return hipGetLastError();
 }
 
 // Split-K prefill plan: RT 16-row tiles (one per wave) x 16 TT tokens x ks slices of K, KB blocks
@@ -1480,13 +1469,19 @@ struct w16_plan {
     long gx = 0, gy = 0;
     size_t ws_bytes = 0;  // workspace for ks > 1: tile counters, then ks partial tiles per tile
 };
+// Workspace layout, the same for every shape: W16_CNT_BYTES of tile counters (split-K runs only
+// while the grid has < 512 tiles), then the partial tiles. A fixed counter region keeps the
+// counters zero across shapes: every launch re-arms its own counters, and no other shape's
+// partial tiles ever overlap them (ADVICE r01: a shape-dependent offset let one shape's partials
+// land in another shape's counters on a shared workspace).
+constexpr size_t W16_CNT_BYTES = 4096;
 
 w16_plan w16_make_plan(int M, int N, int K) {
     w16_plan p;
     const int nb = K / QK;
     if (M <= 8 || K % QK != 0) return p;
     // M <= 64: 64-row x 32-token tiles, 8-block chunks, K split until >= 512 workgroups (two per CU:
-    // one's loads overlap the other's compute); profiles/tools_archive/w16_sk_probe.hip, profiles/r01_tuning/
+    // one's loads overlap the other's compute); tools/w16_sk_probe.hip, profiles/r01_tuning/
     // w16_sk_probe.txt: M=32 N=K=4096 16.7 us vs 18.8 for 128-row tiles, 16-block chunks, 256 WGs.
     // M > 64: 128-row (N >= 2048) or 64-row tiles x 64 tokens, >= 256 workgroups.
     int want = 256;
@@ -1507,33 +1502,50 @@ w16_plan w16_make_plan(int M, int N, int K) {
     return p;
 }
 
-// Round-2 plan (w16s_kernel; Q4_0 and Q8_0, 8 < M <= 64, K % 256 == 0): 128-row x 16-token tiles, K split
+// Round-2 plan (w16s_kernel; Q4_0, 8 < M <= 64, K % 256 == 0): 128-row x 16-token tiles, K split
 // into ks slices of ns 4-block stages (see below for the count).
-constexpr int W16S_R = 2;          // LDS ring slots of w16s_kernel (2: one stage in flight ahead; 3-4 measured slower)
-constexpr int W16S_MINWG = 512;    // split K until the grid has this many workgroups
-constexpr int W16S_MINST = 4;      // ... keeping at least this many 4-block stages per slice
-constexpr int W16_NP2_MINK = 1024; // K from which the prefill kernels split activations into TWO bf16 parts
+#ifndef QG_W16S
+#define QG_W16S 1
+#endif
+#ifndef W16S_R
+#define W16S_R 2  // LDS ring slots of w16s_kernel (2: one stage in flight ahead; 3-4 measured slower)
+#endif
+#ifndef QG_W16S_Q8
+#define QG_W16S_Q8 1  // the round-2 prefill for W8A16 (Q8_0 weights) too
+#endif
+#ifndef W16S_TT2
+#define W16S_TT2 2  // 32-token tiles: 0 never, 1 for every M > 16, 2 by the rule in w16s_make_plan
+#endif
+#ifndef W16S_MINWG
+#define W16S_MINWG 512  // split K until the grid has this many workgroups (tuning knob)
+#endif
+#ifndef W16S_MINST
+#define W16S_MINST 4  // ... keeping at least this many 4-block stages per slice (tuning knob)
+#endif
+#ifndef QG_W16S_NP2_MINK
+#define QG_W16S_NP2_MINK 1024  // K from which w16s_kernel splits activations into TWO bf16 parts (0: never)
+#endif
 // Activation parts of the round-2 prefill. Three truncated parts represent every fp32 activation
 // exactly; two round-to-nearest parts leave |r| <= 2^-16 |a| per element, i.e. at most
 // 2^-16 sum_k |a_k w_k| = 256 u sum_k |a_k w_k| (u = 2^-24) on an output, against the fp32 K-term
 // summation bound 2 (K + 2) u sum_k |a_k w_k| the parity tests hold the kernel to (oracle.w16_tol):
 // from K = 1024 on the representation error stays below an eighth of that bound.
-inline int w16s_parts(int K) { return K >= W16_NP2_MINK ? 2 : 3; }
+inline int w16s_parts(int K) { return QG_W16S_NP2_MINK > 0 && K >= QG_W16S_NP2_MINK ? 2 : 3; }
 w16_plan w16s_make_plan(int M, int N, int K) {
     w16_plan p;
-    if (M <= 8 || M > 64 || N < 1 || K % 256 != 0) return p;
+    if (!QG_W16S || M <= 8 || M > 64 || N < 1 || K % 256 != 0) return p;
     p.gx = (N + 127) / 128;
     // 32-token tiles decode each weight fragment once for two token tiles; they pay off only while the
     // grid keeps >= 64 tiles of 128 rows x 32 tokens with no idle token rows (profiles/r03_tuning/
     // r03_ab_w16_tt2.txt: M = 32 N = 11008 27.8 -> 23.6 us, M = 64 N = 4096 18.3 -> 17.9; slower at
     // N = 4096 M = 24 / 32 (12.7 -> 14.8: half the tiles) and M = 48 (idle rows))
-    const bool tt2 = M % 32 == 0 && p.gx * (M / 32) >= 64;
+    const bool tt2 = W16S_TT2 == 1 ? M > 16 : W16S_TT2 == 2 && M % 32 == 0 && p.gx * (M / 32) >= 64;
     p.tt = tt2 ? 2 : 1;
     p.gy = (M + 16 * p.tt - 1) / (16 * p.tt);
     const long tiles = p.gx * p.gy;
     const int nst = K / 128;
     // >= 512 workgroups (two per CU overlap each other's barriers and LDS latency) with >= 4 stages per
-    // slice (profiles/tools_archive/w16s_probe.hip, profiles/r02_tuning/w16s_probe.txt: M=32 N=K=4096 14.3 us at 8 x 4
+    // slice (tools/w16s_probe.hip, profiles/r02_tuning/w16s_probe.txt: M=32 N=K=4096 14.3 us at 8 x 4
     // stages vs 15.8 at 4 x 8, 16.8 for the round-1 kernel)
     int ks = (int)std::max<long>(1, std::min<long>(nst / W16S_MINST, (W16S_MINWG + tiles - 1) / tiles));
     p.ns = (nst + ks - 1) / ks;
@@ -1544,135 +1556,177 @@ w16_plan w16s_make_plan(int M, int N, int K) {
     return p;
 }
 
-template <int F, int TT, int NP> W16Pick w16s_pick(const w16_plan& pl) {
+template <int F, int TT, int NP> hipError_t w16s_launch_tt(const GemmArgs& g, const w16_plan& p, void* ws, hipStream_t st) {
     using G = w16s_geom<TT, F, NP>;
-    constexpr int R = W16S_R;
-    constexpr size_t lds = (size_t)R * G::SBYTES + G::PLB;
-    static_assert(lds <= MAX_LDS_BYTES, "LDS per workgroup");
-    W16Pick p = w16_pick<w16s_kernel<TT, R, F, NP>>(W16_SIG_NS, "w16s", {W16_C(F), W16_C(TT), W16_C(R), W16_C(NP)},
-                                                    dim3(pl.gx, pl.gy, pl.ks), 256, lds);
-    p.ks = pl.ks; p.per = pl.ns; p.ws = pl.ws_bytes;
-    return p;
+    unsigned* cnt = (unsigned*)ws;
+    float* part = ws ? (float*)((uint8_t*)ws + W16_CNT_BYTES) : nullptr;
+    constexpr size_t lds = (size_t)W16S_R * G::SBYTES + G::PLB;
+    static_assert(lds <= 160 * 1024, "LDS per workgroup");
+    static std::atomic<unsigned long long> attr_done{0};
+    {
+        const hipError_t e = set_max_lds_once((const void*)w16s_kernel<TT, W16S_R, 0, F, NP>, (int)lds, attr_done);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((w16s_kernel<TT, W16S_R, 0, F, NP>), dim3(p.gx, p.gy, p.ks), dim3(256), lds, st, (const float*)g.A,
+                       (const uint8_t*)g.B, g.C, g.M, g.N, g.K, g.ldc_m, g.ldc_n, p.ns, part, cnt);
+    return hipGetLastError();
 }
-// 16-B aligned activations and weights (rows are then 16-B multiples)
-template <int F> W16Pick w16s_cand(const GemmArgs& g) {
-    if (!(aligned_to(g.A, 16) && aligned_to(g.B, 16) && (g.M + 15) / 16 <= 65535)) return {};
-    const w16_plan pl = w16s_make_plan(g.M, g.N, g.K);
-    if (!pl.ns) return {};
-    if (w16s_parts(g.K) == 2) return pl.tt == 2 ? w16s_pick<F, 2, 2>(pl) : w16s_pick<F, 1, 2>(pl);
-    return pl.tt == 2 ? w16s_pick<F, 2, 3>(pl) : w16s_pick<F, 1, 3>(pl);
-}
-
-template <int F, int RT, int TT, int NP> W16Pick w16sk_pick(const GemmArgs& g, const w16_plan& pl, int ks) {
-    constexpr int KB = 8;
-    W16Pick p = w16_pick<w16_sk_kernel<F, RT, TT, KB, NP>>(W16_SIG_KBS, "w16sk", {W16_C(F), W16_C(RT), W16_C(TT), W16_C(KB), W16_C(NP)},
-                                                           dim3(pl.gx, pl.gy, ks), RT * 64, (size_t)TT * KB * NP * 1024);
-    p.lds_cap = p.lds;  // a constant of the instantiation; the kernel's s_last is static LDS
-    p.ks = ks; p.per = g.K / QK / ks; p.ws = ks > 1 ? pl.ws_bytes : 0;
-    return p;
-}
-// w16_sk_kernel: 16-B aligned activations, 4-B aligned weights. SPLIT: the plan's K slices, through a workspace. Else
-// (the plan has one slice, or no workspace could be had) one slice — unless a grid that small would leave most CUs
-// idle: then the older kernel (w16mfma_cand).
-template <int F, bool SPLIT> W16Pick w16sk_cand(const GemmArgs& g) {
-    if (!(aligned_to(g.A, 16) && aligned_to(g.B, 4) && (g.M + 63) / 64 <= 65535)) return {};
-    const w16_plan pl = w16_make_plan(g.M, g.N, g.K);
-    if (!pl.rt || (SPLIT ? pl.ks == 1 : pl.ks > 1 && pl.gx * pl.gy < 128)) return {};
-    const int ks = SPLIT ? pl.ks : 1;
-    const bool np2 = w16s_parts(g.K) == 2;
-    if (pl.tt == 2) return np2 ? w16sk_pick<F, 4, 2, 2>(g, pl, ks) : w16sk_pick<F, 4, 2, 3>(g, pl, ks);
-    if (pl.rt == 8) return np2 ? w16sk_pick<F, 8, 4, 2>(g, pl, ks) : w16sk_pick<F, 8, 4, 3>(g, pl, ks);
-    return np2 ? w16sk_pick<F, 4, 4, 2>(g, pl, ks) : w16sk_pick<F, 4, 4, 3>(g, pl, ks);
+template <int F> hipError_t w16s_launch(const GemmArgs& g, const w16_plan& p, void* ws, hipStream_t st) {
+    if (w16s_parts(g.K) == 2) return p.tt == 2 ? w16s_launch_tt<F, 2, 2>(g, p, ws, st) : w16s_launch_tt<F, 1, 2>(g, p, ws, st);
+    return p.tt == 2 ? w16s_launch_tt<F, 2, 3>(g, p, ws, st) : w16s_launch_tt<F, 1, 3>(g, p, ws, st);
 }
 
-// ---- the no-split-K small-M prefill (w16d_kernel) where w16d_ok holds ----
-constexpr int W16D_MAXK = 8192;  // beyond, the split-K kernel is faster (K = 14336: 30.4 vs 29.4 us, ab_w16d_v2.txt)
+template <int F, int RT, int TT, int KB, int NP> hipError_t w16_sk_launch_np(const GemmArgs& g, const w16_plan& p, void* ws,
+                                                                          hipStream_t st) {
+    const int ks = ws ? p.ks : 1;
+    unsigned* cnt = (unsigned*)ws;
+    float* part = ws ? (float*)((uint8_t*)ws + W16_CNT_BYTES) : nullptr;
+    constexpr size_t lds = (size_t)TT * KB * NP * 1024;
+    auto kfn = w16_sk_kernel<F, RT, TT, KB, 0, NP>;
+    if (lds > 64 * 1024) {
+        static std::atomic<unsigned long long> attr_done{0};
+        const hipError_t e = set_max_lds_once((const void*)kfn, (int)lds, attr_done);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kfn, dim3(p.gx, p.gy, ks), dim3(RT * 64), lds, st, (const float*)g.A, (const uint8_t*)g.B, g.C,
+                       g.M, g.N, g.K, g.ldc_m, g.ldc_n, g.K / QK / ks, part, cnt);
+    return hipGetLastError();
+}
+template <int F, int RT, int TT, int KB> hipError_t w16_sk_launch(const GemmArgs& g, const w16_plan& p, void* ws, hipStream_t st) {
+    if (w16s_parts(g.K) == 2) return w16_sk_launch_np<F, RT, TT, KB, 2>(g, p, ws, st);
+    return w16_sk_launch_np<F, RT, TT, KB, 3>(g, p, ws, st);
+}
+
+#ifndef QG_W16D
+#define QG_W16D 1  // the no-split-K small-M prefill (w16d_kernel) where w16d_ok holds
+#endif
+#ifndef QG_W16D_MAXK
+#define QG_W16D_MAXK 8192  // beyond, the split-K kernel is faster (K = 14336: 30.4 vs 29.4 us, ab_w16d_v2.txt)
+#endif
 // 8 < M <= 32 tokens, K % 256 == 0 (16-B aligned weight rows), 16-B aligned operands, 32-bit strides.
-// One dispatch round only (<= one workgroup per CU: device_cus(), 256 on a whole MI355X): with more, each CU runs
-// several workgroups in turn (one fits at a time) and the split-K kernel is faster (M = 32, N = 11008: 29.6 vs
-// 23.5 us, profiles/r04_tuning/ab_w16d_v1.txt).
+// One dispatch round only (<= one workgroup per CU: device_cus(), 256 on a whole MI355X): with more, each
+// CU runs several workgroups in turn
+// (one fits at a time) and the split-K kernel is faster (M = 32, N = 11008: 29.6 vs 23.5 us,
+// profiles/r04_tuning/ab_w16d_v1.txt).
 inline bool w16d_ok(const GemmArgs& g) {
-    if (!(g.M > 8 && g.M <= 32 && g.N >= 1 && g.K % 256 == 0 && aligned_to(g.A, 16) && aligned_to(g.B, 16) &&
-          g.ldc_m <= INT32_MAX && g.ldc_n <= INT32_MAX))
+    if (!(QG_W16D && g.M > 8 && g.M <= 32 && g.N >= 1 && g.K % 256 == 0 && ((uintptr_t)g.A & 15) == 0 &&
+          ((uintptr_t)g.B & 15) == 0 && g.ldc_m <= INT32_MAX && g.ldc_n <= INT32_MAX))
         return false;
     const long rows = (g.N + 15) / 16 * ((g.M + 15) / 16);  // 16-row tiles
     const long cus = device_cus();
-    return (rows <= cus || (long)((g.N + 31) / 32) * ((g.M + 15) / 16) <= cus) && g.K <= W16D_MAXK &&
+    return (rows <= cus || (long)((g.N + 31) / 32) * ((g.M + 15) / 16) <= cus) && g.K <= QG_W16D_MAXK &&
            (long)g.M * g.K * 4 < 0x7FFFFFF0L && (long)g.N * (g.K / QK) * wfmt<FMT_Q8_0>::BB < 0x7FFFFFF0L;  // buffer ranges
 }
+#ifndef QG_W16D_W
 // waves per workgroup (stage slots per wave: the most that fit): 16 waves with one slot each
-// (profiles/r04_tuning/ab_waves_r4v.txt, W4A16 M = 32: 10.80 -> 10.15 us, M = 24 10.34 -> 9.52, M = 16 8.54 -> 8.40,
-// K = 8192 18.47 -> 17.57 against 12 waves with two slots, which beat 8 waves with three: ab_w16d_waves.txt, 11.75 ->
-// 10.78; that record's `wtype=8` row timed the W4A16 kernel, DESIGN.md §6, so the W8A16 (Q8_0) wave count is inherited
-// from Q4_0, not separately tuned) — more waves per SIMD overlap one wave's DMA wait with another's VALU; the refill of
-// a wave's slot is issued right after its LDS reads, before the stage's compute
-constexpr int W16D_W = 16;
-constexpr int W16D_SB = 2;  // blocks per stage (Q4_0 from K = W16D_SB4_MINK takes 4, w16d_cand)
-template <int F, int RT, int NP, int SB = W16D_SB, int WREQ = W16D_W> W16Pick w16d_pick(const GemmArgs& g) {
+// (profiles/r04_tuning/ab_waves_r4v.txt, W4A16 M = 32: 10.80 -> 10.15 us, M = 24 10.34 -> 9.52, M = 16
+// 8.54 -> 8.40, K = 8192 18.47 -> 17.57 against 12 waves with two slots, which beat 8 waves with three:
+// ab_w16d_waves.txt, 11.75 -> 10.78; that record's `wtype=8` row timed the W4A16 kernel, DESIGN.md §6, so
+// the W8A16 (Q8_0) wave count is inherited from Q4_0, not separately tuned) — more waves per SIMD overlap one wave's DMA
+// wait with another's VALU; the refill of a wave's slot is issued right after its LDS reads, before the
+// stage's compute
+#define QG_W16D_W 16
+#endif
+#ifndef QG_W16D_SB
+#define QG_W16D_SB 2  // blocks per stage (tuning knob; Q4_0 from K = QG_W16D_SB4_MINK takes 4, w16d_launch)
+#endif
+#ifndef QG_W16D_ABL
+#define QG_W16D_ABL 0  // (tuning probes only) w16d_kernel ablation
+#endif
+template <int F, int RT, int NP, int SB = QG_W16D_SB, int WREQ = QG_W16D_W>
+hipError_t w16d_launch_np(const GemmArgs& g, hipStream_t st) {
     constexpr int W = w16d_geom<F, RT, WREQ, NP, SB>::FITS         ? WREQ
                       : w16d_geom<F, RT, WREQ - 1, NP, SB>::FITS ? WREQ - 1
                       : w16d_geom<F, RT, WREQ - 2, NP, SB>::FITS ? WREQ - 2
                                                                  : 8;
     using G = w16d_geom<F, RT, W, NP, SB>;
-    W16Pick p = w16_pick<w16d_kernel<F, RT, W, NP, SB>>(W16_SIG_TILE, "w16d", {W16_C(F), W16_C(RT), W16_C(W), W16_C(NP), W16_C(SB)},
-                                                        dim3((g.N + G::ROWS - 1) / G::ROWS, (g.M + 15) / 16), W * 64, G::LDS);
-    p.ldc32 = true;
-    return p;
+    auto k = w16d_kernel<F, RT, W, NP, SB, QG_W16D_ABL>;
+    static std::atomic<unsigned long long> attr_done{0};
+    const hipError_t e = set_max_lds_once((const void*)k, (int)G::LDS, attr_done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((g.N + G::ROWS - 1) / G::ROWS, (g.M + 15) / 16), dim3(W * 64), G::LDS, st, (const float*)g.A,
+                       (const uint8_t*)g.B, g.C, g.M, g.N, g.K, (int)g.ldc_m, (int)g.ldc_n);
+    return hipGetLastError();
 }
+// 16-row tiles while their grid fits one dispatch round (<= one workgroup per CU), else 32-row ones (w16d_ok)
+inline bool w16d_rt2(const GemmArgs& g) { return (long)((g.N + 15) / 16) * ((g.M + 15) / 16) > device_cus(); }
 // Q4_0 from K = 4096 (>= 32 four-block stages, so each of 12 waves takes two or three): 4-block stages
 // with 12 waves (profiles/r04_tuning/ab_w16d_sb4*.txt: M = 32 10.12 -> 9.90 us, M = 16 8.38 -> 8.19,
 // M = 12 8.20 -> 8.06, K = 8192 17.54 -> 17.25, M = 20 / 24 +0.8 / +1.3 %; K = 1024 +8 %: 8 stages for 12
 // waves). The longer 72-B weight windows take fewer DMA requests per byte.
-constexpr int W16D_SB4_MINK = 4096;
-static_assert(W16D_SB4_MINK >= W16_NP2_MINK, "the 4-block stages exist with two activation parts only");
-template <int F> W16Pick w16d_cand(const GemmArgs& g) {
-    if (!w16d_ok(g)) return {};
-    // 16-row tiles while their grid fits one dispatch round (<= one workgroup per CU), else 32-row ones (w16d_ok)
-    const bool rt2 = (long)((g.N + 15) / 16) * ((g.M + 15) / 16) > device_cus();
-    if constexpr (F == FMT_Q4_0)
-        if (g.K >= W16D_SB4_MINK) return rt2 ? w16d_pick<F, 2, 2, 4, 12>(g) : w16d_pick<F, 1, 2, 4, 12>(g);
-    if (w16s_parts(g.K) == 2) return rt2 ? w16d_pick<F, 2, 2>(g) : w16d_pick<F, 1, 2>(g);
-    return rt2 ? w16d_pick<F, 2, 3>(g) : w16d_pick<F, 1, 3>(g);
-}
-
-// ---- the dispatch -----------------------------------------------------------------------------------------------
-// The rules in their order of preference; the first one that takes the call and whose workspace need (W16Pick::ws)
-// is 0 or can be met runs. So a caller workspace too small for the w16s plan may still serve the w16_sk plan, and
-// a call without any runs w16_sk with one slice or falls through to w16_mfma.
-using W16Cand = W16Pick (*)(const GemmArgs&);
-template <int F> constexpr W16Cand W16_CANDS[] = {w16d_cand<F>,    w16s_cand<F>,    w16sk_cand<F, true>, w16sk_cand<F, false>,
-                                                 w16mfma_cand<F>, w16gemv_cand<F>, w16generic_cand<F>};
-
-// The workspace of a launch that needs `bytes`: the caller's (qg_gemm_w4a16_ws; one that is too small or not 256-B
-// aligned is not used, and not replaced), else the library's one for this stream. hold: the library buffer's lock
-// stays taken until the kernel is enqueued, so another host thread on this stream cannot grow (and free) it in
-// between. nullptr: none can be had; a config query asks the device for none.
-void* w16_workspace(const GemmArgs& g, size_t bytes, hipStream_t st, std::unique_lock<std::mutex>* hold) {
-    if (g.ws) return g.ws_bytes >= bytes && aligned_to(g.ws, 256) ? g.ws : nullptr;
-    return g.describe ? nullptr : stream_workspace(st, bytes, 0, hold);
+#ifndef QG_W16D_SB4_MINK
+#define QG_W16D_SB4_MINK 4096
+#endif
+template <int F> hipError_t w16d_launch(const GemmArgs& g, hipStream_t st) {
+    const bool rt2 = w16d_rt2(g);
+    if constexpr (F == FMT_Q4_0 && QG_W16D_SB4_MINK > 0 && QG_W16D_SB == 2) {
+        if (g.K >= QG_W16D_SB4_MINK) {
+            if (w16s_parts(g.K) == 2) return rt2 ? w16d_launch_np<F, 2, 2, 4, 12>(g, st) : w16d_launch_np<F, 1, 2, 4, 12>(g, st);
+            return rt2 ? w16d_launch_np<F, 2, 3, 4, 12>(g, st) : w16d_launch_np<F, 1, 3, 4, 12>(g, st);
+        }
+    }
+    if (w16s_parts(g.K) == 2) return rt2 ? w16d_launch_np<F, 2, 2>(g, st) : w16d_launch_np<F, 1, 2>(g, st);
+    return rt2 ? w16d_launch_np<F, 2, 3>(g, st) : w16d_launch_np<F, 1, 3>(g, st);
 }
 
 template <int F> hipError_t w16_dispatch(const GemmArgs& g, hipStream_t st) {
-    for (const W16Cand cand : W16_CANDS<F>) {
-        const W16Pick p = cand(g);
-        if (!p.fn) continue;
-        std::unique_lock<std::mutex> hold;  // outlives the launch
-        void* ws = p.ws ? w16_workspace(g, p.ws, st, &hold) : nullptr;
-        if (p.ws && !ws) continue;
-        return w16_run(p, g, ws, st);
+    if constexpr (F == FMT_Q4_0 || F == FMT_Q8_0)
+        if (w16d_ok(g)) return w16d_launch<F>(g, st);
+    if constexpr (F == FMT_Q4_0 || (F == FMT_Q8_0 && QG_W16S_Q8)) {
+        // round-2 prefill: 16-B aligned activations and weights (rows are then 16-B multiples)
+        if (((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0 && (g.M + 15) / 16 <= 65535) {
+            const w16_plan p = w16s_make_plan(g.M, g.N, g.K);
+            if (p.ns) {
+                // hold: the library buffer's lock stays taken until the kernel is enqueued, so another
+                // host thread on this stream cannot grow (and free) it in between
+                std::unique_lock<std::mutex> hold;
+                void* ws = nullptr;
+                if (p.ks > 1) {
+                    if (g.ws) ws = g.ws_bytes >= p.ws_bytes && ((uintptr_t)g.ws & 255) == 0 ? g.ws : nullptr;
+                    else ws = stream_workspace(st, p.ws_bytes, 0, &hold);
+                }
+                if (ws || p.ks == 1) return w16s_launch<F>(g, p, ws, st);
+            }
+        }
     }
-    return hipErrorInvalidValue;  // (M > 65535 rows of the generic kernel)
+    if (((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 3) == 0 && (g.M + 63) / 64 <= 65535) {
+        const w16_plan p = w16_make_plan(g.M, g.N, g.K);
+        if (p.rt) {
+            // the caller's workspace (qg_gemm_w4a16_ws), else the library's one for this stream
+            std::unique_lock<std::mutex> hold;
+            void* ws = nullptr;
+            if (p.ks > 1) {
+                if (g.ws) ws = g.ws_bytes >= p.ws_bytes && ((uintptr_t)g.ws & 255) == 0 ? g.ws : nullptr;
+                else ws = stream_workspace(st, p.ws_bytes, 0, &hold);
+            }
+            // without one, a grid this small would leave most CUs idle: the older kernel below
+            if (ws || p.ks == 1 || p.gx * p.gy >= 128) {
+                if (p.tt == 2) return w16_sk_launch<F, 4, 2, 8>(g, p, ws, st);
+                return p.rt == 8 ? w16_sk_launch<F, 8, 4, 8>(g, p, ws, st) : w16_sk_launch<F, 4, 4, 8>(g, p, ws, st);
+            }
+        }
+    }
+    if (g.M > 8 && ((uintptr_t)g.A & 15) == 0 && (g.M + 31) / 32 <= 65535) {
+        // one 16-row tile per workgroup while that leaves < 256 workgroups of 32 rows
+        if ((long)((g.N + 31) / 32) * ((g.M + 31) / 32) < 256) return w16_mfma_launch<F, 1, 2, 16>(g, st);
+        return w16_mfma_launch<F, 2, 2, 16>(g, st);
+    }
+    switch (w16_pick_mt<F>(g)) {
+        case 1: return w16_launch_mt<F, 1>(g, st);
+        case 2: return w16_launch_mt<F, 2>(g, st);
+        case 4: return w16_launch_mt<F, 4>(g, st);
+        case 8: return w16_launch_mt<F, 8>(g, st);
+    }
+    if (g.M > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(w16_generic_kernel<F>, dim3((g.N + 3) / 4, g.M), dim3(256), 0, st, (const float*)g.A,
+                       (const uint8_t*)g.B, g.C, g.M, g.N, g.K, g.ldc_m, g.ldc_n);
+    return hipGetLastError();
 }
 }  // namespace
 
-// one size for both weight types and any alignment: the largest need among the rules, on aligned stand-in operands
+// one size for both weight types: the larger of the two plans' workspaces
 size_t w16_workspace_bytes(int M, int N, int K) {
-    GemmArgs g;
-    g.A = g.B = (const void*)256;
-    g.M = M; g.N = N; g.K = K; g.ldc_m = N;
-    size_t need = 0;
-    for (const W16Cand cand : W16_CANDS<FMT_Q4_0>) need = std::max(need, cand(g).ws);
-    return need;
+    return std::max(w16_make_plan(M, N, K).ws_bytes, w16s_make_plan(M, N, K).ws_bytes);
 }
 
 hipError_t launch_w16(const GemmArgs& g, hipStream_t st) {

@@ -2,8 +2,9 @@
 // activations). Not part of the product. Cold weights (64 rotating copies, 600 MB), graph of 64
 // launches, median of 5. ABL=1: slices store their partials and exit (no reduction).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-//         -I../llama.cpp-quant-gemm_amd/csrc -o w16_sk_probe w16_sk_probe.hip
-#include "../llama.cpp-quant-gemm_amd/csrc/qg_w4a16.hip"
+//         -I../../llama.cpp-quant-gemm_amd/csrc -o w16_sk_probe w16_sk_probe.hip
+// (archived: the ABL variants it instantiates live in qg_w4a16_r06_knobs.hpp, no longer in csrc/qg_w4a16.hip)
+#include "qg_w4a16_r06_knobs.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>

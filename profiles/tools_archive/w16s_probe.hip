@@ -3,8 +3,9 @@
 // round-1 split-K kernel. Not part of the product. Cold weights (64 rotating copies, 600 MB), graph
 // of 64 launches, median of 5 replays.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-//         -mllvm -amdgpu-kernarg-preload-count=16 -I../llama.cpp-quant-gemm_amd/csrc -o w16s_probe w16s_probe.hip
-#include "../llama.cpp-quant-gemm_amd/csrc/qg_w4a16.hip"
+//         -mllvm -amdgpu-kernarg-preload-count=16 -I../../llama.cpp-quant-gemm_amd/csrc -o w16s_probe w16s_probe.hip
+// (archived: the ABL variants it instantiates live in qg_w4a16_r06_knobs.hpp, no longer in csrc/qg_w4a16.hip)
+#include "qg_w4a16_r06_knobs.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>

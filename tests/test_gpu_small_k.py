@@ -58,11 +58,14 @@ def test_small_k_grouped_bit_identical(O, qg):
         assert np.array_equal(host(outs[i]).view(np.uint32), single.view(np.uint32))
 
 
+TWO_ROWS_NK = (11008, 4096)
+
+
 def test_w16_two_rows_per_wave_bit_identical(O, qg):
     """M = 1 W4A16 from N = 8192 on: two weight rows per wave (w16_gemv1r_kernel) share the lane's
     activation reads; each row keeps its summation order, so the first 4096 rows equal the one-row
     kernel's (N = 4096) bit for bit, and all rows are within the fp32 K-term bound."""
-    n, k = 11008, 4096
+    n, k = TWO_ROWS_NK
     a, b = O.fill_uniform_step4(1, n, k, seed=3)
     bq = O.quantize(b, 2)
     a_d, b_d = dev(a), dev(bq)

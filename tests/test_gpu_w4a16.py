@@ -55,9 +55,34 @@ def test_w4a16_full_size_nmse(O, qg):
     assert O.nmse(c, O.gemm_fp32(a, b)) <= 5e-3
 
 
+UNALIGNED_A_SHAPE = (2, 24, 1024)
+SK_SMALL_M_SHAPE = (17, 64, 256)  # weights 4 B off 16-B alignment: neither w16d_ nor w16s_kernel takes them
+
+
+def test_w4a16_sk_kernel_small_m_weights_4B_aligned(O, qg):
+    """w16_sk_kernel with 32-token tiles (M <= 64), which aligned operands never reach (w16d_ / w16s_kernel come
+    first): weights that are only 4-B aligned, the smallest such shape — one workgroup, one 8-block chunk, three
+    activation parts."""
+    import torch
+    m, n, k = SK_SMALL_M_SHAPE
+    a, b = O.fill_uniform_step4(m, n, k, seed=17)
+    bq = O.quantize(b, 2)
+    raw = torch.zeros(bq.size + 16, dtype=torch.uint8, device="cuda")
+    w = raw[4 : 4 + bq.size]
+    w.copy_(dev(bq).ravel())
+    assert w.data_ptr() % 16 == 4
+    x = dev(a)
+    c = torch.empty((m, n), dtype=torch.float32, device="cuda")
+    lib = qg._lib.load()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = ctypes.c_void_p
+    assert lib.qg_gemm_w4a16(P(x.data_ptr()), P(w.data_ptr()), P(c.data_ptr()), m, n, k, st) == 0
+    check(O, host(c), a, bq, 2)
+
+
 def test_w4a16_unaligned_activation_generic_path(O, qg):
     import torch
-    m, n, k = 2, 24, 1024
+    m, n, k = UNALIGNED_A_SHAPE
     a, b = O.fill_uniform_step4(m, n, k)
     bq = O.quantize(b, 2)
     raw = torch.zeros(a.size + 1, dtype=torch.float32, device="cuda")
@@ -72,9 +97,11 @@ def test_w4a16_unaligned_activation_generic_path(O, qg):
     check(O, host(c), a, bq, 2)
 
 
-# Prefill (M > 8, K % 256 == 0): the split-K kernel (w16_sk_kernel) — K slices across workgroups
-# meet through the library's per-stream workspace; 16-token tiles (M <= 64) and 64-token tiles,
-# 64- and 128-row workgroups, ragged M and N, several slices per chunk count.
+# Prefill (M > 8, K % 256 == 0) on aligned operands, by what qg_w16_config names (tests/test_w16_shapes_cpu.py holds
+# the list to it): M <= 32 in one dispatch round runs w16d_kernel (no split, no workspace: (32, 4096, 4096),
+# (17, 300, 1024), (9, 33, 512)); 32 < M <= 64 w16s_kernel, K slices across workgroups meeting through the library's
+# per-stream workspace ((64, 2048, 2048) 4 slices, (40, 640, 14336) 28); M > 64 w16_sk_kernel with 64-token tiles,
+# 64- and 128-row workgroups, 8 and 2 slices, and one slice without a workspace ((65, 16, 256)). Ragged M and N.
 @pytest.mark.parametrize("t", [2, 8])
 @pytest.mark.parametrize("m,n,k", [(32, 4096, 4096), (17, 300, 1024), (64, 2048, 2048), (100, 256, 2048),
                                    (130, 2100, 512), (40, 640, 14336), (9, 33, 512), (65, 16, 256)])
@@ -95,7 +122,8 @@ def test_w16_prefill_split_k(O, qg, t, m, n, k):
                                    (100, 256, 2048), (130, 300, 1024), (257, 64, 4096),
                                    (64, 4096, 1024), (32, 8200, 2048)])  # the last two: 32-token tiles
 def test_w16_prefill_two_part_split_error(O, qg, t, m, n, k):
-    """From K = 1024 the prefill (w16s_kernel, M <= 64; w16_sk_kernel beyond) splits each activation into two round-to-nearest bf16
+    """From K = 1024 the prefill (w16d_kernel for M <= 32 at K <= 8192, w16s_kernel up to M = 64, w16_sk_kernel beyond)
+    splits each activation into two round-to-nearest bf16
     parts: |a - hi - mid| <= 2^-16 |a|. Against the exact (float64) product the error must stay within
     that representation error plus the fp32 accumulation's (K + 2) u share, 2^-16 + (K + 2) 2^-24 of
     sum_k |a_k w_k| (about half of the oracle-vs-kernel bound at K = 4096); a split that dropped the
@@ -115,10 +143,13 @@ def test_w16_prefill_two_part_split_error(O, qg, t, m, n, k):
     check(O, c.astype(np.float32), a, bq, t)
 
 
+SECOND_STREAM_SHAPE = (40, 1024, 4096)  # w16s_kernel, 8 slices (M <= 32 would run w16d_kernel: no workspace)
+
+
 def test_w16_prefill_split_k_second_stream(O, qg):
     """Each stream gets its own workspace; results are bit-identical across streams."""
     import torch
-    m, n, k = 32, 1024, 4096
+    m, n, k = SECOND_STREAM_SHAPE
     a, b = O.fill_uniform_step4(m, n, k, seed=5)
     bq = O.quantize(b, 2)
     ad, bd = dev(a), dev(bq)
@@ -131,11 +162,16 @@ def test_w16_prefill_split_k_second_stream(O, qg):
     check(O, c0, a, bq, 2)
 
 
+# w16s_kernel plans 16 x 3 tiles of 16 stages: 4 K slices through the workspace. (M <= 32 here would run w16d_kernel,
+# which takes none.) With the 64-byte workspace no split-K plan can be served: w16_mfma_kernel.
+WS_SHAPE = (40, 2048, 2048)
+
+
 @pytest.mark.parametrize("t", [2, 8])
 def test_w16_prefill_caller_workspace(O, qg, t):
     """qg_gemm_w{4,8}a16_ws: the caller's zeroed workspace, left zeroed; too small -> not used."""
     import torch
-    m, n, k = 24, 2048, 2048
+    m, n, k = WS_SHAPE
     a, b = O.fill_uniform_step4(m, n, k, seed=t)
     bq = O.quantize(b, t)
     lib = qg._lib.load()
@@ -159,6 +195,9 @@ def test_w16_prefill_caller_workspace(O, qg, t):
     check(O, outs[2], a, bq, t)
 
 
+TWO_THREAD_SHAPES = [(40, 1024, 4096), (64, 8192, 4096)]  # M > 32: both split K (M <= 32 runs w16d, no workspace)
+
+
 def test_w16_library_workspace_two_threads_one_stream(O, qg):
     """two host threads on ONE stream, the second asking for a larger split-K workspace
     than the first's (the library's per-stream buffer grows: stream sync + free of the old block).
@@ -168,7 +207,7 @@ def test_w16_library_workspace_two_threads_one_stream(O, qg):
 
     import torch
     lib = qg._lib.load()
-    shapes = [(40, 1024, 4096), (64, 8192, 4096)]  # M > 32: both split K (M <= 32 runs w16d, no workspace)
+    shapes = TWO_THREAD_SHAPES
     need = [lib.qg_gemm_w16_workspace_size(*s) for s in shapes]
     assert need[1] > max(need[0], 4 << 20)  # the second shape must grow the buffer past its first size
     data = []

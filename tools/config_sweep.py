@@ -21,6 +21,9 @@ ROW_K = (64, 96, 256, 512, 1024, 2048, 2304, 4096, 4128, 4352, 8192, 11008, 1433
 KQ_K = tuple(sorted({k for k in ROW_K if k % 256 == 0} | {768}))
 NS = (1, 300, 4096, 8192, 20000)
 MOE = ((1, 2, 4), (3, 2, 8), (64, 8, 128))  # (T, n_used, n_expert)
+W16_TYPES = (2, 8)
+W16_M = tuple(range(1, 9)) + (9, 16, 17, 24, 32, 33, 40, 64, 65, 100, 128, 512)
+W16_OFFS = ((0, 0), (0, 4), (0, 2), (4, 0))  # (a_off, b_off) bytes off 256-B alignment
 
 
 def main():
@@ -31,7 +34,7 @@ def main():
     import quant_gemm._lib as L
     lib = ctypes.CDLL(args.lib) if args.lib else L.load()
     for name in ("qg_debug_config", "qg_moe_config", "qg_moe_batch_config", "qg_moe_glu_config", "qg_moe_prefill_config",
-                 "qg_group_config", "qg_select_algo", "qg_set_group_affine", "qg_block_bytes"):
+                 "qg_group_config", "qg_w16_config", "qg_select_algo", "qg_set_group_affine", "qg_block_bytes"):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = L.SIGNATURES[name]
 
@@ -67,6 +70,14 @@ def main():
                         rc = lib.qg_group_config(arr, len(items), m, k, t, buf, 256)
                         print(f'qg_group_config affine={mode} {tag} {m} {k} {t} -> {rc} "{buf.value.decode()}"')
     lib.qg_set_group_affine(1)
+    # W4A16 / W8A16: the operand offsets reach the alignment rules of the dispatch, ws_bytes a caller workspace (none, any)
+    for t in W16_TYPES:
+        for k in ROW_K:
+            for n in NS:
+                for m in W16_M:
+                    for a_off, b_off in W16_OFFS:
+                        for ws in (0, 1 << 40):
+                            print(line("qg_w16_config", m, n, k, t, a_off, b_off, ws))
 
 
 if __name__ == "__main__":

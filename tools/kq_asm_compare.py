@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Compare the GEMV / K-quant / expert kernels of two `make asm` outputs (csrc/Makefile), instantiation by instantiation.
 
-    python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR
+    python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR [--drop KERNEL:POS ...]
+
+--drop w16s_kernel:2 leaves the parent's third integer / bool template argument of w16s_kernel out of the pairing key: for
+a result that removed that template parameter.
 
 Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_plan, qg_gemv,
 qg_gemv_q4_0 .. qg_gemv_q8_0, qg_capture_fuse and qg_w4a16 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
@@ -69,7 +72,9 @@ def resources(txt):
     return out
 
 
-def main(parent, result):
+def main(parent, result, drop=()):
+    """drop: (kernel name, position) pairs — that integer / bool template argument is left out of the PARENT's key (the
+    result removed the parameter, so its mangled names no longer carry it)."""
     side = []
     for d in (Path(parent), Path(result)):
         side.append({})
@@ -79,8 +84,12 @@ def main(parent, result):
                 continue
             k, r = kernels(asm), resources(d / f"{f}.hip.resource.txt")
             for s in k:
-                assert key(s) not in side[-1], (f, s, "two kernels with one key")
-                side[-1][key(s)] = (f, s, k[s], r[s])
+                kk = key(s)
+                for name, pos in drop if len(side) == 1 else ():
+                    if kk[0] == name:
+                        kk = kk[: 1 + pos] + kk[2 + pos :]
+                assert kk not in side[-1], (f, s, "two kernels with one key")
+                side[-1][kk] = (f, s, k[s], r[s])
     assert side[1].keys() <= side[0].keys(), ("only in the result", sorted(side[1].keys() - side[0].keys()))
     bad = 0
     for f in FILES:
@@ -104,4 +113,6 @@ def main(parent, result):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    drops = [(a.split(":")[0], int(a.split(":")[1])) for i, a in enumerate(sys.argv[1:]) if sys.argv[i] == "--drop"]
+    dirs = [a for i, a in enumerate(sys.argv[1:]) if a != "--drop" and sys.argv[i] != "--drop"]
+    sys.exit(main(*dirs[:2], drop=drops))
