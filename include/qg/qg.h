@@ -374,7 +374,8 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  * Prefill-size T of Q4_K / Q6_K experts: qg_gemm_w4a8_moe_prefill below (this entry streams the slot's whole
  * expert matrix for every slot); slots of different tokens sharing one pass over an expert they both chose, at decode
  * sizes: qg_gemm_w4a8_moe_batch below.
- * The gate and the up product of a Q4_K / Q6_K FFN block with their GLU in one launch: qg_gemm_w4a8_moe_glu below.
+ * The gate and the up product of a Q4_K / Q6_K FFN block with their GLU in one launch: qg_gemm_w4a8_moe_glu below; the
+ * down product with the router-weighted sum over the token's experts in one launch: qg_gemm_w4a8_moe_down below.
  * Not built: prefill-size T and shared passes for the five 32-element types, tiled-layout experts,
  * FP32 activations. */
 int qg_gemm_w4a8_moe(const void* A_q8_1, int a_rows, const void* B_experts, int n_expert, const int32_t* ids,
@@ -517,13 +518,70 @@ int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype
  * codes for the shape.
  * Standing against the three-kernel sequence (MI355X, uniform router): DESIGN.md 3f, profiles/moe_glu/.
  * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, a Q8_1-quantized output for the down
- * product, the weighted sum over experts after down, fused forms of the prefill and batch entries. */
+ * product, fused forms of the prefill and batch entries. (The weighted sum over experts after down:
+ * qg_gemm_w4a8_moe_down below.) */
 #define QG_GLU_REGLU  0   /* numbered as ggml's enum ggml_glu_op */
 #define QG_GLU_SWIGLU 2
 int qg_gemm_w4a8_moe_glu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
                          int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op,
                          qg_stream_t stream);
 int qg_moe_glu_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- down mul_mat_id with the weighted expert sum: the second half of an MoE FFN block in one launch ----
+ * sum_u w[t,u] * down_e(h[t,u]) is a mul_mat_id with one activation row per slot, the caller's multiply by the router
+ * weights and the caller's sum over the token's n_used slots. This entry replaces those kernels (qg_gemm_w4a8_moe at
+ * a_rows = n_used, which writes T * n_used * N floats that are read back once) for Q4_K / Q6_K experts. With
+ * qg_gemm_w4a8_moe_glu an MoE FFN block at decode is four calls: quantize, moe_glu, quantize, moe_down.
+ * Token t < T, slot u < n_used, e_u = ids[t * ids_stride + u]:
+ *   d_u[n] = sum_k B_experts[e_u][n][k] * A[t * n_used + u][k]
+ *   acc = +0.0f; for u = 0 .. n_used - 1 in ascending order, where 0 <= e_u < n_expert:
+ *       acc = acc + weights[t * w_stride + u] * d_u[n]
+ *   C[t * ldc + n] = acc                                                                      (n < N)
+ * A: block_q8_1 [T][n_used][K/32], one row per slot (there is no a_rows: the a_rows = n_used case of qg_gemm_w4a8_moe).
+ * B_experts, ids and ids_stride are those of qg_gemm_w4a8_moe; wtype QG_TYPE_Q4_K or QG_TYPE_Q6_K.
+ * weights: float in DEVICE memory, 4-B aligned, w_stride >= n_used floats between tokens. NULL: every weight is 1.0f,
+ *    the plain sum over the token's experts, bit-equal to passing ones (w_stride is then not looked at).
+ * C: float [T][ldc], ONE row per token (not per slot), ldc = 0 means N.
+ * Bits: d_u is the value qg_gemm_w4a8_moe(A, a_rows = n_used, ...) gives slot t * n_used + u at row n, bit for bit (the
+ * kernel runs the same decode GEMV body at the same LPR and ONE); the multiplication and the addition of the fold are
+ * each one rounded fp32 operation (no contraction), in ascending u as llama.cpp adds the experts. Two launches give
+ * identical bits.
+ * A slot whose id is outside [0, n_expert) reads no weight byte and contributes nothing: its weights value is not read,
+ * so an inf or a NaN there does not reach the output. A token with no id in range gets N times +0.0f.
+ * ONE launch, a single kernel node when captured. The host reads neither ids nor weights; no device allocation, no
+ * synchronisation: capture-safe, and a replayed graph follows the ids and the weights it finds in the buffers.
+ * Validation: the order of qg_gemm_w4a8_moe: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive multiple
+ * of 256 (32 where wtype is no super-block type) -> QG_ERR_BAD_K; wtype other than Q4_K / Q6_K (the five 32-element
+ * types among them) -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched; a null A, B_experts,
+ * ids or C -> QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A, ids and a non-null weights 4 B; B_experts 16 B for Q4_K,
+ * 2 B for Q6_K). Then ids_stride < n_used, n_expert < 1, ldc < 0 or 0 < ldc < N, w_stride < n_used with non-null
+ * weights -> QG_ERR_INVALID_ARG; then T > 65535 (the token is the grid's y; the number of slots is not bounded) or an
+ * expert stride off the weight alignment -> QG_ERR_UNSUPPORTED; then the entry's own refusals, QG_ERR_UNSUPPORTED with
+ * nothing launched: a shape that QG_ALGO_AUTO at M = 1 does not send to the type's decode GEMV; an LDS need beyond
+ * 160 KiB. The workgroup keeps the records of all n_used activation rows (336 B per 256 elements for Q4_K, 304 B for
+ * Q6_K) and n_used x RPB products: n_used * (K/256 * record + 4 RPB) bytes, RPB <= 64 the rows per workgroup
+ * (qg_moe_down_config). The largest K served, by n_used:
+ *   n_used      1       2      4      6      8     10     16     32
+ *   Q4_K   124672   62208  30976  20736  15360  12288   7680   3840
+ *   Q6_K   137728   68864  34304  22784  17152  13568   8448   4096
+ * qg_moe_down_config names the launch ("moe_down:q4k_gemv" / "moe_down:q6k_gemv", LPR, WGS and ONE: those of
+ * qg_moe_config for the same K and type; SW: the waves of a workgroup that stand side by side on the slots of one row
+ * group, the largest power of two <= min(n_used, WGS / 64); grid = ceil(N / RPB) x T with RPB = (WGS / 64 / SW) *
+ * (64 / LPR); lds), launch-free; the same status codes for the shape.
+ * Which to use (measured on an MI355X with a uniform router against qg_gemm_w4a8_moe plus torch's multiply and sum,
+ * DESIGN.md 3g, profiles/moe_down/ab_moe_down.txt): this entry at Qwen3-MoE's shape (N x K = 2048 x 768, 8 of 128
+ * experts), both types, T = 1 and T = 8 (0.64 .. 0.78 of the sequence's time captured, 0.65 .. 0.78 eager), and at
+ * Mixtral's (4096 x 14336, 2 of 8) at T = 1 (0.76 Q4_K, 0.89 Q6_K captured). It is NOT ahead at Mixtral's shape at
+ * T = 8, where the weight stream and not the launch count is the time: 1.05 (Q4_K) and 1.17 (Q6_K) times the
+ * sequence's time; keep qg_gemm_w4a8_moe and the caller's sum there. In all but one class the launch takes longer than
+ * the sequence's product launch alone (1.01 .. 1.40 of it captured): what it saves is the two elementwise kernels and
+ * the round trip of the T * n_used * N floats, not time in the product.
+ * Not built: the five 32-element types, FP32 input quantized in the prologue, a Q8_1-writing GLU ahead of it, fused
+ * forms of the prefill and batch entries. */
+int qg_gemm_w4a8_moe_down(const void* A_q8_1, const void* B_experts, int n_expert, const int32_t* ids, int64_t ids_stride,
+                          const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
+                          int wtype, qg_stream_t stream);
+int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -642,6 +700,16 @@ int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view
  * as_gate in type, ne or nb. */
 int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
                                 const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, qg_stream_t stream);
+/* The down product of an MoE FFN block with the weighted sum over the token's experts on views, mapped onto
+ * qg_gemm_w4a8_moe_down: out[t] = sum_u weights[t, u] * (as[ids[t, u]] x b[t, u]).
+ *   as, ids: as in qg_mul_mat_id_from_view; b: Q8_1, ne = [K, n_used, T], dense;
+ *   weights: NULL (every weight 1), or F32 with ne = [n_used, T] or [1, n_used, T] (ggml's router weights), the n_used
+ *            floats of a token dense, the token stride a multiple of 4 B;
+ *   out: F32, ne = [N, T], nb[0] = 4, nb[1] a multiple of 4 and >= 4 N.
+ * The refusals of qg_mul_mat_id_from_view, and QG_ERR_UNSUPPORTED for b with ne[1] != n_used, weights of another type
+ * or with strides the entry cannot express, out with ne[2] > 1; weights with other dims are QG_ERR_INVALID_ARG. */
+int qg_mul_mat_id_down_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                 const qg_tensor_view* weights, qg_tensor_view* out, qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

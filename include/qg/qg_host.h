@@ -64,6 +64,16 @@ int qg_gemm_w4a8_moe_glu_cpu(const void* A_q8_1, const void* B_gate, const void*
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                              int glu_op, int threads);
 
+/* Host twin of qg_gemm_w4a8_moe_down (qg.h): the same arguments with `ids` and `weights` in host memory, and `threads`
+ * as above. d_u has the bits of qg_gemm_w4a8_moe_cpu at a_rows = n_used; the fold is the same: acc = +0.0f, then
+ * acc = acc + weights[t * w_stride + u] * d_u in ascending u, one rounded fp32 operation each, an id outside
+ * [0, n_expert) left out with its weight unread; weights == NULL is every weight 1.0f. C is [T][ldc], one row per
+ * token. The same validation codes (wtype other than Q4_K / Q6_K is QG_ERR_UNSUPPORTED; no alignment is asked); no
+ * shape is unsupported. */
+int qg_gemm_w4a8_moe_down_cpu(const void* A_q8_1, const void* B_experts, int n_expert, const int32_t* ids,
+                              int64_t ids_stride, const float* weights, int64_t w_stride, float* C, int64_t ldc, int T,
+                              int n_used, int N, int K, int wtype, int threads);
+
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */
 int qg_gemm_fp32_cpu(const float* A, const float* B, float* C, int M, int N, int K);
 

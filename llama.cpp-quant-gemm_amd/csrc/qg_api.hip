@@ -11,6 +11,7 @@
 #include "../../include/qg/qg.h"
 #include "qg_kernels.hpp"
 #include "qg_moe_batch.hpp"
+#include "qg_moe_down.hpp"
 #include "qg_moe_glu.hpp"
 #include "qg_moe_prefill.hpp"
 #include "qg_q4k.hpp"
@@ -393,10 +394,10 @@ int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
     return QG_ERR_UNSUPPORTED;
 }
 
-// ---- mul_mat_id: the three expert entries and the fused gate / up entry ---------------------------------------
-// A call of qg_gemm_w4a8_moe, _moe_prefill, _moe_batch or _moe_glu under the names of qg.h (ws: the entries with a
-// plan; B_up, glu_op: _moe_glu, whose B is B_gate), a qg_moe*_config query of one (describe: name the launch there and
-// launch nothing), and what moe_front adds.
+// ---- mul_mat_id: the three expert entries, the fused gate / up entry and the down entry with the expert sum -----
+// A call of qg_gemm_w4a8_moe, _moe_prefill, _moe_batch, _moe_glu or _moe_down under the names of qg.h (ws: the entries
+// with a plan; B_up, glu_op: _moe_glu, whose B is B_gate; weights, w_stride: _moe_down, whose C has a row per token), a
+// qg_moe*_config query of one (describe: name the launch there and launch nothing), and what moe_front adds.
 struct MoeCall {
     const void* A; int a_rows;
     const void* B; int n_expert;
@@ -409,6 +410,7 @@ struct MoeCall {
     long estride;  // moe_front: bytes between experts
     int slots;     // moe_front: T * n_used
     const void* B_up; int glu_op;
+    const float* weights; int64_t w_stride;
 };
 
 // Bytes of a plan's workspace whose tile region is sized for tiles of min_r rows (qg_moe_plan.hpp).
@@ -420,20 +422,23 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 // What the entries check alike, in the order qg.h documents. rows_ok: the entry takes the 32-element types
 // (otherwise one of them is a type it does not take, checked at the 32-element granule as in run_product). min_r: 0,
 // or the entry runs a plan in a workspace sized for tiles of min_r rows. up: the entry has a second weights pointer,
-// B_up, checked beside B with the same mask.
+// B_up, checked beside B with the same mask. down: the entry is qg_gemm_w4a8_moe_down: weights stands beside the other
+// pointers (null allowed, 4 B otherwise), w_stride beside ids_stride, and the grid's y is the token, so T is what 65535
+// bounds (slots stays 0).
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
 //   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
 //   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
-int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false) {
+int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
     const bool ksb = is_sb_type(c.wtype);
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? 256 : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
-                            {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3}, {c.C, 0}});
+                            {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
+                             {down && c.weights ? c.weights : c.A, 3}, {c.C, 0}});
     if (rc != QG_GO) return rc;
     if ((c.a_rows != 1 && c.a_rows != c.n_used) || c.ids_stride < c.n_used || c.n_expert < 1 || c.ldc < 0 ||
-        (c.ldc > 0 && c.ldc < c.N))
+        (c.ldc > 0 && c.ldc < c.N) || (down && c.weights && c.w_stride < c.n_used))
         return QG_ERR_INVALID_ARG;
     if (min_r) {
         if (!c.ws) return QG_ERR_INVALID_ARG;
@@ -441,8 +446,8 @@ int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false) {
         if (c.ws_bytes < moe_ws_bytes(c.T, c.n_used, c.n_expert, min_r)) return QG_ERR_INVALID_ARG;
     }
     const int64_t slots = (int64_t)c.T * c.n_used;
-    if (slots > MOE_MAX_SLOTS || (min_r && c.n_expert > MOE_MAX_EXPERTS)) return QG_ERR_UNSUPPORTED;
-    c.slots = (int)slots;
+    if ((down ? c.T : slots) > MOE_MAX_SLOTS || (min_r && c.n_expert > MOE_MAX_EXPERTS)) return QG_ERR_UNSUPPORTED;
+    c.slots = down ? 0 : (int)slots;
     if (!c.ldc) c.ldc = c.N;
     c.estride = (long)c.N * (long)(c.K / block_elems(c.wtype)) * block_bytes(c.wtype);
     return ((uintptr_t)c.estride & wmask) != 0 ? QG_ERR_UNSUPPORTED : QG_GO;
@@ -512,6 +517,21 @@ int run_moe_glu(MoeCall& c) {
     a.ids_stride = (long)c.ids_stride; a.ldc = (long)c.ldc; a.estride = c.estride; a.arow = (long)(c.K / 32) * 36;
     a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots; a.glu_op = c.glu_op;
     return hip_status(launch_moe_glu(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_down, qg_moe_down_config: Q4_K / Q6_K, a_rows = n_used. Its own refusals: a shape off the decode
+// GEMV, the records of the token's n_used activation rows and its n_used x RPB products beyond the LDS.
+int run_moe_down(MoeCall& c) {
+    c.a_rows = c.n_used;
+    const int rc = moe_front(c, false, 0, false, true);
+    if (rc != QG_GO) return rc;
+    if (!moe_gemv_route(c) || moe_down_form(c.n_used, c.K, c.wtype).lds > MAX_LDS_BYTES) return QG_ERR_UNSUPPORTED;
+    MoeDownArgs a;
+    a.A = c.A; a.B = c.B; a.ids = c.ids; a.weights = c.weights; a.C = c.C;
+    a.ids_stride = (long)c.ids_stride; a.w_stride = (long)c.w_stride; a.ldc = (long)c.ldc; a.estride = c.estride;
+    a.arow = (long)(c.K / 32) * 36;
+    a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.T = c.T;
+    return hip_status(launch_moe_down(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
 // qg_moe*_config: the shape alone, as qg_debug_config: 256-B aligned stand-in pointers (a workspace of any size among
@@ -671,6 +691,53 @@ int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_v
     c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
     c.B_up = as_up->data; c.glu_op = glu_op;
     return run_moe_glu(c);
+}
+
+int qg_gemm_w4a8_moe_down(const void* A_q8_1, const void* B_experts, int n_expert, const int32_t* ids, int64_t ids_stride,
+                          const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
+                          int wtype, qg_stream_t stream) {
+    MoeCall c{A_q8_1, n_used, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, nullptr, 0,
+              (hipStream_t)stream};
+    c.weights = weights; c.w_stride = w_stride;
+    return run_moe_down(c);
+}
+
+int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_down, T, n_used, 1, N, K, wtype, buf, len);
+}
+
+int qg_mul_mat_id_down_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                 const qg_tensor_view* weights, qg_tensor_view* out, qg_stream_t stream) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    // as, b and ids go through the checks of qg_mul_mat_id_from_view beside a dense stand-in [N, n_used, T] for its
+    // output (this entry's has a row per token): every refusal of that entry's, then what is this entry's own
+    const int64_t n_used = ids ? ids->ne[0] : 0;
+    auto one = [](int64_t v) { return v == 1 || v == 0; };
+    if (!one(out->ne[2])) return QG_ERR_UNSUPPORTED;
+    qg_tensor_view slots = *out;
+    slots.ne[1] = n_used; slots.ne[2] = out->ne[1];
+    slots.nb[1] = (size_t)(out->ne[0] > 0 ? out->ne[0] : 0) * sizeof(float); slots.nb[2] = (size_t)n_used * slots.nb[1];
+    MoeCall c;
+    const int rc = mul_mat_id_view(as, b, ids, &slots, c);
+    if (rc != QG_GO) return rc;
+    if (c.a_rows != c.n_used) return QG_ERR_UNSUPPORTED;
+    if (c.T > 1 && out->nb[1] % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
+    c.ldc = c.T > 1 ? (int64_t)(out->nb[1] / sizeof(float)) : c.N;
+    c.weights = nullptr; c.w_stride = c.n_used;
+    if (weights) {
+        // F32 [n_used, T] or [1, n_used, T]: the router's weights as ggml keeps them
+        const int d = weights->ne[0] == 1 && weights->ne[1] == c.n_used && weights->ne[2] == c.T ? 1 : 0;
+        if (weights->type != QG_TYPE_F32) return QG_ERR_UNSUPPORTED;
+        if (weights->ne[d] != c.n_used || weights->ne[d + 1] != c.T) return QG_ERR_INVALID_ARG;
+        if (!one(weights->ne[d + 2]) || (d == 0 && !one(weights->ne[3]))) return QG_ERR_UNSUPPORTED;
+        if ((c.n_used > 1 && weights->nb[d] != sizeof(float)) || (c.T > 1 && weights->nb[d + 1] % sizeof(float) != 0))
+            return QG_ERR_UNSUPPORTED;
+        c.weights = (const float*)weights->data;
+        if (!c.weights) return QG_ERR_INVALID_ARG;
+        if (c.T > 1) c.w_stride = (int64_t)(weights->nb[d + 1] / sizeof(float));
+    }
+    c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
+    return run_moe_down(c);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -1,6 +1,7 @@
 // qg_q6k_gemv_body.inc — the body of the Q6_K decode GEMV, included as text into q6k_gemv_kernel (qg_q6k_gemv.hip,
 // where the work decomposition is described) and q6k_moe_body (qg_moe.hip) and
-// q6k_moeb_kernel (qg_moe_batch.hip) and q6k_glu_product[_staged] (qg_moe_glu.hip). Text and not a function they
+// q6k_moeb_kernel (qg_moe_batch.hip) and q6k_glu_product[_staged] (qg_moe_glu.hip) and q6k_down_stage /
+// q6k_down_product (qg_moe_down.hip). Text and not a function they
 // call: the compiler sees the same tokens in the same function as before, so the shipped code objects do not move
 // (DESIGN.md 3c).
 // Expects in scope: A, B (the operands), M, N, K, out, ldc, the template parameters or constants MT, LPR, WGS, SUMI,
@@ -9,18 +10,33 @@
 //   QG_KQ_ABLK(g)       the address of activation block g = m * K/32 + b in staging: `A + (long)g * 9` for dense rows,
 //                       the gathered row of tile position m in the expert-grouped GEMV (qg_moe_batch.hip)
 //   QG_KQ_OUT(m)        the output of token m at this lane's row: `C[m * ldc + row]`, the slot's row there
-// and one the shipped includers leave undefined:
+// and four the shipped includers leave undefined:
 //   QG_KQ_A_STAGED      defined: the LDS records already hold the activation row (an earlier pass of the same
 //                       workgroup staged it and a barrier has passed); the body loads its first unit and goes on
+//   QG_KQ_STAGE_ONLY    defined: the inclusion is the staging prologue alone, the M activation rows into the records
+//                       and its barrier: no weights, no row, no product (B, N, out, MT, SUMI, ONE are not needed)
+//   QG_KQ_ROW           the lane's output row, where it is not `tile * RPB + (tid >> 6) * RPW + lane / LPR` (a
+//                       workgroup whose waves share rows; tile is then not needed)
+//   QG_KQ_RECS          the first LDS record of the activation row(s) the product reads, where that is not the start
+//                       of the dynamic LDS (with QG_KQ_A_STAGED: the row of another slot)
     constexpr int RPW = 64 / LPR;
     constexpr int RPB = (WGS / 64) * RPW;  // rows per workgroup
+#ifdef QG_KQ_RECS
+    const uint32_t* const lds = QG_KQ_RECS;
+#else
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+#endif
 
     const int nb = K / QK, nsb = K / SB_ELEMS;
     const int U = 4 * nsb;  // units per row
     const int tid = threadIdx.x, lane = tid & 63, lir = lane % LPR;
+#ifndef QG_KQ_STAGE_ONLY
+#ifdef QG_KQ_ROW
+    const int row = QG_KQ_ROW;
+#else
     QG_KQ_DECLARE_TILE
     const int row = tile * RPB + (tid >> 6) * RPW + lane / LPR;
+#endif
     const bool row_ok = row < N;
     const uint8_t* wrow = B + (long)(row_ok ? row : 0) * ((long)nsb * Q6K_BYTES);
     // (units past the row's end are clamped to its last one: loaded, never used)
@@ -41,6 +57,7 @@
         dst[18] = s3[0]; dst[19] = s3[1]; dst[20] = s3[2];
         dst[21] = d1[0];
     };
+#endif
 
 #ifdef QG_KQ_A_STAGED
     uint32_t cur[Q6K_UNIT_DW];
@@ -72,8 +89,10 @@
     };
     uint32_t ab[9];
     if (tid < totb) load_ablk(tid, ab);
+#ifndef QG_KQ_STAGE_ONLY
     uint32_t cur[Q6K_UNIT_DW];
     load_unit(cur, lir);
+#endif
     if (tid < totb) put_ablk(tid, ab);
     for (int g = tid + WGS; g < totb; g += WGS) {
         load_ablk(g, ab);
@@ -82,6 +101,7 @@
     __syncthreads();
 #endif
 
+#ifndef QG_KQ_STAGE_ONLY
     float acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = 0.0f;
@@ -175,3 +195,4 @@
                 if (m < M) QG_KQ_OUT(m) = acc[m];
         }
     }
+#endif

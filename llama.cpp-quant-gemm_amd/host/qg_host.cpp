@@ -385,6 +385,39 @@ int qg_gemm_w4a8_moe_glu_cpu(const void* A, const void* B_gate, const void* B_up
     return QG_OK;
 }
 
+int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
+                              const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
+                              int wtype, int threads) {
+    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    // the order of qg_gemm_w4a8_moe_down
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % (ksb ? 256 : QK) != 0) return QG_ERR_BAD_K;
+    if (!ksb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
+    if (ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N) || (weights && w_stride < n_used))
+        return QG_ERR_INVALID_ARG;
+    const size_t arow = (size_t)(K / QK) * 36;
+    const size_t estride = (size_t)N * (size_t)(K / 256) * (size_t)(wtype == QG_TYPE_Q4_K ? FmtQ4_K::bytes : FmtQ6_K::bytes);
+    if (ldc == 0) ldc = N;
+    std::vector<float> d((size_t)N);
+    for (int t = 0; t < T; ++t) {
+        float* c = C + (int64_t)t * ldc;
+        for (int n = 0; n < N; ++n) c[n] = 0.0f;
+        for (int u = 0; u < n_used; ++u) {
+            const int e = ids[(int64_t)t * ids_stride + u];
+            if (e < 0 || e >= n_expert) continue;  // neither its weight nor a weight byte is read
+            const uint8_t* a = (const uint8_t*)A + ((size_t)t * n_used + (size_t)u) * arow;
+            const int rc = qg_gemm_w4a8_cpu_mt(a, (const uint8_t*)B + (size_t)e * estride, d.data(), 1, N, K, wtype, threads);
+            if (rc != QG_OK) return rc;
+            // each operation one rounded fp32 operation (-ffp-contract=off), as the GPU entry
+            const float w = weights ? weights[(int64_t)t * w_stride + u] : 1.0f;
+            for (int n = 0; n < N; ++n) c[n] = c[n] + w * d[n];
+        }
+    }
+    return QG_OK;
+}
+
 int qg_gemm_w4a8_q4_0_cpu(const void* A, const void* B, float* C, int M, int N, int K) {
     return qg_gemm_w4a8_cpu_mt(A, B, C, M, N, K, QG_TYPE_Q4_0, 1);
 }

@@ -226,9 +226,11 @@ def gemm_w4a8_grouped(activations_q, weights_q, Ns, M: int, K: int, wtype: int =
     return res
 
 
-def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: int, wtype: int, a_rows: int, out):
-    """What the three mul_mat_id wrappers check alike, after the weight type: the contiguous operands, n_expert,
-    ids_stride, ``out`` (allocated unless given) and its ldc."""
+def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: int, wtype: int, a_rows: int, out,
+                  per_token: bool = False):
+    """What the mul_mat_id wrappers check alike, after the weight type: the contiguous operands, n_expert,
+    ids_stride, ``out`` (allocated unless given) and its ldc. per_token: ``out`` is [T, N], a row per token
+    (gemm_w4a8_moe_down), not [T, n_used, N]."""
     be = block_elems(wtype)
     _require(K % be == 0, f"K must be divisible by {be}, got {K}")
     _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
@@ -244,6 +246,16 @@ def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: 
     ids_stride = ids.stride(0) if T > 1 else n_used
     _require(ids_stride >= n_used, "ids row stride below n_used")
     a, w = activation_q.contiguous(), experts_q.contiguous()
+    if per_token:
+        if out is None:
+            out = torch.empty((T, N), dtype=torch.float32, device=w.device)
+        else:
+            _require(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, N), "bad out tensor")
+            _require(out.device == w.device, "out must be on the experts' device")
+            _require(N <= 1 or out.stride(1) == 1, "bad out tensor: rows must be dense")
+        ldc = out.stride(0) if T > 1 else N
+        _require(ldc >= N, "bad out tensor: rows overlap")
+        return a, w, n_expert, ids_stride, out, ldc
     if out is None:
         out = torch.empty((T, n_used, N), dtype=torch.float32, device=w.device)
     else:
@@ -410,6 +422,45 @@ def moe_glu_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> st
     """The launch ``gemm_w4a8_moe_glu`` makes for this shape ("moe_glu:q4k_gemv LPR=.. WGS=.. ONE=.. grid=XxY lds=..", the
     LPR / WGS / ONE of ``moe_config``); nothing is launched. Raises where the shape is not served."""
     return _config("qg_moe_glu_config", T, n_used, N, K, wtype)
+
+
+def gemm_w4a8_moe_down(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor,
+                       weights: torch.Tensor | None, T: int, n_used: int, N: int, K: int, wtype: int = Q4_K,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """The second half of an MoE FFN block in ONE launch (qg_gemm_w4a8_moe_down): C[t, :] = sum over u, in ascending
+    order, of weights[t, u] * (experts_q[ids[t, u]] . activation_q[t, u]), float32 [T, N]. It replaces ``gemm_w4a8_moe``
+    at ``a_rows = n_used``, the multiply by the router weights and the sum over the token's experts.
+
+    ``activation_q``: Q8_1 [T, n_used, K/32, 36], one row per slot. ``experts_q``: [n_expert, N, K/256, block bytes] of
+    ``wtype``, Q4_K or Q6_K, dense. ``ids``: as ``gemm_w4a8_moe``; a slot whose id is outside [0, n_expert) contributes
+    nothing and its weight is not read. ``weights``: float32 CUDA tensor [T, n_used] (a view with a row stride is fine,
+    ``weights.stride(1) == 1``), or None for the plain sum (every weight 1). Neither ids nor weights is copied to the
+    host: a captured graph follows what each replay finds. ``out``: optional float32 [T, N] with ``out.stride(1) == 1``
+    and ``out.stride(0) >= N``. Every product has the bits ``gemm_w4a8_moe`` gives the slot; the fold is one rounded
+    fp32 multiplication and addition per slot. Shapes the entry does not serve raise."""
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the down entry with the expert sum takes Q4_K and Q6_K")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, n_used, out,
+                                                        per_token=True)
+    w_stride = n_used
+    if weights is not None:
+        _require(weights.is_cuda and weights.dtype == torch.float32 and weights.device == w.device,
+                 "weights must be a float32 tensor on the experts' device")
+        _require(weights.dim() == 2 and tuple(weights.shape) == (T, n_used) and (n_used <= 1 or weights.stride(1) == 1),
+                 "weights must be [T, n_used] with unit column stride")
+        w_stride = weights.stride(0) if T > 1 else n_used
+        _require(w_stride >= n_used, "weights row stride below n_used")
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_down(_ptr(a), _ptr(w), n_expert, _ptr(ids), ids_stride,
+                                                     None if weights is None else _ptr(weights), w_stride, _ptr(out), ldc,
+                                                     T, n_used, N, K, wtype, _stream(w.device)), "gemm_w4a8_moe_down")
+    return out
+
+
+def moe_down_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_down`` makes for this shape ("moe_down:q4k_gemv LPR=.. WGS=.. ONE=.. SW=.. grid=XxY
+    lds=..", the LPR / WGS / ONE of ``moe_config``, SW waves side by side on the slots of a row group, Y = T); nothing
+    is launched. Raises where the shape is not served."""
+    return _config("qg_moe_down_config", T, n_used, N, K, wtype)
 
 
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
@@ -808,5 +859,5 @@ __all__ = [
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
-    "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU",
+    "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
 ]

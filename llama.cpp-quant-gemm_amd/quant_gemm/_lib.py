@@ -43,6 +43,8 @@ SIGNATURES = {
     "qg_moe_batch_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_glu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, P], I),
     "qg_moe_glu_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_down": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
+    "qg_moe_down_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_workspace_size": ([I, I, I, I], SZ),
     "qg_gemm_w4a8_ws": ([P, P, P, I, I, I, I, P, SZ, P], I),
     "qg_repack_weights_bytes": ([I, I, I], SZ),
@@ -98,6 +100,7 @@ SIGNATURES = {
     "qg_mul_mat_id_from_view_ws": ([P, P, P, P, P, SZ, P], I),
     "qg_mul_mat_id_from_view_batch": ([P, P, P, P, P, SZ, P], I),
     "qg_mul_mat_id_glu_from_view": ([P, P, P, P, P, I, P], I),
+    "qg_mul_mat_id_down_from_view": ([P, P, P, P, P, P], I),
     "qg_validate_view_types": ([P, P, P, I, I, I], I),
     "qg_gemm_fp32": ([P, P, P, I, I, I, P], I),
     "qg_gguf_open": ([ctypes.c_char_p, ctypes.POINTER(P)], I),

@@ -110,6 +110,18 @@ def mul_mat_id_glu_from_ggml(gate: TensorView, up: TensorView, act: TensorView, 
                "qg_mul_mat_id_glu_from_view")
 
 
+def mul_mat_id_down_from_ggml(experts: TensorView, act: TensorView, ids: TensorView, weights: TensorView | None,
+                              out: TensorView) -> None:
+    """The down product of an MoE FFN block with the weighted sum over the token's experts on views
+    (qg_mul_mat_id_down_from_view): out[t] = sum_u weights[t, u] * (experts[ids[t, u]] x act[t, u]), Q4_K / Q6_K experts,
+    act [K, n_used, T], weights F32 [n_used, T] or [1, n_used, T] or None (every weight 1), out F32 [N, T]."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().qg_mul_mat_id_down_from_view(ctypes.byref(experts), ctypes.byref(act), ctypes.byref(ids),
+                                                        None if weights is None else ctypes.byref(weights),
+                                                        ctypes.byref(out), st),
+               "qg_mul_mat_id_down_from_view")
+
+
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:
     """include/llama_adapter.h:110-117."""
     return bool(_lib.load().qg_validate_view_types(ctypes.byref(act), ctypes.byref(w), ctypes.byref(out), ea, ew, eo))

@@ -21,6 +21,7 @@ SIGNATURES = {
     "qg_gemm_w4a8_cpu_mt": ([P, P, P, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_cpu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_down_cpu": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_fp32_cpu": ([P, P, P, I, I, I], I),
     "qg_quantize_row_q8_1_cpu": ([P, P, I64], I),
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
@@ -119,6 +120,29 @@ def gemm_w4a8_moe_glu(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, ids
     c = np.empty((t, n_used, n), np.float32)
     _ok(load().qg_gemm_w4a8_moe_glu_cpu(_p(a_q), _p(gate_q), _p(up_q), n_expert, _p(ids), ids_stride, _p(c), n, t, n_used, n,
                                         k, wtype, glu_op, threads), "gemm_w4a8_moe_glu_cpu")
+    return c
+
+
+def gemm_w4a8_moe_down(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, weights: np.ndarray | None, t: int,
+                       n_used: int, n: int, k: int, wtype: int = 12, threads: int = 1, ids_stride: int | None = None,
+                       w_stride: int | None = None) -> np.ndarray:
+    """C[t, n] of qg_gemm_w4a8_moe_down_cpu: token t = the sum over u, in ascending order, of weights[t, u] times the
+    product of activation row t * n_used + u with expert ids[t, u] of ``experts_q`` (n_expert Q4_K / Q6_K matrices).
+    ``ids``: int32 [t, ids_stride], ``weights``: float32 [t, w_stride] or None for ones (the strides default to the
+    arrays' row lengths); a slot whose id is outside [0, n_expert) contributes nothing and its weight is not read."""
+    a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    n_expert = experts_q.size // (n * (k // 256) * BLOCK_BYTES[wtype])
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if w_stride is None:
+            w_stride = weights.size // t if t else n_used
+    c = np.empty((t, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_down_cpu(_p(a_q), _p(experts_q), n_expert, _p(ids), ids_stride,
+                                         None if weights is None else _p(weights), w_stride or n_used, _p(c), n, t, n_used,
+                                         n, k, wtype, threads), "gemm_w4a8_moe_down_cpu")
     return c
 
 

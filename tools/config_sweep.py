@@ -33,8 +33,10 @@ def main():
     import quant_gemm
     import quant_gemm._lib as L
     lib = ctypes.CDLL(args.lib) if args.lib else L.load()
-    for name in ("qg_debug_config", "qg_moe_config", "qg_moe_batch_config", "qg_moe_glu_config", "qg_moe_prefill_config",
-                 "qg_group_config", "qg_w16_config", "qg_select_algo", "qg_set_group_affine", "qg_block_bytes"):
+    for name in ("qg_debug_config", "qg_moe_config", "qg_moe_batch_config", "qg_moe_glu_config", "qg_moe_down_config",
+                 "qg_moe_prefill_config", "qg_group_config", "qg_w16_config", "qg_select_algo", "qg_set_group_affine", "qg_block_bytes"):
+        if name == "qg_moe_down_config" and not hasattr(lib, name):
+            continue  # --lib: a build from before the entry
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = L.SIGNATURES[name]
 
@@ -51,6 +53,8 @@ def main():
                 for T, n_used, n_expert in MOE:
                     print(line("qg_moe_config", T, n_used, n, k, t))
                     print(line("qg_moe_glu_config", T, n_used, n, k, t))
+                    if hasattr(lib, "qg_moe_down_config"):
+                        print(line("qg_moe_down_config", T, n_used, n, k, t))
                     print(line("qg_moe_batch_config", T, n_used, n_expert, n, k, t))
                     print(line("qg_moe_prefill_config", T, n_used, n_expert, n, k, t))
     # grouped launches on addresses nothing dereferences: 2 and 8 equal items (an affine progression), one mixed-N group

@@ -6,9 +6,9 @@
 --drop w16s_kernel:2 leaves the parent's third integer / bool template argument of w16s_kernel out of the pairing key: for
 a result that removed that template parameter.
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_plan, qg_gemv,
+Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_down, qg_moe_plan, qg_gemv,
 qg_gemv_q4_0 .. qg_gemv_q8_0, qg_capture_fuse and qg_w4a16 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
-does not have is skipped there), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
+does not have is skipped there; one only the result has is a new file: NEW <file>, its kernels not paired), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
 numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file of the result and every pair
 that differs: REGS where the instruction sequence and the remarks are the parent's and only register numbers moved,
 DIFF otherwise; GONE <symbol> for a kernel of the parent the result no longer builds (an instantiation no shape
@@ -18,7 +18,7 @@ import sys
 from pathlib import Path
 
 FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_glu",
-         "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0", "qg_capture_fuse",
+         "qg_moe_down", "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0", "qg_capture_fuse",
          "qg_w4a16"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
@@ -81,6 +81,9 @@ def main(parent, result, drop=()):
         for f in FILES:
             asm = d / f"{f}-hip-amdgcn-amd-amdhsa-gfx950.s"
             if not asm.exists():
+                continue
+            if len(side) == 2 and not (Path(parent) / asm.name).exists():
+                print(f"NEW {f}: {len(kernels(asm))} kernels, none paired")
                 continue
             k, r = kernels(asm), resources(d / f"{f}.hip.resource.txt")
             for s in k:
