@@ -90,7 +90,18 @@ typedef struct {
     uint16_t d;          /* fp16 scale of the group scales */
 } qg_block_q6_K;
 
+/* ggml's block_mxfp4 (type 39): 32 elements, an E8M0 scale byte and 4-bit E2M1 codes in the Q4_0 nibble order:
+ *   element j (0..15) has the code qs[j] & 15, element j + 16 the code qs[j] >> 4
+ *   value = kv[code] * 2^(e - 128),  kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12}
+ * (the doubled E2M1 values, hence 128 and not 127; code 8 is the integer 0). 17 bytes, alignment 1: blocks, rows and
+ * expert matrices start at any byte. */
+typedef struct {
+    uint8_t e;       /* E8M0: the scale 2^(e - 128), fp32 bits e < 2 ? 0x00200000 << e : (e - 1) << 23 */
+    uint8_t qs[16];
+} qg_block_mxfp4;
+
 #ifdef __cplusplus
+static_assert(sizeof(qg_block_mxfp4) == 17 && alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");
 static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");
@@ -100,6 +111,7 @@ static_assert(sizeof(qg_block_q5_1) == 24, "block_q5_1 must be 24 bytes");
 static_assert(sizeof(qg_block_q8_0) == 34, "block_q8_0 must be 34 bytes");
 static_assert(sizeof(qg_block_q8_1) == 36, "block_q8_1 must be 36 bytes");
 #else
+_Static_assert(sizeof(qg_block_mxfp4) == 17 && _Alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 _Static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 _Static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");
 _Static_assert(sizeof(qg_block_q4_0) == 18, "block_q4_0 must be 18 bytes");

@@ -41,7 +41,8 @@ typedef enum {
     QG_TYPE_Q8_1 = 9,
     QG_TYPE_Q4_K = 12, /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
     QG_TYPE_Q6_K = 14, /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
-    QG_TYPE_I32 = 26   /* int32 elements: the ids view of qg_mul_mat_id_from_view, nothing else */
+    QG_TYPE_I32 = 26,  /* int32 elements: the ids view of qg_mul_mat_id_from_view, nothing else */
+    QG_TYPE_MXFP4 = 39 /* 32-element blocks of 17 B, E8M0 scale and E2M1 codes (qg/blocks.h); see "MXFP4 weights" below */
 } qg_type;
 
 typedef enum {
@@ -131,6 +132,35 @@ int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, 
  * parities); QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace ->
  * QG_ERR_UNSUPPORTED. Every other entry that takes a wtype returns QG_ERR_UNSUPPORTED for it, as for Q4_K,
  * and qg_tile_weights_bytes / qg_repack_weights_bytes return 0. */
+
+/* ---- MXFP4 weights (wtype == QG_TYPE_MXFP4) -------------------------------------------------
+ * B: block_mxfp4[N][K/32], ggml's bytes (qg/blocks.h), rows dense: 17 bytes per 32 elements, one E8M0 scale byte e
+ * and 16 bytes of 4-bit codes in the Q4_0 nibble order. A code indexes
+ *   kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12}     (the doubled E2M1 values; code 8 is 0)
+ * and scale(e) is the fp32 with bits e < 2 ? 0x00200000 << e : (e - 1) << 23, i.e. 2^(e - 128) for all 256 values of
+ * e (e = 0, 1: the subnormals 2^-128, 2^-127; e = 255: 2^127; there is no NaN code). qg_dequantize gives
+ * float(kv[code]) * scale(e): exact for every (code, e), +0.0f for code 8.
+ * The product of block b of a weight row with Q8_1 block b of the activation row:
+ *   sumi(m, n, b) = sum_j kv[code_j] * a_j                       (int32, exact; |sumi| <= 32 * 12 * 128 < 2^24)
+ *   C(m, n) = sum_b (d_a * scale(e)) * float(sumi)               (the multiplications in that order, each rounded)
+ * The Q8_1 block's stored sum s_a is not used. The order of the additions is the kernel's; each output is within
+ * 2 * (K/32 + W + 2) * 2^-24 * sum_b |term| of the exact value, W = 0 for the decode GEMV and the host twin and
+ * W = 8 for the MFMA prefill (the K-slice partials it chains per output; MXFP4_MMQ_W in csrc/qg_mxfp4.hpp), and two
+ * launches give identical bits. fp32 subnormals are kept: where a term or d_a * scale(e) lies below 2^-126 the
+ * bound gains 2^-149 per term. Overflow (large e with large d_a * sumi) gives what fp32 gives.
+ * Taken by: qg_gemm_w4a8, qg_gemm_w4a8_ex, qg_gemm_w4a8_ldc, qg_debug_sumi (sumi[M][N][K/32] from the product's own
+ * instantiation), qg_debug_config, qg_select_algo, qg_dequantize, qg_gemm_w4a8_from_view (weights view:
+ * nb[0] = 17, ne[0] = K, dense rows), qg_gemm_w4a8_f32 with a workspace, and qg_gemm_w4a8_moe /
+ * qg_mul_mat_id_from_view (family "moe:mxfp4_gemv"; the expert stride N * K/32 * 17 is any number of bytes).
+ * QG_ALGO_AUTO: the decode GEMV ("mxfp4_gemv") for M <= 8, the MFMA prefill ("mxfp4_mmq") from M = 9 on; both may
+ * be forced (the GEMV only for M <= 8 and while its LDS records, 48 B per token and block, fit 160 KiB:
+ * M * K <= 109216 elements). A captured MXFP4 GEMV is a plain kernel node: the capture-time merge never considers it.
+ * Validation: K not a positive multiple of 32 -> QG_ERR_BAD_K; A not 4-B aligned -> QG_ERR_ALIGN; B has NO alignment
+ * requirement (17-B blocks start at any byte: the kernels read aligned dwords and realign them, and read nothing
+ * outside the tensor); QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace
+ * -> QG_ERR_UNSUPPORTED. Every other entry that takes a wtype (tiled, repacked, prepacked, padded, grouped,
+ * strided-batched, _ws, qg_quantize, the weight-major qg_gemm_q*, qg_gemm_w4a8_moe_prefill, _batch, _glu, _down)
+ * returns QG_ERR_UNSUPPORTED for it and launches nothing. There is no MXFP4 quantizer. */
 
 /* The Solution entry point of the definition gemm_q4_0_q8_1_w4a8
  * (schemas/definitions/gemm/gemm_q4_0_q8_1_w4a8.json:35-53: inputs A_q8_1[M][K/32], B_q4_0[N][K/32],
@@ -344,7 +374,7 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  *   e = ids[t * ids_stride + u]
  *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k]      (n < N)
  * B_experts: n_expert dense matrices [N][K/bs] of `wtype`, one after another (ggml's [K, N, n_expert]); any of
- *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K (bs = 256).
+ *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K (bs = 256), MXFP4 (bs = 32, 17-byte blocks: experts at any byte).
  * A: block_q8_1 [T][a_rows][K/32], a_rows == 1 (gate / up: one row per token, shared by its slots) or
  *    a_rows == n_used (down: one row per slot).
  * ids: int32 in DEVICE memory, read by the kernel; ids_stride >= n_used elements between tokens (ggml's top-k
@@ -360,13 +390,14 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  * C_row, 1, N, K, wtype, stream) called eagerly, so each inherits that product's documented bound; two launches
  * give identical bits.
  * Served shapes: those where QG_ALGO_AUTO at M = 1 picks the decode GEMV of the type ("gemv", "q4k_gemv",
- * "q6k_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32; LDS records of the activation
- * row beyond 160 KiB (Q4_K: K > 124672, Q6_K: K > 137728, the 32-element types: K > 93568); an expert stride
+ * "q6k_gemv", "mxfp4_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32 (the five 32-element types;
+ * MXFP4 takes any K/32); LDS records of the activation
+ * row beyond 160 KiB (Q4_K: K > 124672, Q6_K: K > 137728, MXFP4: K > 109216, the 32-element types: K > 93568); an expert stride
  * N * K/bs * block_bytes off the kernel's weight alignment; more than 65535 slots.
  * Validation, in the order of every entry: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive
  * multiple of bs -> QG_ERR_BAD_K; wtype -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched;
  * a null pointer -> QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A and ids 4 B; B 4 B for the 32-element types,
- * 16 B for Q4_K, 2 B for Q6_K). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
+ * 16 B for Q4_K, 2 B for Q6_K, none for MXFP4). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
  * 0 < ldc < N -> QG_ERR_INVALID_ARG (after the precheck: an empty call is a no-op whatever they are), then the
  * unsupported shapes above.
  * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
@@ -761,7 +792,7 @@ void qg_set_capture_fusion(int on);
 void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
-int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 0 if unknown */
+int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 17 for MXFP4, 0 if unknown */
 int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K / Q6_K, 0 if unknown */
 const char* qg_version(void);
 

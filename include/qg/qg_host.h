@@ -42,7 +42,9 @@ int qg_gemm_w8a8_cpu(const void* A_q8_1, const void* B_q8_0, float* C, int M, in
  * (<= 0: one). Also QG_TYPE_Q4_K (K % 256 == 0, else QG_ERR_BAD_K): the Q4_K product contract of qg.h,
  * one dot and one min accumulator per super-block in sub-block order, super-blocks summed in order.
  * And QG_TYPE_Q6_K (K % 256 == 0, else QG_ERR_BAD_K): the Q6_K product contract of qg.h, isum in int32, one
- * fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order. Bits are
+ * fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order.
+ * And QG_TYPE_MXFP4 (K % 32 == 0): the MXFP4 product contract of qg.h, sumi in int32, (d_a * scale(e)) * float(sumi)
+ * per block, one fp32 accumulator per output, blocks in order (W = 0). Bits are
  * identical for every thread count (threads split the weight rows only). */
 int qg_gemm_w4a8_cpu_mt(const void* A_q8_1, const void* B, float* C, int M, int N, int K, int wtype, int threads);
 
@@ -76,6 +78,10 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A_q8_1, const void* B_experts, int n_e
 
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */
 int qg_gemm_fp32_cpu(const float* A, const float* B, float* C, int M, int N, int K);
+
+/* Host twin of qg_dequantize for QG_TYPE_MXFP4: k elements (a multiple of 32, else QG_ERR_BAD_K) of block_mxfp4 ->
+ * y[i] = float(kv[code]) * scale(e), exact for every (code, e), +0.0f for code 8 (qg.h, "MXFP4 weights"). */
+int qg_dequantize_row_mxfp4_cpu(const void* x, float* y, int64_t k);
 
 /* quantize_row_q8_1_ref / quantize_row_q4_0_ref (include/quantize.h:165-193, 35-70). */
 int qg_quantize_row_q8_1_cpu(const float* x, void* y, int64_t k);

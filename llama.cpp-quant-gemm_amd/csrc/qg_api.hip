@@ -14,6 +14,7 @@
 #include "qg_moe_down.hpp"
 #include "qg_moe_glu.hpp"
 #include "qg_moe_prefill.hpp"
+#include "qg_mxfp4.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
 
@@ -30,6 +31,7 @@ int block_bytes(int t) {
         case QG_TYPE_Q8_1: return 36;
         case QG_TYPE_Q4_K: return 144;
         case QG_TYPE_Q6_K: return 210;
+        case QG_TYPE_MXFP4: return MXFP4_BYTES;
     }
     return 0;
 }
@@ -54,11 +56,19 @@ bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
 bool is_q6k_type(int t) { return t == QG_TYPE_Q6_K; }
 bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t); }
 
+// MXFP4 (32 elements in 17 bytes): a route of its own beside the 32-element families and the super-block types,
+// taken by the same entries as the latter (run_product with sb_ok) and by qg_gemm_w4a8_moe; is_weight_type does not
+// know it, so every entry that tests that alone refuses it.
+bool is_mxfp4_type(int t) { return t == QG_TYPE_MXFP4; }
+// the types with a route of their own: their kernels, their K granule, their weight alignment
+bool is_routed_type(int t) { return is_sb_type(t) || is_mxfp4_type(t); }
+
 int block_elems(int t) { return is_sb_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
 
-// Weight pointer alignment of a super-block type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
-// super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load.
-uintptr_t sb_weight_mask(int t) { return is_q6k_type(t) ? 1u : 15u; }
+// Weight pointer alignment of a routed type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
+// super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load; an
+// MXFP4 block is 17 B of bytes, so there is no requirement at all.
+uintptr_t sb_weight_mask(int t) { return is_mxfp4_type(t) ? 0u : is_q6k_type(t) ? 1u : 15u; }
 
 // ---- the one ordered precheck ------------------------------------------------------------------------------
 // The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
@@ -198,6 +208,11 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
 #ifndef QG_Q6K_GEMV_MAXM
 #define QG_Q6K_GEMV_MAXM 8
 #endif
+// MXFP4 keeps the threshold (profiles/mxfp4/ab_mxfp4_threshold.txt, N = K = 4096, each kernel forced): M = 5 GEMV
+// 5.95 us, MFMA 12.04; M = 8 GEMV 6.99, MFMA 12.08.
+#ifndef QG_MXFP4_GEMV_MAXM
+#define QG_MXFP4_GEMV_MAXM 8
+#endif
 struct SbRoute {
     bool (*gemv_eligible)(const GemmArgs&);
     hipError_t (*launch_gemv)(const GemmArgs&, hipStream_t);
@@ -209,15 +224,18 @@ constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K
     {q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, QG_Q4K_GEMV_MAXM},
     {q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, QG_Q6K_GEMV_MAXM},
 };
-// the route of a super-block type (is_sb_type holds)
-const SbRoute& sb_route(int t) { return SB_ROUTES[is_q6k_type(t) ? 1 : 0]; }
+// The third route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
+constexpr SbRoute MXFP4_ROUTE = {mxfp4_gemv_eligible, launch_mxfp4_gemv, mxfp4_mmq_eligible, launch_mxfp4_mmq,
+                                 QG_MXFP4_GEMV_MAXM};
+// the route of a routed type (is_routed_type holds)
+const SbRoute& sb_route(int t) { return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_q6k_type(t) ? 1 : 0]; }
 
 int select_algo_sb(const GemmArgs& g) {
     const SbRoute& r = sb_route(g.wtype);
     return g.M <= r.maxm && r.gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
 }
 
-// A super-block type after the precheck.
+// A super-block type, or MXFP4, after the precheck.
 int run_sb(GemmArgs& g, int algo, hipStream_t st) {
     const SbRoute& r = sb_route(g.wtype);
     if (algo == QG_ALGO_RAGGED || algo == QG_ALGO_GENERIC) return QG_ERR_UNSUPPORTED;
@@ -227,11 +245,11 @@ int run_sb(GemmArgs& g, int algo, hipStream_t st) {
     return QG_ERR_INVALID_ARG;
 }
 
-// The quantized product: one precheck, then the 32-element families or the super-block route by the weight
-// type's block size. sb_ok = false: the entries that refuse the super-block types (qg.h) -- such a type is then
+// The quantized product: one precheck, then the 32-element families or the route of a super-block type or of MXFP4
+// by the weight type. sb_ok = false: the entries that refuse the routed types (qg.h) -- such a type is then
 // one like any other they do not take, checked at the 32-element granule.
 int run_product(GemmArgs& g, int algo, hipStream_t st, bool sb_ok = true) {
-    const bool ksb = sb_ok && is_sb_type(g.wtype);
+    const bool ksb = sb_ok && is_routed_type(g.wtype);
     // 32-element families: fp16 fields, 2-byte alignment is the floor; super-block types: 4-B activation records,
     // weights by the type (sb_weight_mask)
     const int rc = precheck({g.M, g.N}, g.K, ksb ? block_elems(g.wtype) : 32, ksb || is_weight_type(g.wtype),
@@ -243,7 +261,7 @@ int run_product(GemmArgs& g, int algo, hipStream_t st, bool sb_ok = true) {
 
 // what QG_ALGO_AUTO dispatches to (qg_select_algo): the same routing
 int select_product_algo(const GemmArgs& g) {
-    const bool ksb = is_sb_type(g.wtype);
+    const bool ksb = is_routed_type(g.wtype);
     if (!(ksb || is_weight_type(g.wtype)) || g.K <= 0 || g.K % block_elems(g.wtype) != 0) return -1;
     if (!ksb) return select_algo(g);
     return select_algo_sb(g);
@@ -350,14 +368,14 @@ size_t fused_workspace_bytes(int M, int K) { return M > 0 && K > 0 ? (size_t)M *
 // the Q8_1 product (same bytes, so the same results); without a workspace, fused GEMV launches
 // over row chunks (the weights are streamed once per chunk).
 int run_fused(GemmArgs g, void* ws, size_t ws_bytes, hipStream_t st) {
-    const bool ksb = is_sb_type(g.wtype);
+    const bool ksb = is_routed_type(g.wtype);
     const size_t es = g.ain == AIN_F32 ? 4 : 2;
     const int rc = precheck({g.M, g.N}, g.K, ksb ? block_elems(g.wtype) : 32, ksb || is_weight_type(g.wtype),
                             {{g.A, ksb ? 3 : es - 1}, {g.B, ksb ? sb_weight_mask(g.wtype) : 1u}, {g.C, 0}});
     if (rc != QG_GO) return rc;
     const bool vec_ok = ((uintptr_t)g.A & 15) == 0;
     const bool ws_ok = ws && ws_bytes >= fused_workspace_bytes(g.M, g.K);
-    // the super-block types have no fused prologue: only FP32 rows through the caller's workspace, then the Q8_1 product on it
+    // the super-block types and MXFP4 have no fused prologue: only FP32 rows through the caller's workspace, then the Q8_1 product on it
     if (ksb && (g.ain != AIN_F32 || !ws_ok)) return QG_ERR_UNSUPPORTED;
     if (!ksb && g.M <= 4 && vec_ok && gemv_eligible(g)) return hip_status(launch_gemv(g, st));
     if (ws_ok) {
@@ -431,9 +449,10 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
 int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    const bool ksb = is_sb_type(c.wtype);
+    // (MXFP4 is a type of qg_gemm_w4a8_moe alone: where the 32-element types are refused, it is refused as they are)
+    const bool ksb = is_sb_type(c.wtype) || (rows_ok && is_mxfp4_type(c.wtype));
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
-    const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? 256 : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
+    const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
                             {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
                              {down && c.weights ? c.weights : c.A, 3}, {c.C, 0}});
     if (rc != QG_GO) return rc;
@@ -465,7 +484,7 @@ template <class KernArgs> KernArgs moe_kernel_args(const MoeCall& c) {
 // AUTO at M = 1 sends this (N, K, type) to the type's decode GEMV: the body the two decode entries run per slot
 bool moe_gemv_route(const MoeCall& c) {
     const GemmArgs q = product_args(c.A, c.B, c.C, 1, c.N, c.K, c.wtype);
-    return is_sb_type(c.wtype) ? select_algo_sb(q) == QG_ALGO_GEMV : select_algo(q) == QG_ALGO_GEMV && gemv_eligible(q);
+    return is_routed_type(c.wtype) ? select_algo_sb(q) == QG_ALGO_GEMV : select_algo(q) == QG_ALGO_GEMV && gemv_eligible(q);
 }
 
 // qg_gemm_w4a8_moe, qg_moe_config. Its own refusals: a shape off the decode GEMV, LDS records beyond 160 KiB.
@@ -550,7 +569,7 @@ int mul_mat_id_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_
                     MoeCall& c) {
     if (!as || !b || !ids || !out) return QG_ERR_INVALID_ARG;
     if (b->type != QG_TYPE_Q8_1 || ids->type != QG_TYPE_I32 || out->type != QG_TYPE_F32 ||
-        !(is_weight_type(as->type) || is_sb_type(as->type)))
+        !(is_weight_type(as->type) || is_routed_type(as->type)))
         return QG_ERR_UNSUPPORTED;
     auto one = [](int64_t v) { return v == 1 || v == 0; };
     if (!one(as->ne[3]) || !one(b->ne[3]) || !one(ids->ne[2]) || !one(ids->ne[3]) || !one(out->ne[3])) return QG_ERR_UNSUPPORTED;
@@ -1053,7 +1072,7 @@ int qg_gemm_w8a8(const void* A, const void* B, float* C, int M, int N, int K, qg
 }
 
 int qg_quantize(int type, int variant, const float* x, void* y, int64_t k, qg_stream_t stream) {
-    const bool type_ok = block_bytes(type) != 0 && !is_sb_type(type);  // (no Q4_K / Q6_K quantizer)
+    const bool type_ok = block_bytes(type) != 0 && !is_routed_type(type);  // (no Q4_K / Q6_K / MXFP4 quantizer)
     const bool variant_ok = variant == 0 || (variant == 1 && type == QG_TYPE_Q8_1) ||
                             (variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0));
     const int rc = precheck_count(k, 32, type_ok && variant_ok, {{x, 3}, {y, type == QG_TYPE_Q8_1 ? 3u : 1u}});
@@ -1072,8 +1091,9 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
     const int be = is_sb_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
-    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, 1}, {y, 3}});
+    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, is_mxfp4_type(type) ? 0u : 1u}, {y, 3}});
     if (rc != QG_GO) return rc;
+    if (is_mxfp4_type(type)) return hip_status(launch_dequantize_mxfp4(x, y, k / 32, (hipStream_t)stream));
     if (is_q6k_type(type)) return hip_status(launch_dequantize_q6k(x, y, k / 256, (hipStream_t)stream));
     if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));
@@ -1115,7 +1135,7 @@ int qg_gemm_w4a8_from_view(const qg_tensor_view* act, const qg_tensor_view* w, q
         else if (strcmp(kernel_type, "ragged") == 0) algo = QG_ALGO_RAGGED;
         else return QG_ERR_INVALID_ARG;
     }
-    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !(is_weight_type(w->type) || is_sb_type(w->type)))
+    if (act->type != QG_TYPE_Q8_1 || out->type != QG_TYPE_F32 || !(is_weight_type(w->type) || is_routed_type(w->type)))
         return QG_ERR_UNSUPPORTED;
     int64_t M, N, K;
     const int rc = view_dims(act, w, out, M, N, K, block_elems(w->type));  // super-block types: K % 256

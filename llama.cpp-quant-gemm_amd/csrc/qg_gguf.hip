@@ -115,12 +115,13 @@ uint64_t tensor_bytes(uint32_t t, const int64_t ne[4], uint32_t n_dims) {
         case QG_TYPE_F32: return n * 4;
         case QG_TYPE_F16: return n * 2;
     }
-    // the types this reader serves: the 32-element blocks and Q4_K (144-B super-blocks of 256). The reader's own
+    // the types this reader serves: the 32-element blocks, MXFP4 (17-B blocks of 32, what the gpt-oss expert tensors
+    // are stored as) and Q4_K (144-B super-blocks of 256). The reader's own
     // list, not every type qg_block_bytes knows: a Q6_K tensor stays listed with nbytes == 0 and is not readable
     // (lifting that is a follow-up of its own, DESIGN.md "Q6_K")
     switch (t) {
         case QG_TYPE_Q4_0: case QG_TYPE_Q4_1: case QG_TYPE_Q5_0: case QG_TYPE_Q5_1: case QG_TYPE_Q8_0: case QG_TYPE_Q8_1:
-        case QG_TYPE_Q4_K: break;
+        case QG_TYPE_Q4_K: case QG_TYPE_MXFP4: break;
         default: return 0;
     }
     const int bb = qg_block_bytes((int)t), be = qg_block_elems((int)t);
@@ -171,6 +172,8 @@ int parse(qg_gguf* g) {
         t.nbytes = tensor_bytes(t.type, t.ne, t.n_dims);
         // a Q4_K row is whole super-blocks: ggml cannot have written anything else
         if (t.type == QG_TYPE_Q4_K && r.ok && t.ne[0] % 256 != 0) return QG_ERR_INVALID_ARG;
+        // an MXFP4 row is whole 32-element blocks
+        if (t.type == QG_TYPE_MXFP4 && r.ok && t.ne[0] % 32 != 0) return QG_ERR_INVALID_ARG;
         g->tensors.push_back(std::move(t));
     }
     if (!r.ok) return QG_ERR_INVALID_ARG;

@@ -1,5 +1,5 @@
 // qg_moe.hip — the expert-indexed decode GEMV (qg_gemm_w4a8_moe, ggml's mul_mat_id), families "moe:gemv",
-// "moe:q4k_gemv", "moe:q6k_gemv".
+// "moe:q4k_gemv", "moe:q6k_gemv", "moe:mxfp4_gemv".
 //
 // One launch computes the T * n_used expert products of a decode step: blockIdx.y is the slot s = t * n_used + u,
 // blockIdx.x its row tile. The workgroup reads its expert id e = ids[t * ids_stride + u] from device memory with one
@@ -13,6 +13,9 @@
 //   * Q4_K / Q6_K: q4k_moe_body / q6k_moe_body<LPR, WGS, ONE> (below: the shipped kernels' bodies at one activation
 //     row, the same text included: qg_q4k_gemv_body.inc, qg_q6k_gemv_body.inc), the single call's LPR, WGS and ONE
 //     (kq_gemv_form, qg_kq_launch.hpp).
+//   * MXFP4: mxfp4_moe_body<LPR, WGS, ONE> (qg_mxfp4_gemv_body.inc at one activation row), the single call's form for
+//     K / 32 units (kq_gemv_form_units). The expert stride N * K/32 * 17 is any number of bytes: the body's loads are
+//     realigned by each block's own address, so an expert at any byte offset is read as the single call reads it.
 // So every slot's outputs are bit-identical to the eager qg_gemm_w4a8 on that slot's operands.
 // An id outside [0, n_expert) is a workgroup-uniform branch taken before any weight address is formed: the
 // workgroup stores +0.0f to its rows of the slot and returns.
@@ -20,6 +23,7 @@
 #include "../../include/qg/qg.h"
 #include "qg_gemv_impl.hpp"
 #include "qg_kq_launch.hpp"
+#include "qg_mxfp4.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
 
@@ -46,6 +50,15 @@ __device__ __forceinline__ void q6k_moe_body(const uint32_t* __restrict__ A, con
     constexpr bool SUMI = false;
     constexpr long ldc = 0;
 #include "qg_q6k_gemv_body.inc"
+}
+
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ void mxfp4_moe_body(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                               void* __restrict__ out, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    constexpr long ldc = 0;
+#include "qg_mxfp4_gemv_body.inc"
 }
 #undef QG_KQ_OUT
 #undef QG_KQ_ABLK
@@ -103,6 +116,7 @@ __global__ __launch_bounds__(WGS) void kq_moe_kernel(const MoeArgs a) {
     MoeSlot s;
     if (!moe_slot<WGS>(a, RPB, tile, s)) return;
     if constexpr (WT == QG_TYPE_Q4_K) q4k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
+    else if constexpr (WT == QG_TYPE_MXFP4) mxfp4_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
     else q6k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
 }
 
@@ -148,12 +162,14 @@ template <int F> hipError_t moe_row(const Launch& L) {
     });
 }
 
+// (MXFP4: a block per unit and per LDS record, where the super-block types have 64 elements and a super-block)
 template <int WT> hipError_t moe_kq_launch(const Launch& L) {
-    return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+    constexpr bool MX = WT == QG_TYPE_MXFP4;
+    return kq_gemv_form_units(MX ? (L.a.K / QK + MXFP4_UB - 1) / MXFP4_UB : L.a.K / 64, [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
-        const size_t lds = (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const size_t lds = MX ? (size_t)(L.a.K / QK) * MXFP4_REC_DW * 4 : (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
         if (L.describe) {
-            describe_line(L.describe, L.describe_len, "moe:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), LPR, WGS,
+            describe_line(L.describe, L.describe_len, "moe:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", MX ? "mxfp4" : kq_family(WT), LPR, WGS,
                           (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
             return hipSuccess;
         }
@@ -165,9 +181,9 @@ template <int WT> hipError_t moe_kq_launch(const Launch& L) {
 }  // namespace
 
 // The row types' LDS records of one activation row must fit (the single call has no such test at M <= 2 and fails
-// in the launch instead); the super-block types' bound is their gemv_eligible.
+// in the launch instead); the super-block types' and MXFP4's bound is their gemv_eligible.
 bool moe_lds_ok(int wtype, int K) {
-    if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K) return true;
+    if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_MXFP4) return true;
     return gemv_lds_bytes<FMT_Q4_0, 2>(1, K) <= MAX_LDS_BYTES;  // (2-block units: the record size is the formats' common one)
 }
 
@@ -181,6 +197,7 @@ hipError_t launch_moe(const MoeArgs& a, int wtype, hipStream_t st, char* describ
         case FMT_Q8_0: return moe_row<FMT_Q8_0>(L);
         case QG_TYPE_Q4_K: return moe_kq_launch<QG_TYPE_Q4_K>(L);
         case QG_TYPE_Q6_K: return moe_kq_launch<QG_TYPE_Q6_K>(L);
+        case QG_TYPE_MXFP4: return moe_kq_launch<QG_TYPE_MXFP4>(L);
     }
     return hipErrorInvalidValue;
 }

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(WGS) void q4k_gemv_kernel(const uint32_t* __restric
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q4k_gemv_fmt {
-    static constexpr int REC_DW = Q4K_REC_DW;
+    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = Q4K_REC_DW, UNIT = 64;
     static constexpr uintptr_t WMASK = 15;  // the 16-B loads
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return q4k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;

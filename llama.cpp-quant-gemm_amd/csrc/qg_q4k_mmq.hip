@@ -117,7 +117,7 @@ __global__ __launch_bounds__(Q4K_MMQ_WGS) void q4k_mmq_kernel(const uint32_t* __
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q4k_mmq_fmt {
     static constexpr const char* NAME = "q4k_mmq";
-    static constexpr int WAVES = Q4K_MMQ_WAVES;
+    static constexpr int WAVES = Q4K_MMQ_WAVES, KMULT = SB_ELEMS;
     static constexpr uintptr_t WMASK = 15;  // the 16-B header loads
     template <int TT, int RG, bool SUMI> static auto kernel() { return q4k_mmq_kernel<TT, RG, SUMI>; }
 };

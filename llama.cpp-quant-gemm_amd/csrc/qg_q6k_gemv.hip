@@ -59,7 +59,7 @@ __global__ __launch_bounds__(WGS) void q6k_gemv_kernel(const uint32_t* __restric
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q6k_gemv_fmt {
-    static constexpr int REC_DW = Q6K_REC_DW;
+    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = Q6K_REC_DW, UNIT = 64;
     static constexpr uintptr_t WMASK = 1;  // every load is realigned
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return q6k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(Q6K_MMQ_WGS) void q6k_mmq_kernel(const uint32_t* __
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q6k_mmq_fmt {
     static constexpr const char* NAME = "q6k_mmq";
-    static constexpr int WAVES = Q6K_MMQ_WAVES;
+    static constexpr int WAVES = Q6K_MMQ_WAVES, KMULT = SB_ELEMS;
     static constexpr uintptr_t WMASK = 1;  // every load is realigned
     template <int TT, int RG, bool SUMI> static auto kernel() { return q6k_mmq_kernel<TT, RG, SUMI>; }
 };

@@ -17,6 +17,7 @@
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
 #include "qg_q4k.hpp"
+#include "qg_mxfp4.hpp"
 #include "qg_q6k.hpp"
 #include "qg_quant_block.hpp"
 
@@ -539,6 +540,29 @@ hipError_t launch_dequantize_q6k(const void* x, float* y, int64_t nsb, hipStream
     const int64_t ngrp = nsb * 16;
     hipLaunchKernelGGL(dequantize_q6k_kernel, dim3((unsigned)((ngrp + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
                        ngrp);
+    return hipGetLastError();
+}
+
+// MXFP4 (qg_mxfp4.hpp): one thread per element, y = float(kv[code]) * scale(e): exact for every (code, e), +0.0f for
+// code 8. Byte loads: a block starts at any byte.
+namespace {
+__global__ __launch_bounds__(256) void dequantize_mxfp4_kernel(const uint8_t* __restrict__ x, float* __restrict__ y,
+                                                              int64_t nelem) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nelem) return;
+    const uint8_t* b = x + (i >> 5) * MXFP4_BYTES;
+    const int j = (int)(i & 31);
+    const uint32_t code = j < 16 ? b[1 + j] & 15u : (uint32_t)b[1 + j - 16] >> 4;
+    const int mag = (int)((0x0C08060403020100ull >> (8 * (code & 7))) & 0xFF);
+    y[i] = (float)((code & 8) ? -mag : mag) * mxfp4_scale(b[0]);
+}
+}  // namespace
+
+hipError_t launch_dequantize_mxfp4(const void* x, float* y, int64_t nblocks, hipStream_t st) {
+    if (nblocks <= 0) return hipSuccess;
+    const int64_t nelem = nblocks * 32;
+    hipLaunchKernelGGL(dequantize_mxfp4_kernel, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
+                       nelem);
     return hipGetLastError();
 }
 

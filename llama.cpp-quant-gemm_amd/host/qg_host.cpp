@@ -267,6 +267,40 @@ class Pool {
     bool stop_ = false;
 };
 
+// MXFP4 (qg/blocks.h: 17-B blocks, an E8M0 scale byte and 16 bytes of 4-bit codes into the doubled E2M1 table). The
+// product contract of qg.h: sumi in int32, (d_a * scale(e)) * float(sumi) per block, one fp32 accumulator per output,
+// blocks in order.
+struct FmtMXFP4 {
+    static constexpr int bytes = 17;
+    static int value(const uint8_t* p, int e) {
+        static const int8_t kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
+        return kv[e < 16 ? (p[1 + e] & 0x0F) : (p[1 + e - 16] >> 4)];
+    }
+    // 2^(e - 128) from its fp32 bits (subnormal for e < 2; no NaN code)
+    static float scale(uint8_t e) {
+        const uint32_t bits = e < 2 ? 0x00200000u << e : (uint32_t)(e - 1) << 23;
+        float f;
+        memcpy(&f, &bits, 4);
+        return f;
+    }
+};
+template <>
+void gemm_rows<FmtMXFP4>(const uint8_t* A, const uint8_t* B, float* C, int M, int N, int K, int j0, int j1) {
+    const int nb = K / QK;
+    const size_t arow = (size_t)nb * 36, wrow = (size_t)nb * FmtMXFP4::bytes;
+    for (int i = 0; i < M; ++i)
+        for (int n = j0; n < j1; ++n) {
+            float sum = 0.0f;
+            for (int b = 0; b < nb; ++b) {
+                const uint8_t* w = B + n * wrow + (size_t)b * FmtMXFP4::bytes;
+                const ActBlock a(A + i * arow + (size_t)b * 36);
+                int32_t sumi = 0;
+                for (int l = 0; l < QK; ++l) sumi += (int32_t)a.qs[l] * FmtMXFP4::value(w, l);
+                sum += (a.d * FmtMXFP4::scale(w[0])) * (float)sumi;
+            }
+            C[(size_t)i * N + n] = sum;
+        }
+}
 template <class F> void gemm_threads(const void* A, const void* B, float* C, int M, int N, int K, int threads) {
     auto run = [&](int j0, int j1) {
         gemm_rows<F>((const uint8_t*)A, (const uint8_t*)B, C, M, N, K, j0, j1);
@@ -300,6 +334,7 @@ int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, in
     switch (wtype) {
         case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q6_K: gemm_threads<FmtQ6_K>(A, B, C, M, N, K, threads); return QG_OK;
+        case QG_TYPE_MXFP4: gemm_threads<FmtMXFP4>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q5_0: gemm_threads<FmtQ5_0>(A, B, C, M, N, K, threads); return QG_OK;
@@ -321,6 +356,7 @@ int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert,
         case QG_TYPE_Q8_0: bb = FmtQ8_0::bytes; break;
         case QG_TYPE_Q4_K: bb = FmtQ4_K::bytes; break;
         case QG_TYPE_Q6_K: bb = FmtQ6_K::bytes; break;
+        case QG_TYPE_MXFP4: bb = FmtMXFP4::bytes; break;
     }
     // the order of qg_gemm_w4a8_moe
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
@@ -414,6 +450,17 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const 
             const float w = weights ? weights[(int64_t)t * w_stride + u] : 1.0f;
             for (int n = 0; n < N; ++n) c[n] = c[n] + w * d[n];
         }
+    }
+    return QG_OK;
+}
+
+int qg_dequantize_row_mxfp4_cpu(const void* x, float* y, int64_t k) {
+    if (k < 0 || k % QK != 0) return QG_ERR_BAD_K;
+    if (k == 0) return QG_OK;
+    if (!x || !y) return QG_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < k; ++i) {
+        const uint8_t* b = (const uint8_t*)x + (i / QK) * FmtMXFP4::bytes;
+        y[i] = (float)FmtMXFP4::value(b, (int)(i % QK)) * FmtMXFP4::scale(b[0]);
     }
     return QG_OK;
 }

@@ -11,7 +11,7 @@ Same names, argument meaning, tensor layouts and error behaviour as the referenc
 Differences, all deliberate: kernels run on torch's *current* HIP stream (the reference launches
 on the legacy default stream, gemm_ops.cu:250); validation errors raise RuntimeError like
 TORCH_CHECK does. Extra entry points expose the rest of the C-ABI: the activation-major
-``gemm_w4a8`` (include/gemm_reference.h convention), Q4_1/Q5_0/Q5_1, Q4_K and Q6_K weights, every quantizer and
+``gemm_w4a8`` (include/gemm_reference.h convention), Q4_1/Q5_0/Q5_1, Q4_K, Q6_K and MXFP4 weights, every quantizer and
 the per-block ``debug_sumi`` parity hook. Every call goes to HIP kernels in ``libqg_hip.so``;
 there is no CPU path.
 """
@@ -34,13 +34,14 @@ BLOCK_Q8_1_BYTES = 36
 Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 2, 3, 6, 7, 8, 9
 Q4_K = 12  # 256-element super-blocks of 144 bytes (qg.h "Q4_K weights")
 Q6_K = 14  # 256-element super-blocks of 210 bytes (qg.h "Q6_K weights")
-BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210}
+MXFP4 = 39  # 32-element blocks of 17 bytes: an E8M0 scale byte and E2M1 codes (qg.h "MXFP4 weights")
+BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210, MXFP4: 17}
 GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* (numbered as ggml_glu_op): the ops of gemm_w4a8_moe_glu
 ALGO_AUTO, ALGO_GEMV, ALGO_MFMA, ALGO_GENERIC, ALGO_RAGGED = 0, 1, 2, 3, 4
 WEIGHT_TYPES = (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0)
 # what gemm_w4a8 / gemm_w4a8_f32 / debug_sumi take; the layout entries (tiled, repacked, grouped, batched) keep
 # WEIGHT_TYPES
-GEMM_WEIGHT_TYPES = WEIGHT_TYPES + (Q4_K, Q6_K)
+GEMM_WEIGHT_TYPES = WEIGHT_TYPES + (Q4_K, Q6_K, MXFP4)
 
 
 def block_elems(qtype: int) -> int:
@@ -71,7 +72,7 @@ def quantize(x: torch.Tensor, qtype: int, variant: int = 0) -> torch.Tensor:
     _require(x.dim() >= 1, "Input must have at least 1 dimension")
     K = x.size(-1)
     _require(K % 32 == 0, f"Last dimension must be divisible by 32, got {K}")
-    _require(qtype in BLOCK_BYTES and qtype not in (Q4_K, Q6_K), f"unknown quant type {qtype}")
+    _require(qtype in BLOCK_BYTES and qtype not in (Q4_K, Q6_K, MXFP4), f"unknown quant type {qtype}")
     x = x.contiguous()
     out = torch.empty(tuple(x.shape[:-1]) + (K // 32, BLOCK_BYTES[qtype]), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
@@ -657,7 +658,8 @@ def gemm_w4a8_f32(x: torch.Tensor, weight_q: torch.Tensor, wtype: int = Q4_0, wo
     _require(wtype in GEMM_WEIGHT_TYPES, f"unsupported weight type {wtype}")
     be = block_elems(wtype)
     _require(K % be == 0, f"K must be divisible by {be}, got {K}")
-    _require(wtype not in (Q4_K, Q6_K) or workspace, "Q4_K / Q6_K weights need the Q8_1 workspace (workspace=True)")
+    _require(wtype not in (Q4_K, Q6_K, MXFP4) or workspace,
+             "Q4_K / Q6_K / MXFP4 weights need the Q8_1 workspace (workspace=True)")
     N = weight_q.numel() // ((K // be) * BLOCK_BYTES[wtype]) if K else 0
     _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype], be)
     x = x.contiguous()
@@ -854,7 +856,7 @@ __all__ = [
     "gemm_w4a16", "gemm_w8a16", "gemm_q4_0_fp32",
     "tile_weights", "gemm_w4a8_tiled", "debug_sumi_tiled", "debug_config_tiled",
     "quantize_q8_1_tiled", "tile_activations", "gemm_w4a8_tiled_act", "debug_sumi_tiled_act", "debug_config_tiled_act",
-    "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "Q6_K", "block_elems",
+    "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q4_K", "Q6_K", "MXFP4", "block_elems",
     "set_capture_fusion", "capture_fusion_stats", "set_group_affine", "group_config",
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",

@@ -20,8 +20,9 @@ from . import _lib
 
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
 Q4_K, Q6_K = 12, 14
+MXFP4 = 39
 I32 = 26  # the ids of mul_mat_id_from_ggml
-_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210}
+_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210, MXFP4: 17}
 _BE = {Q4_K: 256, Q6_K: 256}  # elements per block where it is not 32 (qg_block_elems)
 # the block types the GGUF reader serves (its own list: a Q6_K tensor is listed, not readable); views of bytes the
 # caller loaded (view_of) take every type of _BB

@@ -25,10 +25,11 @@ SIGNATURES = {
     "qg_gemm_fp32_cpu": ([P, P, P, I, I, I], I),
     "qg_quantize_row_q8_1_cpu": ([P, P, I64], I),
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
+    "qg_dequantize_row_mxfp4_cpu": ([P, P, I64], I),
     "qg_fill_step4_cpu": ([ctypes.c_uint, I, I, I, I, I, P, P], I),
 }
-# 12: Q4_K, 14: Q6_K, 256-element super-blocks
-BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210}
+# 12: Q4_K, 14: Q6_K, 256-element super-blocks; 39: MXFP4, 32-element blocks of 17 bytes
+BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210, 39: 17}
 GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* of qg.h
 _lib = None
 
@@ -76,6 +77,15 @@ def quantize_q4_0(x: np.ndarray) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32)
     out = np.empty(x.shape[:-1] + (x.shape[-1] // 32, 18), np.uint8)
     _ok(load().qg_quantize_row_q4_0_cpu(_p(x), _p(out), x.size), "quantize_row_q4_0")
+    return out
+
+
+def dequantize_mxfp4(x_q: np.ndarray) -> np.ndarray:
+    """float32 [..., 32 * blocks] of block_mxfp4 bytes [..., blocks, 17] (qg_dequantize_row_mxfp4_cpu)."""
+    x_q = np.ascontiguousarray(x_q, np.uint8)
+    assert x_q.shape[-1] == 17
+    out = np.empty(x_q.shape[:-2] + (x_q.shape[-2] * 32,), np.float32)
+    _ok(load().qg_dequantize_row_mxfp4_cpu(_p(x_q), _p(out), out.size), "dequantize_row_mxfp4")
     return out
 
 
