@@ -614,6 +614,64 @@ int qg_gemm_w4a8_moe_down(const void* A_q8_1, const void* B_experts, int n_exper
                           int wtype, qg_stream_t stream);
 int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
+/* ---- the two fused FFN entries with per-expert bias, gpt-oss's clamped SwiGLU and MXFP4 experts ----
+ * A gpt-oss FFN block is g = gate_e(x) + bg[e], u = up_e(x) + bu[e], h = swiglu_oai(g, u), d = down_e(h) + bd[e],
+ * y = sum_u w[t,u] * d_u. These two entries are qg_gemm_w4a8_moe_glu and qg_gemm_w4a8_moe_down above with the bias rows
+ * and the third op, for wtype QG_TYPE_Q4_K, QG_TYPE_Q6_K or QG_TYPE_MXFP4 (which the two above refuse): the block at
+ * decode is again four calls, quantize, moe_glu_bias, quantize, moe_down_bias. Everything not said here (operands, slot
+ * numbering, ids, ldc, weights, an id outside [0, n_expert), capture, the host reading nothing) is as above.
+ * Bias: float [n_expert][bias_stride] in DEVICE memory, 4-B aligned, bias_stride = 0 means N. Each bias pointer may be
+ * NULL on its own: no add for that operand (not an add of 0.0f: -0.0f stays -0.0f).
+ * qg_gemm_w4a8_moe_glu_bias, slot s = t * n_used + u, e = ids[t * ids_stride + u], g and u the two products:
+ *   g = g + bias_gate[e * bias_stride + n]   (bias_gate != NULL)      u = u + bias_up[e * bias_stride + n]   (bias_up != NULL)
+ *   C[s * ldc + n] = QG_GLU_REGLU, QG_GLU_SWIGLU: as qg_gemm_w4a8_moe_glu
+ *                    QG_GLU_SWIGLU_OAI: x = fminf(g, limit); y = fminf(fmaxf(u, -limit), limit);
+ *                                       (x / (1.0f + expf(alpha * (-x)))) * (y + 1.0f)
+ *   alpha and limit are read for QG_GLU_SWIGLU_OAI alone (gpt-oss: 1.702f, 7.0f). Each step is one rounded fp32
+ *   operation. An id outside [0, n_expert) stores +0.0f: no bias is read or applied.
+ * qg_gemm_w4a8_moe_down_bias: d_u[n] = d_u[n] + bias[e_u * bias_stride + n] (one rounded add) ahead of the fold
+ *   acc = acc + weights[t * w_stride + u] * d_u[n], which is unchanged. An id outside [0, n_expert) contributes nothing:
+ *   neither its bias nor its weight is read.
+ * Bits: g, u and d_u are those of qg_gemm_w4a8_moe on the same operands (MXFP4: the "moe:mxfp4_gemv" body at the
+ * single call's LPR, WGS and ONE for K / 32 units). With Q4_K / Q6_K and null biases the outputs are bit-identical to
+ * qg_gemm_w4a8_moe_glu / qg_gemm_w4a8_moe_down.
+ * MXFP4 weights need no alignment: B_gate, B_up, B_experts and the expert stride N * K/32 * 17 are any number of bytes.
+ * Validation: the order of the two entries above, with K a positive multiple of 32 for MXFP4; a non-null bias off 4 B
+ * -> QG_ERR_ALIGN beside the other pointers; bias_stride < 0 or 0 < bias_stride < N -> QG_ERR_INVALID_ARG beside
+ * ids_stride (whether or not a bias is given), and there too, for QG_GLU_SWIGLU_OAI, an alpha that is not finite or a
+ * limit that is not finite and > 0; then the QG_ERR_UNSUPPORTED shapes of moe_front; then the entry's own refusals,
+ * QG_ERR_UNSUPPORTED with nothing launched: a glu_op other than the three, a shape that QG_ALGO_AUTO at M = 1 does not
+ * send to the type's decode GEMV, for down an LDS need beyond 160 KiB. MXFP4's need is
+ * n_used * (K/32 * 48 + 4 RPB) bytes; the largest K served, by n_used:
+ *   n_used        1       2       3       4       6       8      10      16      32
+ *   MXFP4    109184   54592   36384   27296   18176   13632   10912    6816    3392
+ * (Q4_K / Q6_K: the table of qg_gemm_w4a8_moe_down.)
+ * qg_moe_glu_bias_config / qg_moe_down_bias_config: for Q4_K / Q6_K the strings of qg_moe_glu_config /
+ * qg_moe_down_config (bias and op are no part of the launch's shape); for MXFP4 "moe_glu:mxfp4_gemv ..." and
+ * "moe_down:mxfp4_gemv ... SW=...", LPR / WGS / ONE those of qg_moe_config for the same K, SW and RPB by the rule above.
+ * Which to use (measured on an MI355X with a uniform router at gpt-oss's N = K = 2880, MXFP4, 4 of 32 and 4 of 128
+ * experts, against the unfused sequence on the same operands -- qg_gemm_w4a8_moe twice, torch's two gathered bias adds
+ * and a torch swiglu_oai for glu; qg_gemm_w4a8_moe at a_rows = n_used, torch's gathered bias add, multiply and sum for
+ * down; DESIGN.md 3i, profiles/mxfp4_ffn/ab_mxfp4_ffn.txt): qg_gemm_w4a8_moe_glu_bias at T = 1 (0.38 of the sequence's
+ * time captured, 0.26 eager) and at T = 8 (0.73 .. 0.75 both ways); qg_gemm_w4a8_moe_down_bias at T = 1 (0.51 captured,
+ * 0.51 .. 0.52 eager). At T = 8 the down entry is NOT ahead beyond what a run resolves: 0.97 .. 1.00 of the sequence's
+ * time with overlapping ranges; the weight stream is the time there, and either form serves. For Q4_K / Q6_K without
+ * bias prefer qg_gemm_w4a8_moe_glu / qg_gemm_w4a8_moe_down: with null biases the new entries give the same bits in
+ * 1.00 .. 1.01 of their time captured at Qwen3-MoE's shape (glu at T = 1: 7.10 against 7.03 us, outside that run's
+ * spread of 0.02; the other three classes within it).
+ * Not built: MXFP4 in the prefill and batch entries, FP32-input or Q8_1-writing fused forms, GEGLU, a dense (no ids)
+ * GLU entry, an MXFP4 quantizer. */
+#define QG_GLU_SWIGLU_OAI 3   /* beside QG_GLU_REGLU 0 / QG_GLU_SWIGLU 2 */
+int qg_gemm_w4a8_moe_glu_bias(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
+                              const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids, int64_t ids_stride,
+                              float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op, float alpha,
+                              float limit, qg_stream_t stream);
+int qg_moe_glu_bias_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+int qg_gemm_w4a8_moe_down_bias(const void* A_q8_1, const void* B_experts, const float* bias, int64_t bias_stride, int n_expert,
+                               const int32_t* ids, int64_t ids_stride, const float* weights, int64_t w_stride, float* C,
+                               int64_t ldc, int T, int n_used, int N, int K, int wtype, qg_stream_t stream);
+int qg_moe_down_bias_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
 int qg_gemm_q4_0_q8_1(const void* W, const void* A_q8_1, float* out, int M, int N, int K, qg_stream_t stream);
@@ -741,6 +799,17 @@ int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_v
  * or with strides the entry cannot express, out with ne[2] > 1; weights with other dims are QG_ERR_INVALID_ARG. */
 int qg_mul_mat_id_down_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                  const qg_tensor_view* weights, qg_tensor_view* out, qg_stream_t stream);
+/* The two views entries above with the bias views of qg_gemm_w4a8_moe_glu_bias / qg_gemm_w4a8_moe_down_bias, for Q4_K /
+ * Q6_K / MXFP4 experts. A bias view is NULL (no add) or F32 with ne = [N, n_expert], nb[0] = 4, nb[1] a multiple of 4
+ * and >= 4 N (the bias stride; two bias views must have the same): another type or such strides QG_ERR_UNSUPPORTED,
+ * other dims or null data QG_ERR_INVALID_ARG. Everything else as in the two entries above; an MXFP4 as->nb[2] off the
+ * dense expert size N * K/32 * 17 is QG_ERR_UNSUPPORTED, as in qg_mul_mat_id_from_view. */
+int qg_mul_mat_id_glu_bias_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* bias_gate,
+                                     const qg_tensor_view* bias_up, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                     qg_tensor_view* out, int glu_op, float alpha, float limit, qg_stream_t stream);
+int qg_mul_mat_id_down_bias_from_view(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                      const qg_tensor_view* ids, const qg_tensor_view* weights, qg_tensor_view* out,
+                                      qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

@@ -76,6 +76,22 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A_q8_1, const void* B_experts, int n_e
                               int64_t ids_stride, const float* weights, int64_t w_stride, float* C, int64_t ldc, int T,
                               int n_used, int N, int K, int wtype, int threads);
 
+/* Host twins of qg_gemm_w4a8_moe_glu_bias / qg_gemm_w4a8_moe_down_bias (qg.h): the same arguments with `ids`, `weights`
+ * and the biases in host memory, and `threads` as above; wtype Q4_K, Q6_K or MXFP4. The products have the bits of
+ * qg_gemm_w4a8_moe_cpu; a non-null bias is added with one rounded fp32 addition (g + bias_gate[e][n], u + bias_up[e][n],
+ * d_u + bias[e_u][n]) ahead of the op or the fold, which are those of the two twins above, and for QG_GLU_SWIGLU_OAI
+ *   x = fminf(g, limit); y = fminf(fmaxf(u, -limit), limit); (x / (1.0f + expf(alpha * (-x)))) * (y + 1.0f)
+ * with libm's expf. An id outside [0, n_expert) gives N times +0.0f (GLU) or contributes nothing (down); its bias is
+ * not read. The same validation codes (no alignment is asked); no shape is unsupported. */
+int qg_gemm_w4a8_moe_glu_bias_cpu(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
+                                  const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids,
+                                  int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                                  int glu_op, float alpha, float limit, int threads);
+int qg_gemm_w4a8_moe_down_bias_cpu(const void* A_q8_1, const void* B_experts, const float* bias, int64_t bias_stride,
+                                   int n_expert, const int32_t* ids, int64_t ids_stride, const float* weights,
+                                   int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                                   int threads);
+
 /* gemm_fp32_reference (include/gemm_reference.h:38-58): float accumulation in k order. */
 int qg_gemm_fp32_cpu(const float* A, const float* B, float* C, int M, int N, int K);
 

@@ -6,6 +6,8 @@
 // qg_workspace.hip, the capture-time merge of GEMVs in qg_capture_fuse.hip.
 #include <string.h>
 
+#include <cmath>
+
 #include <initializer_list>
 
 #include "../../include/qg/qg.h"
@@ -429,6 +431,10 @@ struct MoeCall {
     int slots;     // moe_front: T * n_used
     const void* B_up; int glu_op;
     const float* weights; int64_t w_stride;
+    // qg_gemm_w4a8_moe_glu_bias, _moe_down_bias (biased; down's one bias is bias_gate). After moe_front: bias_stride never 0
+    bool biased;
+    const float* bias_gate; const float* bias_up; int64_t bias_stride;
+    float alpha, limit;
 };
 
 // Bytes of a plan's workspace whose tile region is sized for tiles of min_r rows (qg_moe_plan.hpp).
@@ -442,23 +448,32 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 // or the entry runs a plan in a workspace sized for tiles of min_r rows. up: the entry has a second weights pointer,
 // B_up, checked beside B with the same mask. down: the entry is qg_gemm_w4a8_moe_down: weights stands beside the other
 // pointers (null allowed, 4 B otherwise), w_stride beside ids_stride, and the grid's y is the token, so T is what 65535
-// bounds (slots stays 0).
+// bounds (slots stays 0). c.biased: the entry is one of the two _bias ones: it takes MXFP4 beside the super-block types,
+// its bias pointers stand beside the other pointers (null allowed, 4 B otherwise), bias_stride and the OAI op's alpha
+// and limit beside ids_stride.
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
 //   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
 //   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
 int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    // (MXFP4 is a type of qg_gemm_w4a8_moe alone: where the 32-element types are refused, it is refused as they are)
-    const bool ksb = is_sb_type(c.wtype) || (rows_ok && is_mxfp4_type(c.wtype));
+    // (MXFP4 is a type of qg_gemm_w4a8_moe and the two _bias entries: elsewhere it is refused as the 32-element types are)
+    const bool ksb = is_sb_type(c.wtype) || ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
                             {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
-                             {down && c.weights ? c.weights : c.A, 3}, {c.C, 0}});
+                             {down && c.weights ? c.weights : c.A, 3}, {c.C, 0},
+                             {c.biased && c.bias_gate ? c.bias_gate : c.A, 3}, {c.biased && c.bias_up ? c.bias_up : c.A, 3}});
     if (rc != QG_GO) return rc;
     if ((c.a_rows != 1 && c.a_rows != c.n_used) || c.ids_stride < c.n_used || c.n_expert < 1 || c.ldc < 0 ||
         (c.ldc > 0 && c.ldc < c.N) || (down && c.weights && c.w_stride < c.n_used))
         return QG_ERR_INVALID_ARG;
+    if (c.biased) {
+        if (c.bias_stride < 0 || (c.bias_stride > 0 && c.bias_stride < c.N)) return QG_ERR_INVALID_ARG;
+        if (c.glu_op == QG_GLU_SWIGLU_OAI && !(std::isfinite(c.alpha) && std::isfinite(c.limit) && c.limit > 0.0f))
+            return QG_ERR_INVALID_ARG;
+        if (!c.bias_stride) c.bias_stride = c.N;
+    }
     if (min_r) {
         if (!c.ws) return QG_ERR_INVALID_ARG;
         if (((uintptr_t)c.ws & (MOE_WS_ALIGN - 1)) != 0) return QG_ERR_ALIGN;
@@ -553,6 +568,57 @@ int run_moe_down(MoeCall& c) {
     return hip_status(launch_moe_down(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
+// qg_gemm_w4a8_moe_glu_bias, qg_moe_glu_bias_config: Q4_K / Q6_K / MXFP4 (c.biased). run_moe_glu's refusals with the
+// third op among the known ones.
+int run_moe_glu_bias(MoeCall& c) {
+    c.biased = true;
+    const int rc = moe_front(c, false, 0, true);
+    if (rc != QG_GO) return rc;
+    if ((c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU && c.glu_op != QG_GLU_SWIGLU_OAI) || !moe_gemv_route(c))
+        return QG_ERR_UNSUPPORTED;
+    MoeGluBiasArgs a;
+    a.A = c.A; a.B_gate = c.B; a.B_up = c.B_up; a.ids = c.ids; a.C = c.C;
+    a.ids_stride = (long)c.ids_stride; a.ldc = (long)c.ldc; a.estride = c.estride; a.arow = (long)(c.K / 32) * 36;
+    a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots; a.glu_op = c.glu_op;
+    a.bias_gate = c.bias_gate; a.bias_up = c.bias_up; a.bias_stride = (long)c.bias_stride; a.alpha = c.alpha; a.limit = c.limit;
+    return hip_status(launch_moe_glu_bias(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_down_bias, qg_moe_down_bias_config: Q4_K / Q6_K / MXFP4 (c.biased), run_moe_down's refusals.
+int run_moe_down_bias(MoeCall& c) {
+    c.a_rows = c.n_used;
+    c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
+    const int rc = moe_front(c, false, 0, false, true);
+    if (rc != QG_GO) return rc;
+    if (!moe_gemv_route(c) || moe_down_form(c.n_used, c.K, c.wtype).lds > MAX_LDS_BYTES) return QG_ERR_UNSUPPORTED;
+    MoeDownBiasArgs a;
+    a.A = c.A; a.B = c.B; a.ids = c.ids; a.weights = c.weights; a.C = c.C;
+    a.ids_stride = (long)c.ids_stride; a.w_stride = (long)c.w_stride; a.ldc = (long)c.ldc; a.estride = c.estride;
+    a.arow = (long)(c.K / 32) * 36;
+    a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.T = c.T;
+    a.bias = c.bias_gate; a.bias_stride = (long)c.bias_stride;
+    return hip_status(launch_moe_down_bias(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// A bias view of the two _bias view entries -> pointer and stride: F32, ne = [N, n_expert], nb[0] = 4, nb[1] a
+// multiple of 4 and >= 4 N. Null: no bias. stride: 0 until a view has set it; two views must agree.
+int bias_view(const qg_tensor_view* v, const MoeCall& c, const float*& p, int64_t& stride) {
+    p = nullptr;
+    if (!v) return QG_GO;
+    auto one = [](int64_t x) { return x == 1 || x == 0; };
+    if (v->type != QG_TYPE_F32) return QG_ERR_UNSUPPORTED;
+    if (v->ne[0] != c.N || v->ne[1] != c.n_expert) return QG_ERR_INVALID_ARG;
+    if (!one(v->ne[2]) || !one(v->ne[3]) || v->nb[0] != sizeof(float) || v->nb[1] % sizeof(float) != 0 ||
+        v->nb[1] < (size_t)c.N * sizeof(float))
+        return QG_ERR_UNSUPPORTED;
+    const int64_t st = (int64_t)(v->nb[1] / sizeof(float));
+    if (stride && stride != st) return QG_ERR_UNSUPPORTED;
+    if (!v->data) return QG_ERR_INVALID_ARG;
+    p = (const float*)v->data;
+    stride = st;
+    return QG_GO;
+}
+
 // qg_moe*_config: the shape alone, as qg_debug_config: 256-B aligned stand-in pointers (a workspace of any size among
 // them), one activation row per token.
 int moe_config(int (*run)(MoeCall&), int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
@@ -603,6 +669,39 @@ int mul_mat_id_from_view(int (*run)(MoeCall&), const qg_tensor_view* as, const q
     if (rc != QG_GO) return rc;
     c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
     return run(c);
+}
+// The views of qg_mul_mat_id_down_from_view -> the call of the down entry (stream apart).
+int mul_mat_id_down_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
+                         const qg_tensor_view* weights, const qg_tensor_view* out, MoeCall& c) {
+    if (!out) return QG_ERR_INVALID_ARG;
+    // as, b and ids go through the checks of qg_mul_mat_id_from_view beside a dense stand-in [N, n_used, T] for its
+    // output (this entry's has a row per token): every refusal of that entry's, then what is this entry's own
+    const int64_t n_used = ids ? ids->ne[0] : 0;
+    auto one = [](int64_t v) { return v == 1 || v == 0; };
+    if (!one(out->ne[2])) return QG_ERR_UNSUPPORTED;
+    qg_tensor_view slots = *out;
+    slots.ne[1] = n_used; slots.ne[2] = out->ne[1];
+    slots.nb[1] = (size_t)(out->ne[0] > 0 ? out->ne[0] : 0) * sizeof(float); slots.nb[2] = (size_t)n_used * slots.nb[1];
+    const int rc = mul_mat_id_view(as, b, ids, &slots, c);
+    if (rc != QG_GO) return rc;
+    if (c.a_rows != c.n_used) return QG_ERR_UNSUPPORTED;
+    if (c.T > 1 && out->nb[1] % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
+    c.ldc = c.T > 1 ? (int64_t)(out->nb[1] / sizeof(float)) : c.N;
+    c.weights = nullptr; c.w_stride = c.n_used;
+    if (weights) {
+        // F32 [n_used, T] or [1, n_used, T]: the router's weights as ggml keeps them
+        const int d = weights->ne[0] == 1 && weights->ne[1] == c.n_used && weights->ne[2] == c.T ? 1 : 0;
+        if (weights->type != QG_TYPE_F32) return QG_ERR_UNSUPPORTED;
+        if (weights->ne[d] != c.n_used || weights->ne[d + 1] != c.T) return QG_ERR_INVALID_ARG;
+        if (!one(weights->ne[d + 2]) || (d == 0 && !one(weights->ne[3]))) return QG_ERR_UNSUPPORTED;
+        if ((c.n_used > 1 && weights->nb[d] != sizeof(float)) || (c.T > 1 && weights->nb[d + 1] % sizeof(float) != 0))
+            return QG_ERR_UNSUPPORTED;
+        c.weights = (const float*)weights->data;
+        if (!c.weights) return QG_ERR_INVALID_ARG;
+        if (c.T > 1) c.w_stride = (int64_t)(weights->nb[d + 1] / sizeof(float));
+    }
+    c.ws = nullptr; c.ws_bytes = 0;
+    return QG_GO;
 }
 }  // namespace
 
@@ -727,36 +826,68 @@ int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, si
 
 int qg_mul_mat_id_down_from_view(const qg_tensor_view* as, const qg_tensor_view* b, const qg_tensor_view* ids,
                                  const qg_tensor_view* weights, qg_tensor_view* out, qg_stream_t stream) {
-    if (!out) return QG_ERR_INVALID_ARG;
-    // as, b and ids go through the checks of qg_mul_mat_id_from_view beside a dense stand-in [N, n_used, T] for its
-    // output (this entry's has a row per token): every refusal of that entry's, then what is this entry's own
-    const int64_t n_used = ids ? ids->ne[0] : 0;
-    auto one = [](int64_t v) { return v == 1 || v == 0; };
-    if (!one(out->ne[2])) return QG_ERR_UNSUPPORTED;
-    qg_tensor_view slots = *out;
-    slots.ne[1] = n_used; slots.ne[2] = out->ne[1];
-    slots.nb[1] = (size_t)(out->ne[0] > 0 ? out->ne[0] : 0) * sizeof(float); slots.nb[2] = (size_t)n_used * slots.nb[1];
     MoeCall c;
-    const int rc = mul_mat_id_view(as, b, ids, &slots, c);
+    const int rc = mul_mat_id_down_view(as, b, ids, weights, out, c);
     if (rc != QG_GO) return rc;
-    if (c.a_rows != c.n_used) return QG_ERR_UNSUPPORTED;
-    if (c.T > 1 && out->nb[1] % sizeof(float) != 0) return QG_ERR_UNSUPPORTED;
-    c.ldc = c.T > 1 ? (int64_t)(out->nb[1] / sizeof(float)) : c.N;
-    c.weights = nullptr; c.w_stride = c.n_used;
-    if (weights) {
-        // F32 [n_used, T] or [1, n_used, T]: the router's weights as ggml keeps them
-        const int d = weights->ne[0] == 1 && weights->ne[1] == c.n_used && weights->ne[2] == c.T ? 1 : 0;
-        if (weights->type != QG_TYPE_F32) return QG_ERR_UNSUPPORTED;
-        if (weights->ne[d] != c.n_used || weights->ne[d + 1] != c.T) return QG_ERR_INVALID_ARG;
-        if (!one(weights->ne[d + 2]) || (d == 0 && !one(weights->ne[3]))) return QG_ERR_UNSUPPORTED;
-        if ((c.n_used > 1 && weights->nb[d] != sizeof(float)) || (c.T > 1 && weights->nb[d + 1] % sizeof(float) != 0))
-            return QG_ERR_UNSUPPORTED;
-        c.weights = (const float*)weights->data;
-        if (!c.weights) return QG_ERR_INVALID_ARG;
-        if (c.T > 1) c.w_stride = (int64_t)(weights->nb[d + 1] / sizeof(float));
-    }
-    c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
+    c.st = (hipStream_t)stream;
     return run_moe_down(c);
+}
+
+
+int qg_gemm_w4a8_moe_glu_bias(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
+                              const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids, int64_t ids_stride,
+                              float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op, float alpha,
+                              float limit, qg_stream_t stream) {
+    MoeCall c{A_q8_1, 1, B_gate, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, nullptr, 0, (hipStream_t)stream};
+    c.B_up = B_up; c.glu_op = glu_op;
+    c.bias_gate = bias_gate; c.bias_up = bias_up; c.bias_stride = bias_stride; c.alpha = alpha; c.limit = limit;
+    return run_moe_glu_bias(c);
+}
+
+int qg_moe_glu_bias_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_glu_bias, T, n_used, 1, N, K, wtype, buf, len);
+}
+
+int qg_mul_mat_id_glu_bias_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* bias_gate,
+                                     const qg_tensor_view* bias_up, const qg_tensor_view* b, const qg_tensor_view* ids,
+                                     qg_tensor_view* out, int glu_op, float alpha, float limit, qg_stream_t stream) {
+    if (!as_up) return QG_ERR_INVALID_ARG;
+    MoeCall c;
+    int rc = mul_mat_id_view(as_gate, b, ids, out, c);
+    if (rc != QG_GO) return rc;
+    if (c.a_rows != 1 || as_up->type != as_gate->type || memcmp(as_up->ne, as_gate->ne, sizeof as_up->ne) != 0 ||
+        memcmp(as_up->nb, as_gate->nb, sizeof as_up->nb) != 0)
+        return QG_ERR_UNSUPPORTED;
+    if ((rc = bias_view(bias_gate, c, c.bias_gate, c.bias_stride)) != QG_GO) return rc;
+    if ((rc = bias_view(bias_up, c, c.bias_up, c.bias_stride)) != QG_GO) return rc;
+    c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
+    c.B_up = as_up->data; c.glu_op = glu_op; c.alpha = alpha; c.limit = limit;
+    return run_moe_glu_bias(c);
+}
+
+int qg_gemm_w4a8_moe_down_bias(const void* A_q8_1, const void* B_experts, const float* bias, int64_t bias_stride, int n_expert,
+                               const int32_t* ids, int64_t ids_stride, const float* weights, int64_t w_stride, float* C,
+                               int64_t ldc, int T, int n_used, int N, int K, int wtype, qg_stream_t stream) {
+    MoeCall c{A_q8_1, n_used, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, nullptr, 0,
+              (hipStream_t)stream};
+    c.weights = weights; c.w_stride = w_stride;
+    c.bias_gate = bias; c.bias_stride = bias_stride;
+    return run_moe_down_bias(c);
+}
+
+int qg_moe_down_bias_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_down_bias, T, n_used, 1, N, K, wtype, buf, len);
+}
+
+int qg_mul_mat_id_down_bias_from_view(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                      const qg_tensor_view* ids, const qg_tensor_view* weights, qg_tensor_view* out,
+                                      qg_stream_t stream) {
+    MoeCall c;
+    int rc = mul_mat_id_down_view(as, b, ids, weights, out, c);
+    if (rc != QG_GO) return rc;
+    if ((rc = bias_view(bias, c, c.bias_gate, c.bias_stride)) != QG_GO) return rc;
+    c.st = (hipStream_t)stream;
+    return run_moe_down_bias(c);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

@@ -1,5 +1,5 @@
 // qg_moe_glu.hpp — what the C-ABI (qg_api.hip) and the kernels (qg_moe_glu.hip) of the fused gate / up mul_mat_id
-// (qg_gemm_w4a8_moe_glu) share.
+// (qg_gemm_w4a8_moe_glu, qg_gemm_w4a8_moe_glu_bias) share.
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
@@ -21,5 +21,18 @@ struct MoeGluArgs {
 // describe: name the kernel there (qg_moe_glu_config) and launch nothing. The caller has checked the type (Q4_K /
 // Q6_K), glu_op and that AUTO at M = 1 takes the decode GEMV of the type.
 hipError_t launch_moe_glu(const MoeGluArgs& a, int wtype, hipStream_t st, char* describe = nullptr, size_t describe_len = 0);
+
+// qg_gemm_w4a8_moe_glu_bias: the same slot with g = g + bias_gate[e * bias_stride + n], u likewise, ahead of the op,
+// and QG_GLU_SWIGLU_OAI among the ops. A kernel argument of its own, so that the entry above keeps its argument block.
+struct MoeGluBiasArgs : MoeGluArgs {
+    const float* bias_gate;  // device memory [n_expert][bias_stride]; null: no add
+    const float* bias_up;
+    long bias_stride;        // floats
+    float alpha, limit;      // QG_GLU_SWIGLU_OAI alone
+};
+// wtype Q4_K / Q6_K / MXFP4 (B_gate, B_up and estride then any number of bytes). The caller has checked what
+// launch_moe_glu's has, glu_op among the three.
+hipError_t launch_moe_glu_bias(const MoeGluBiasArgs& a, int wtype, hipStream_t st, char* describe = nullptr,
+                               size_t describe_len = 0);
 
 }  // namespace qg

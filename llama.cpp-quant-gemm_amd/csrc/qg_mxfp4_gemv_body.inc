@@ -1,21 +1,40 @@
 // qg_mxfp4_gemv_body.inc — the body of the MXFP4 decode GEMV, included as text into mxfp4_gemv_kernel
-// (qg_mxfp4_gemv.hip, where the work decomposition is described) and mxfp4_moe_body (qg_moe.hip). Text and not a
-// function they call, as the K-quant bodies (DESIGN.md 3c): one instantiation per (K, M) form, the same tokens in
-// the single call and in the expert entry, so a slot's bits are the single call's.
+// (qg_mxfp4_gemv.hip, where the work decomposition is described) and mxfp4_moe_body (qg_moe.hip) and
+// mxfp4_glu_product[_staged] (qg_moe_glu.hip) and mxfp4_down_stage / mxfp4_down_product (qg_moe_down.hip). Text and
+// not a function they call, as the K-quant bodies (DESIGN.md 3c): one instantiation per (K, M) form, the same tokens
+// in the single call and in the expert entries, so a slot's bits are the single call's.
 // Expects in scope: A, B (the operands), M, N, K, out, ldc, the template parameters or constants MT, LPR, WGS, SUMI,
 // ONE, and three macros, the lines in which the includers differ:
 //   QG_KQ_DECLARE_TILE  the declaration of `const int tile` in the kernel, nothing where tile is a parameter
 //   QG_KQ_ABLK(g)       the address of activation block g = m * K/32 + b: `A + (long)g * 9` for dense rows
 //   QG_KQ_OUT(m)        the output of token m at this lane's row: `C[m * ldc + row]`
+// and four the shipped includers leave undefined (the meaning they have in qg_q4k_gemv_body.inc):
+//   QG_KQ_A_STAGED      defined: the LDS records already hold the activation row (an earlier pass of the same
+//                       workgroup staged it and a barrier has passed); the body loads its first unit and goes on
+//   QG_KQ_STAGE_ONLY    defined: the inclusion is the staging prologue alone, the M dense activation rows into the
+//                       records and its barrier: no weights, no row, no product (B, N, out, MT, SUMI, ONE are not needed)
+//   QG_KQ_ROW           the lane's output row, where it is not `tile * RPB + (tid >> 6) * RPW + lane / LPR` (a
+//                       workgroup whose waves share rows; tile is then not needed)
+//   QG_KQ_RECS          the first LDS record of the activation row(s) the product reads, where that is not the start
+//                       of the dynamic LDS (with QG_KQ_A_STAGED: the row of another slot)
     constexpr int RPW = 64 / LPR;
     constexpr int RPB = (WGS / 64) * RPW;  // rows per workgroup
+#ifdef QG_KQ_RECS
+    const uint32_t* const lds = QG_KQ_RECS;
+#else
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+#endif
 
     const int nb = K / QK;                        // blocks per row
     const int U = (nb + MXFP4_UB - 1) / MXFP4_UB;  // units per row: MXFP4_UB consecutive blocks each (1 as shipped)
     const int tid = threadIdx.x, lane = tid & 63, lir = lane % LPR;
+#ifndef QG_KQ_STAGE_ONLY
+#ifdef QG_KQ_ROW
+    const int row = QG_KQ_ROW;
+#else
     QG_KQ_DECLARE_TILE
     const int row = tile * RPB + (tid >> 6) * RPW + lane / LPR;
+#endif
     const bool row_ok = row < N;
     const uint8_t* wrow = B + (long)(row_ok ? row : 0) * ((long)nb * MXFP4_BYTES);
     // (blocks past the row's end are clamped to its last one: loaded, never used)
@@ -28,7 +47,12 @@
             for (int i = 0; i < MXFP4_COVER_DW; ++i) dst[MXFP4_COVER_DW * x + i] = c[i];
         }
     };
+#endif
 
+#ifdef QG_KQ_A_STAGED
+    uint32_t cur[MXFP4_UNIT_DW];
+    load_unit(cur, lir);
+#else
     // 1) this thread's first activation block, 2) the lane's first unit, 3) the LDS records
     const int totb = M * nb;
     auto load_ablk = [&](int g, uint32_t (&d)[9]) {
@@ -44,15 +68,19 @@
     };
     uint32_t ab[9];
     if (tid < totb) load_ablk(tid, ab);
+#ifndef QG_KQ_STAGE_ONLY
     uint32_t cur[MXFP4_UNIT_DW];
     load_unit(cur, lir);
+#endif
     if (tid < totb) put_ablk(tid, ab);
     for (int g = tid + WGS; g < totb; g += WGS) {
         load_ablk(g, ab);
         put_ablk(g, ab);
     }
     __syncthreads();
+#endif
 
+#ifndef QG_KQ_STAGE_ONLY
     float acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m] = 0.0f;
@@ -123,3 +151,4 @@
                 if (m < M) QG_KQ_OUT(m) = acc[m];
         }
     }
+#endif

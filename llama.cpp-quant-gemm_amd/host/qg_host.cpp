@@ -454,6 +454,108 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const 
     return QG_OK;
 }
 
+namespace {
+// the two _bias twins: Q4_K / Q6_K / MXFP4, the bytes of a block and the elements it holds (0: not a type of theirs)
+int bias_block(int wtype, int& elems) {
+    elems = wtype == QG_TYPE_MXFP4 ? QK : 256;
+    switch (wtype) {
+        case QG_TYPE_Q4_K: return FmtQ4_K::bytes;
+        case QG_TYPE_Q6_K: return FmtQ6_K::bytes;
+        case QG_TYPE_MXFP4: return FmtMXFP4::bytes;
+    }
+    elems = QK;
+    return 0;
+}
+}  // namespace
+
+int qg_gemm_w4a8_moe_glu_bias_cpu(const void* A, const void* B_gate, const void* B_up, const float* bias_gate,
+                                  const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids,
+                                  int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                                  int glu_op, float alpha, float limit, int threads) {
+    int be;
+    const int bb = bias_block(wtype, be);
+    // the order of qg_gemm_w4a8_moe_glu_bias
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B_gate || !B_up || !ids || !C) return QG_ERR_INVALID_ARG;
+    if (ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N)) return QG_ERR_INVALID_ARG;
+    if (bias_stride < 0 || (bias_stride > 0 && bias_stride < N)) return QG_ERR_INVALID_ARG;
+    if (glu_op == QG_GLU_SWIGLU_OAI && !(std::isfinite(alpha) && std::isfinite(limit) && limit > 0.0f)) return QG_ERR_INVALID_ARG;
+    if (glu_op != QG_GLU_REGLU && glu_op != QG_GLU_SWIGLU && glu_op != QG_GLU_SWIGLU_OAI) return QG_ERR_UNSUPPORTED;
+    const size_t arow = (size_t)(K / QK) * 36, estride = (size_t)N * (size_t)(K / be) * (size_t)bb;
+    if (ldc == 0) ldc = N;
+    if (bias_stride == 0) bias_stride = N;
+    std::vector<float> g((size_t)N), up((size_t)N);
+    for (int t = 0; t < T; ++t)
+        for (int u = 0; u < n_used; ++u) {
+            const int e = ids[(int64_t)t * ids_stride + u];
+            float* c = C + ((int64_t)t * n_used + u) * ldc;
+            if (e < 0 || e >= n_expert) {  // no bias is read or applied
+                for (int n = 0; n < N; ++n) c[n] = 0.0f;
+                continue;
+            }
+            const uint8_t* a = (const uint8_t*)A + (size_t)t * arow;
+            int rc = qg_gemm_w4a8_cpu_mt(a, (const uint8_t*)B_gate + (size_t)e * estride, g.data(), 1, N, K, wtype, threads);
+            if (rc == QG_OK)
+                rc = qg_gemm_w4a8_cpu_mt(a, (const uint8_t*)B_up + (size_t)e * estride, up.data(), 1, N, K, wtype, threads);
+            if (rc != QG_OK) return rc;
+            // each operation one rounded fp32 operation (-ffp-contract=off), as the GPU entry
+            if (bias_gate)
+                for (int n = 0; n < N; ++n) g[n] = g[n] + bias_gate[(int64_t)e * bias_stride + n];
+            if (bias_up)
+                for (int n = 0; n < N; ++n) up[n] = up[n] + bias_up[(int64_t)e * bias_stride + n];
+            if (glu_op == QG_GLU_REGLU)
+                for (int n = 0; n < N; ++n) c[n] = (g[n] > 0.0f ? g[n] : 0.0f) * up[n];
+            else if (glu_op == QG_GLU_SWIGLU)
+                for (int n = 0; n < N; ++n) c[n] = (g[n] / (1.0f + expf(-g[n]))) * up[n];
+            else
+                for (int n = 0; n < N; ++n) {
+                    const float x = fminf(g[n], limit), y = fminf(fmaxf(up[n], -limit), limit);
+                    c[n] = (x / (1.0f + expf(alpha * (-x)))) * (y + 1.0f);
+                }
+        }
+    return QG_OK;
+}
+
+int qg_gemm_w4a8_moe_down_bias_cpu(const void* A, const void* B, const float* bias, int64_t bias_stride, int n_expert,
+                                   const int32_t* ids, int64_t ids_stride, const float* weights, int64_t w_stride, float* C,
+                                   int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
+    int be;
+    const int bb = bias_block(wtype, be);
+    // the order of qg_gemm_w4a8_moe_down_bias
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
+    if (ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N) || (weights && w_stride < n_used))
+        return QG_ERR_INVALID_ARG;
+    if (bias_stride < 0 || (bias_stride > 0 && bias_stride < N)) return QG_ERR_INVALID_ARG;
+    const size_t arow = (size_t)(K / QK) * 36, estride = (size_t)N * (size_t)(K / be) * (size_t)bb;
+    if (ldc == 0) ldc = N;
+    if (bias_stride == 0) bias_stride = N;
+    std::vector<float> d((size_t)N);
+    for (int t = 0; t < T; ++t) {
+        float* c = C + (int64_t)t * ldc;
+        for (int n = 0; n < N; ++n) c[n] = 0.0f;
+        for (int u = 0; u < n_used; ++u) {
+            const int e = ids[(int64_t)t * ids_stride + u];
+            if (e < 0 || e >= n_expert) continue;  // neither its bias, its weight nor a weight byte is read
+            const uint8_t* a = (const uint8_t*)A + ((size_t)t * n_used + (size_t)u) * arow;
+            const int rc = qg_gemm_w4a8_cpu_mt(a, (const uint8_t*)B + (size_t)e * estride, d.data(), 1, N, K, wtype, threads);
+            if (rc != QG_OK) return rc;
+            // each operation one rounded fp32 operation (-ffp-contract=off), as the GPU entry
+            if (bias)
+                for (int n = 0; n < N; ++n) d[n] = d[n] + bias[(int64_t)e * bias_stride + n];
+            const float w = weights ? weights[(int64_t)t * w_stride + u] : 1.0f;
+            for (int n = 0; n < N; ++n) c[n] = c[n] + w * d[n];
+        }
+    }
+    return QG_OK;
+}
+
 int qg_dequantize_row_mxfp4_cpu(const void* x, float* y, int64_t k) {
     if (k < 0 || k % QK != 0) return QG_ERR_BAD_K;
     if (k == 0) return QG_OK;

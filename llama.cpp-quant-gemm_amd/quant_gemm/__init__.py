@@ -37,6 +37,7 @@ Q6_K = 14  # 256-element super-blocks of 210 bytes (qg.h "Q6_K weights")
 MXFP4 = 39  # 32-element blocks of 17 bytes: an E8M0 scale byte and E2M1 codes (qg.h "MXFP4 weights")
 BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210, MXFP4: 17}
 GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* (numbered as ggml_glu_op): the ops of gemm_w4a8_moe_glu
+GLU_SWIGLU_OAI = 3  # gpt-oss's clamped SwiGLU: gemm_w4a8_moe_glu_bias alone
 ALGO_AUTO, ALGO_GEMV, ALGO_MFMA, ALGO_GENERIC, ALGO_RAGGED = 0, 1, 2, 3, 4
 WEIGHT_TYPES = (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0)
 # what gemm_w4a8 / gemm_w4a8_f32 / debug_sumi take; the layout entries (tiled, repacked, grouped, batched) keep
@@ -464,6 +465,90 @@ def moe_down_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> s
     return _config("qg_moe_down_config", T, n_used, N, K, wtype)
 
 
+def _moe_bias(bias, n_expert: int, N: int, device, what: str):
+    """A bias of the two _bias entries: None, or float32 [n_expert, N] on the experts' device with unit column stride
+    (a view with a row stride is fine) -> (tensor or None, its row stride; 0: none)."""
+    if bias is None:
+        return None, 0
+    _require(bias.is_cuda and bias.dtype == torch.float32 and bias.device == device,
+             f"{what} must be a float32 tensor on the experts' device")
+    _require(bias.dim() == 2 and tuple(bias.shape) == (n_expert, N) and (N <= 1 or bias.stride(1) == 1),
+             f"{what} must be [n_expert, N] with unit column stride")
+    stride = bias.stride(0) if n_expert > 1 else N
+    _require(stride >= N, f"{what}: row stride below N")
+    return bias, stride
+
+
+def gemm_w4a8_moe_glu_bias(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor,
+                           bias_gate: torch.Tensor | None, bias_up: torch.Tensor | None, ids: torch.Tensor, T: int,
+                           n_used: int, N: int, K: int, wtype: int = MXFP4, glu_op: int = GLU_SWIGLU_OAI,
+                           alpha: float = 1.702, limit: float = 7.0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_glu`` with per-expert biases and gpt-oss's clamped SwiGLU, for Q4_K / Q6_K / MXFP4 experts, in ONE
+    launch (qg_gemm_w4a8_moe_glu_bias): g = gate product + bias_gate[e], u = up product + bias_up[e], then ``glu_op``.
+
+    ``gate_q``, ``up_q``: [n_expert, N, K/32, 17] for MXFP4 (at any byte address), as ``gemm_w4a8_moe_glu`` otherwise.
+    ``bias_gate``, ``bias_up``: float32 [n_expert, N] CUDA tensors of one row stride (``stride(1) == 1``), or None: no
+    add. ``glu_op``: GLU_REGLU, GLU_SWIGLU, or GLU_SWIGLU_OAI, with x = min(g, limit), y = clamp(u, -limit, limit):
+    (x / (1 + expf(alpha * -x))) * (y + 1); ``alpha`` and ``limit`` are read for it alone. A slot whose id is outside
+    [0, n_expert) gets zeros, no bias applied."""
+    _require(wtype in (Q4_K, Q6_K, MXFP4), f"unsupported weight type {wtype}: the biased gate / up entry takes Q4_K, Q6_K and MXFP4")
+    _require(glu_op in (GLU_REGLU, GLU_SWIGLU, GLU_SWIGLU_OAI), f"unsupported glu_op {glu_op}")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, gate_q, ids, T, n_used, N, K, wtype, 1, out)
+    _require(up_q.is_cuda and up_q.dtype == torch.uint8 and up_q.device == w.device and up_q.numel() == w.numel(),
+             "Up experts must be a CUDA uint8 tensor of the gate experts' size, on their device")
+    up = up_q.contiguous()
+    bg, sg = _moe_bias(bias_gate, n_expert, N, w.device, "bias_gate")
+    bu, su = _moe_bias(bias_up, n_expert, N, w.device, "bias_up")
+    _require(bg is None or bu is None or sg == su, "bias_gate and bias_up must have one row stride")
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_glu_bias(_ptr(a), _ptr(w), _ptr(up), None if bg is None else _ptr(bg),
+                                                         None if bu is None else _ptr(bu), sg or su, n_expert, _ptr(ids),
+                                                         ids_stride, _ptr(out), ldc, T, n_used, N, K, wtype, glu_op, alpha,
+                                                         limit, _stream(w.device)), "gemm_w4a8_moe_glu_bias")
+    return out
+
+
+def moe_glu_bias_config(T: int, n_used: int, N: int, K: int, wtype: int = MXFP4) -> str:
+    """The launch ``gemm_w4a8_moe_glu_bias`` makes for this shape ("moe_glu:mxfp4_gemv LPR=.. WGS=.. ONE=.. grid=XxY
+    lds=..", ``moe_glu_config``'s string for Q4_K / Q6_K); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_glu_bias_config", T, n_used, N, K, wtype)
+
+
+def gemm_w4a8_moe_down_bias(activation_q: torch.Tensor, experts_q: torch.Tensor, bias: torch.Tensor | None,
+                            ids: torch.Tensor, weights: torch.Tensor | None, T: int, n_used: int, N: int, K: int,
+                            wtype: int = MXFP4, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_down`` with a per-expert bias, for Q4_K / Q6_K / MXFP4 experts, in ONE launch
+    (qg_gemm_w4a8_moe_down_bias): C[t, :] = sum over u of weights[t, u] * (product of slot (t, u) + bias[ids[t, u]]).
+
+    ``bias``: float32 [n_expert, N] CUDA tensor (``stride(1) == 1``), or None: no add. Everything else as
+    ``gemm_w4a8_moe_down``; a slot whose id is outside [0, n_expert) contributes nothing, its bias and weight unread."""
+    _require(wtype in (Q4_K, Q6_K, MXFP4), f"unsupported weight type {wtype}: the biased down entry takes Q4_K, Q6_K and MXFP4")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, n_used, out,
+                                                        per_token=True)
+    b, b_stride = _moe_bias(bias, n_expert, N, w.device, "bias")
+    w_stride = n_used
+    if weights is not None:
+        _require(weights.is_cuda and weights.dtype == torch.float32 and weights.device == w.device,
+                 "weights must be a float32 tensor on the experts' device")
+        _require(weights.dim() == 2 and tuple(weights.shape) == (T, n_used) and (n_used <= 1 or weights.stride(1) == 1),
+                 "weights must be [T, n_used] with unit column stride")
+        w_stride = weights.stride(0) if T > 1 else n_used
+        _require(w_stride >= n_used, "weights row stride below n_used")
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_down_bias(_ptr(a), _ptr(w), None if b is None else _ptr(b), b_stride, n_expert,
+                                                          _ptr(ids), ids_stride, None if weights is None else _ptr(weights),
+                                                          w_stride, _ptr(out), ldc, T, n_used, N, K, wtype,
+                                                          _stream(w.device)), "gemm_w4a8_moe_down_bias")
+    return out
+
+
+def moe_down_bias_config(T: int, n_used: int, N: int, K: int, wtype: int = MXFP4) -> str:
+    """The launch ``gemm_w4a8_moe_down_bias`` makes for this shape ("moe_down:mxfp4_gemv LPR=.. WGS=.. ONE=.. SW=..
+    grid=XxY lds=..", ``moe_down_config``'s string for Q4_K / Q6_K); nothing is launched. Raises where the shape is not
+    served."""
+    return _config("qg_moe_down_bias_config", T, n_used, N, K, wtype)
+
+
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
     """Load-time layout for K/32 not a multiple of 8 (qg_repack_weights): [N, K'/32, bb] uint8,
     the real blocks then zero blocks (K'/32 = round_up(K/32, 8)). Feed it to gemm_w4a8_prepacked."""
@@ -862,4 +947,5 @@ __all__ = [
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
     "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
+    "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
 ]

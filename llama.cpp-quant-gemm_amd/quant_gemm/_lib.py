@@ -21,7 +21,7 @@ STATUS = {0: "ok", -1: "invalid argument", -2: "K must be a positive multiple of
           -5: "HIP launch error"}
 
 # exported symbols and their signatures (kept in sync with include/qg/qg.h; tests check both ways)
-P, I, I64, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
+P, I, I64, SZ, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 SIGNATURES = {
     "qg_gemm_w4a8": ([P, P, P, I, I, I, I, P], I),
     "qg_gemm_w4a8_ex": ([P, P, P, I, I, I, I, I, P], I),
@@ -45,6 +45,10 @@ SIGNATURES = {
     "qg_moe_glu_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_down": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
     "qg_moe_down_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_glu_bias": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, P], I),
+    "qg_moe_glu_bias_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_down_bias": ([P, P, P, I64, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
+    "qg_moe_down_bias_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_workspace_size": ([I, I, I, I], SZ),
     "qg_gemm_w4a8_ws": ([P, P, P, I, I, I, I, P, SZ, P], I),
     "qg_repack_weights_bytes": ([I, I, I], SZ),
@@ -101,6 +105,8 @@ SIGNATURES = {
     "qg_mul_mat_id_from_view_batch": ([P, P, P, P, P, SZ, P], I),
     "qg_mul_mat_id_glu_from_view": ([P, P, P, P, P, I, P], I),
     "qg_mul_mat_id_down_from_view": ([P, P, P, P, P, P], I),
+    "qg_mul_mat_id_glu_bias_from_view": ([P, P, P, P, P, P, P, I, F, F, P], I),
+    "qg_mul_mat_id_down_bias_from_view": ([P, P, P, P, P, P, P], I),
     "qg_validate_view_types": ([P, P, P, I, I, I], I),
     "qg_gemm_fp32": ([P, P, P, I, I, I, P], I),
     "qg_gguf_open": ([ctypes.c_char_p, ctypes.POINTER(P)], I),

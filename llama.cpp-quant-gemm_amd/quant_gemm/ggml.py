@@ -123,6 +123,30 @@ def mul_mat_id_down_from_ggml(experts: TensorView, act: TensorView, ids: TensorV
                "qg_mul_mat_id_down_from_view")
 
 
+def mul_mat_id_glu_bias_from_ggml(gate: TensorView, up: TensorView, bias_gate: TensorView | None,
+                                  bias_up: TensorView | None, act: TensorView, ids: TensorView, out: TensorView,
+                                  glu_op: int = 3, alpha: float = 1.702, limit: float = 7.0) -> None:
+    """``mul_mat_id_glu_from_ggml`` with per-expert biases and gpt-oss's clamped SwiGLU (``glu_op`` 3), for Q4_K /
+    Q6_K / MXFP4 experts (qg_mul_mat_id_glu_bias_from_view). A bias: F32 [N, n_expert] with nb[0] = 4, or None."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ref = lambda v: None if v is None else ctypes.byref(v)
+    _lib.check(_lib.load().qg_mul_mat_id_glu_bias_from_view(ctypes.byref(gate), ctypes.byref(up), ref(bias_gate),
+                                                            ref(bias_up), ctypes.byref(act), ctypes.byref(ids),
+                                                            ctypes.byref(out), glu_op, alpha, limit, st),
+               "qg_mul_mat_id_glu_bias_from_view")
+
+
+def mul_mat_id_down_bias_from_ggml(experts: TensorView, bias: TensorView | None, act: TensorView, ids: TensorView,
+                                   weights: TensorView | None, out: TensorView) -> None:
+    """``mul_mat_id_down_from_ggml`` with a per-expert bias added to every product ahead of the weighted sum, for
+    Q4_K / Q6_K / MXFP4 experts (qg_mul_mat_id_down_bias_from_view). ``bias``: F32 [N, n_expert] with nb[0] = 4, or None."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ref = lambda v: None if v is None else ctypes.byref(v)
+    _lib.check(_lib.load().qg_mul_mat_id_down_bias_from_view(ctypes.byref(experts), ref(bias), ctypes.byref(act),
+                                                             ctypes.byref(ids), ref(weights), ctypes.byref(out), st),
+               "qg_mul_mat_id_down_bias_from_view")
+
+
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:
     """include/llama_adapter.h:110-117."""
     return bool(_lib.load().qg_validate_view_types(ctypes.byref(act), ctypes.byref(w), ctypes.byref(out), ea, ew, eo))

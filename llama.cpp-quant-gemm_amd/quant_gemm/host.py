@@ -12,7 +12,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libqg_host.so")
-P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+P, I, I64, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 SIGNATURES = {
     "qg_gemm_w4a8_q4_0_cpu": ([P, P, P, I, I, I], I),
     "qg_vec_dot_q4_0_q8_1_cpu": ([I, P, P, P], None),
@@ -22,6 +22,8 @@ SIGNATURES = {
     "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_cpu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_down_cpu": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_glu_bias_cpu": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, I], I),
+    "qg_gemm_w4a8_moe_down_bias_cpu": ([P, P, P, I64, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_fp32_cpu": ([P, P, P, I, I, I], I),
     "qg_quantize_row_q8_1_cpu": ([P, P, I64], I),
     "qg_quantize_row_q4_0_cpu": ([P, P, I64], I),
@@ -30,7 +32,7 @@ SIGNATURES = {
 }
 # 12: Q4_K, 14: Q6_K, 256-element super-blocks; 39: MXFP4, 32-element blocks of 17 bytes
 BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210, 39: 17}
-GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* of qg.h
+GLU_REGLU, GLU_SWIGLU, GLU_SWIGLU_OAI = 0, 2, 3  # QG_GLU_* of qg.h
 _lib = None
 
 
@@ -153,6 +155,64 @@ def gemm_w4a8_moe_down(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, 
     _ok(load().qg_gemm_w4a8_moe_down_cpu(_p(a_q), _p(experts_q), n_expert, _p(ids), ids_stride,
                                          None if weights is None else _p(weights), w_stride or n_used, _p(c), n, t, n_used,
                                          n, k, wtype, threads), "gemm_w4a8_moe_down_cpu")
+    return c
+
+
+def _bias(b: np.ndarray | None, n_expert: int, n: int, what: str):
+    """A bias of the _bias twins: None, or float32 [n_expert, >= n] -> (array or None, its row stride)."""
+    if b is None:
+        return None, 0
+    b = np.ascontiguousarray(b, np.float32)
+    if b.ndim != 2 or b.shape[0] != n_expert or b.shape[1] < n:
+        raise RuntimeError(f"{what}: a bias must be [n_expert, >= n]")
+    return b, b.shape[1]
+
+
+def gemm_w4a8_moe_glu_bias(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, bias_gate: np.ndarray | None,
+                           bias_up: np.ndarray | None, ids: np.ndarray, t: int, n_used: int, n: int, k: int,
+                           wtype: int = 39, glu_op: int = GLU_SWIGLU_OAI, alpha: float = 1.702, limit: float = 7.0,
+                           threads: int = 1, ids_stride: int | None = None) -> np.ndarray:
+    """C[t, n_used, n] of qg_gemm_w4a8_moe_glu_bias_cpu: ``gemm_w4a8_moe_glu`` with the per-expert bias rows
+    (float32 [n_expert, >= n] of one row length, or None) added to g and to u ahead of the op, GLU_SWIGLU_OAI among the
+    ops, and Q4_K / Q6_K / MXFP4 experts."""
+    a_q, gate_q, up_q = np.ascontiguousarray(a_q), np.ascontiguousarray(gate_q), np.ascontiguousarray(up_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    if gate_q.size != up_q.size:
+        raise RuntimeError("gemm_w4a8_moe_glu_bias_cpu: gate and up experts differ in size")
+    n_expert = gate_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    bg, sg = _bias(bias_gate, n_expert, n, "gemm_w4a8_moe_glu_bias_cpu")
+    bu, su = _bias(bias_up, n_expert, n, "gemm_w4a8_moe_glu_bias_cpu")
+    if bg is not None and bu is not None and sg != su:
+        raise RuntimeError("gemm_w4a8_moe_glu_bias_cpu: the two biases differ in row length")
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    c = np.empty((t, n_used, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_glu_bias_cpu(_p(a_q), _p(gate_q), _p(up_q), None if bg is None else _p(bg),
+                                             None if bu is None else _p(bu), sg or su, n_expert, _p(ids), ids_stride, _p(c),
+                                             n, t, n_used, n, k, wtype, glu_op, alpha, limit, threads),
+        "gemm_w4a8_moe_glu_bias_cpu")
+    return c
+
+
+def gemm_w4a8_moe_down_bias(a_q: np.ndarray, experts_q: np.ndarray, bias: np.ndarray | None, ids: np.ndarray,
+                            weights: np.ndarray | None, t: int, n_used: int, n: int, k: int, wtype: int = 39,
+                            threads: int = 1, ids_stride: int | None = None, w_stride: int | None = None) -> np.ndarray:
+    """C[t, n] of qg_gemm_w4a8_moe_down_bias_cpu: ``gemm_w4a8_moe_down`` with the per-expert bias row (float32
+    [n_expert, >= n], or None) added to every product ahead of the fold, and Q4_K / Q6_K / MXFP4 experts."""
+    a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    n_expert = experts_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    b, sb = _bias(bias, n_expert, n, "gemm_w4a8_moe_down_bias_cpu")
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float32)
+        if w_stride is None:
+            w_stride = weights.size // t if t else n_used
+    c = np.empty((t, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_down_bias_cpu(_p(a_q), _p(experts_q), None if b is None else _p(b), sb, n_expert, _p(ids),
+                                              ids_stride, None if weights is None else _p(weights), w_stride or n_used,
+                                              _p(c), n, t, n_used, n, k, wtype, threads), "gemm_w4a8_moe_down_bias_cpu")
     return c
 
 
