@@ -659,8 +659,8 @@ int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, si
  * bias prefer qg_gemm_w4a8_moe_glu / qg_gemm_w4a8_moe_down: with null biases the new entries give the same bits in
  * 1.00 .. 1.01 of their time captured at Qwen3-MoE's shape (glu at T = 1: 7.10 against 7.03 us, outside that run's
  * spread of 0.02; the other three classes within it).
- * Not built: MXFP4 in the prefill and batch entries, FP32-input or Q8_1-writing fused forms, GEGLU, a dense (no ids)
- * GLU entry, an MXFP4 quantizer. */
+ * Not built: FP32-input or Q8_1-writing fused forms, GEGLU, a dense (no ids) GLU entry, an MXFP4 quantizer (MXFP4 in
+ * the prefill and batch entries: the two _bias entries below). */
 #define QG_GLU_SWIGLU_OAI 3   /* beside QG_GLU_REGLU 0 / QG_GLU_SWIGLU 2 */
 int qg_gemm_w4a8_moe_glu_bias(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
                               const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids, int64_t ids_stride,
@@ -671,6 +671,58 @@ int qg_gemm_w4a8_moe_down_bias(const void* A_q8_1, const void* B_experts, const 
                                const int32_t* ids, int64_t ids_stride, const float* weights, int64_t w_stride, float* C,
                                int64_t ldc, int T, int n_used, int N, int K, int wtype, qg_stream_t stream);
 int qg_moe_down_bias_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- the two expert-grouped entries with per-expert bias and MXFP4 experts ----
+ * qg_gemm_w4a8_moe_prefill and qg_gemm_w4a8_moe_batch above with ggml's add_id folded in, for wtype QG_TYPE_Q4_K,
+ * QG_TYPE_Q6_K or QG_TYPE_MXFP4 (which the two above refuse): what a gpt-oss FFN block needs beyond a handful of tokens,
+ * where each of its three products is followed by a per-expert bias. With e = ids[t * ids_stride + u], s = t * n_used + u:
+ *   C[s * ldc + n] = (sum_k B[e][n][k] * A[t * a_rows + u % a_rows][k]) + bias[e * bias_stride + n]
+ * The add is one rounded fp32 addition on the finished product. bias: float [n_expert][bias_stride] in DEVICE memory,
+ * 4-B aligned, bias_stride = 0 means N. bias == NULL: no addition at all (not an add of 0.0f: a -0.0f product stays
+ * -0.0f). An id outside [0, n_expert) gives N times +0.0f: no weight byte and no bias is read.
+ * Everything else is the contract of the entry each stands beside: slot numbering, a_rows, ids_stride, ldc, the limits
+ * of 65535 slots and 4096 experts, the workspace (qg_gemm_w4a8_moe_prefill_workspace_size /
+ * qg_gemm_w4a8_moe_batch_workspace_size serve these entries too, with the same rules), capture (the host never reads
+ * ids; a replay follows the ids it finds), an empty call QG_OK.
+ * MXFP4 weights need no alignment: B_experts and the expert stride N * K/32 * 17 are any number of bytes; K is a positive
+ * multiple of 32 (Q4_K / Q6_K: of 256, with their alignment rules).
+ * Validation: the order of the entry beside it; a non-null bias off 4 B -> QG_ERR_ALIGN beside the other pointers;
+ * bias_stride < 0 or 0 < bias_stride < N -> QG_ERR_INVALID_ARG beside ids_stride (whether or not a bias is given); then
+ * the workspace checks; then the QG_ERR_UNSUPPORTED shapes.
+ * qg_gemm_w4a8_moe_prefill_bias, family "moe:mxfp4_mmq" for MXFP4: the plan, tiles and forms of
+ *   qg_gemm_w4a8_moe_prefill; (TT, RG) by its general rule (not the Q6_K one), whose thresholds were measured for the
+ *   K-quants. Bits: every product has the bits of the eager "mxfp4_mmq" product at the same RG on its own activation row
+ *   and weight row, whatever TT, the tile and the slot's position; two launches give identical bits. Q4_K / Q6_K: the
+ *   products of qg_gemm_w4a8_moe_prefill, bit for bit (with a null bias, its launch).
+ * qg_gemm_w4a8_moe_batch_bias, family "moeb:mxfp4_gemv" for MXFP4: the plan and tiles of qg_gemm_w4a8_moe_batch; LPR, WGS
+ *   and ONE those of qg_moe_config for the same K. An LDS record is one block, 48 B, so a tile needs R * K/32 * 48 bytes:
+ *   R = 8 up to K = 13632, R = 4 up to K = 27296, R = 2 up to K = 54592, beyond that QG_ERR_UNSUPPORTED (Q4_K / Q6_K: the
+ *   thresholds of qg_gemm_w4a8_moe_batch). Bits: every product is bit-identical to qg_gemm_w4a8_moe on the same operands.
+ * qg_moe_prefill_bias_config / qg_moe_batch_bias_config: for Q4_K / Q6_K the strings of qg_moe_prefill_config /
+ * qg_moe_batch_config (the bias is no part of the launch's shape); for MXFP4 "moe:mxfp4_mmq TT=.. RG=.. KS=.. R=..
+ * grid=XxY" and "moeb:mxfp4_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=..".
+ * A gpt-oss FFN block at prompt size: quantize, qg_gemm_w4a8_moe_prefill_bias twice (gate, up), the caller's clamped
+ * SwiGLU, quantize, qg_gemm_w4a8_moe_prefill_bias (down, a_rows = n_used), the caller's weighted sum.
+ * Which entry for which T (measured on an MI355X at gpt-oss's N = K = 2880, MXFP4, uniform router, captured, against
+ * qg_gemm_w4a8_moe plus torch's gathered bias add on the same operands; DESIGN.md 3j,
+ * profiles/moe_id_bias/ab_moe_id_bias.txt). 4 of 32 experts: qg_gemm_w4a8_moe_batch_bias from T = 8 (0.89 of the
+ * sequence's time) through T = 64 (0.37), where qg_gemm_w4a8_moe_prefill_bias draws level (0.41) and then leads: 0.31 at
+ * T = 256, 0.08 at T = 1024. 4 of 128 experts: the batch entry from T = 32 (0.91; 0.75 at T = 64), the prefill entry
+ * from T = 256 (0.38; 0.30 at T = 1024). NOT ahead, keep qg_gemm_w4a8_moe and the caller's add: the prefill entry at
+ * T = 16 (1.35 and 2.24 of the sequence's time) and at T = 64 with 128 experts (1.25); the batch entry with 128 experts
+ * at T = 8 and 16 (1.07, 1.02). The prefill's (TT, RG) thresholds are the K-quants' and do not suit MXFP4 everywhere: at
+ * T = 256 with 32 experts the rule's (2, 1) takes 2.1 times as long as a forced (4, 4). Q4_K / Q6_K with a bias cost a
+ * third launch (an add kernel behind the unbiased entries' kernels): a convenience there, not a saving.
+ * Not built: a fused GLU at prefill or batch size, one plan shared by the three products of a layer, an automatic choice
+ * between the entries, the 32-element types in these entries, an MXFP4 quantizer. */
+int qg_gemm_w4a8_moe_prefill_bias(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
+                                  int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
+                                  int N, int K, int wtype, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_prefill_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
+int qg_gemm_w4a8_moe_batch_bias(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
+                                int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
+                                int N, int K, int wtype, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_batch_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */
@@ -810,6 +862,15 @@ int qg_mul_mat_id_glu_bias_from_view(const qg_tensor_view* as_gate, const qg_ten
 int qg_mul_mat_id_down_bias_from_view(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
                                       const qg_tensor_view* ids, const qg_tensor_view* weights, qg_tensor_view* out,
                                       qg_stream_t stream);
+/* qg_mul_mat_id_from_view_ws / qg_mul_mat_id_from_view_batch with the bias view of qg_gemm_w4a8_moe_prefill_bias /
+ * qg_gemm_w4a8_moe_batch_bias, for Q4_K / Q6_K / MXFP4 experts: bias NULL (no add) or F32 with ne = [N, n_expert],
+ * nb[0] = 4, nb[1] a multiple of 4 and >= 4 N; its refusals as in the two entries above. */
+int qg_mul_mat_id_bias_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                    const qg_tensor_view* ids, qg_tensor_view* out, void* workspace, size_t workspace_bytes,
+                                    qg_stream_t stream);
+int qg_mul_mat_id_bias_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                       const qg_tensor_view* ids, qg_tensor_view* out, void* workspace, size_t workspace_bytes,
+                                       qg_stream_t stream);
 /* validate_tensor_types (llama_adapter.h:110-117): 1 if all three types match, else 0. */
 int qg_validate_view_types(const qg_tensor_view* activation, const qg_tensor_view* weights,
                            const qg_tensor_view* output, int expected_activation_type, int expected_weight_type,

@@ -76,6 +76,15 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A_q8_1, const void* B_experts, int n_e
                               int64_t ids_stride, const float* weights, int64_t w_stride, float* C, int64_t ldc, int T,
                               int n_used, int N, int K, int wtype, int threads);
 
+/* Host twin of qg_gemm_w4a8_moe_prefill_bias / qg_gemm_w4a8_moe_batch_bias (qg.h), beside qg_gemm_w4a8_moe_cpu: the same
+ * arguments without the workspace, `ids` and `bias` in host memory, `threads` as above; wtype Q4_K, Q6_K or MXFP4. Every
+ * product has the bits of qg_gemm_w4a8_moe_cpu; where bias is non-null, bias[e][n] is then added with one rounded fp32
+ * addition. An id outside [0, n_expert) gives N times +0.0f, its bias not read. The same validation codes (no alignment is
+ * asked); no shape is unsupported. */
+int qg_gemm_w4a8_moe_bias_cpu(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
+                              int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
+                              int N, int K, int wtype, int threads);
+
 /* Host twins of qg_gemm_w4a8_moe_glu_bias / qg_gemm_w4a8_moe_down_bias (qg.h): the same arguments with `ids`, `weights`
  * and the biases in host memory, and `threads` as above; wtype Q4_K, Q6_K or MXFP4. The products have the bits of
  * qg_gemm_w4a8_moe_cpu; a non-null bias is added with one rounded fp32 addition (g + bias_gate[e][n], u + bias_up[e][n],

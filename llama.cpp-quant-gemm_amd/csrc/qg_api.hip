@@ -431,7 +431,8 @@ struct MoeCall {
     int slots;     // moe_front: T * n_used
     const void* B_up; int glu_op;
     const float* weights; int64_t w_stride;
-    // qg_gemm_w4a8_moe_glu_bias, _moe_down_bias (biased; down's one bias is bias_gate). After moe_front: bias_stride never 0
+    // qg_gemm_w4a8_moe_glu_bias, _moe_down_bias, _moe_prefill_bias, _moe_batch_bias (biased; the one bias of the last three
+    // is bias_gate). After moe_front: bias_stride never 0
     bool biased;
     const float* bias_gate; const float* bias_up; int64_t bias_stride;
     float alpha, limit;
@@ -448,7 +449,7 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 // or the entry runs a plan in a workspace sized for tiles of min_r rows. up: the entry has a second weights pointer,
 // B_up, checked beside B with the same mask. down: the entry is qg_gemm_w4a8_moe_down: weights stands beside the other
 // pointers (null allowed, 4 B otherwise), w_stride beside ids_stride, and the grid's y is the token, so T is what 65535
-// bounds (slots stays 0). c.biased: the entry is one of the two _bias ones: it takes MXFP4 beside the super-block types,
+// bounds (slots stays 0). c.biased: the entry is one of the four _bias ones: it takes MXFP4 beside the super-block types,
 // its bias pointers stand beside the other pointers (null allowed, 4 B otherwise), bias_stride and the OAI op's alpha
 // and limit beside ids_stride.
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
@@ -457,7 +458,7 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
 int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    // (MXFP4 is a type of qg_gemm_w4a8_moe and the two _bias entries: elsewhere it is refused as the 32-element types are)
+    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries: elsewhere it is refused as the 32-element types are)
     const bool ksb = is_sb_type(c.wtype) || ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
@@ -538,6 +539,33 @@ int run_moe_batch(MoeCall& c) {
     MoePlanArgs a = moe_kernel_args<MoePlanArgs>(c);
     a.ws = (int32_t*)c.ws;
     return hip_status(launch_moe_batch(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_prefill_bias, qg_moe_prefill_bias_config: Q4_K / Q6_K / MXFP4 (c.biased; the one bias is bias_gate),
+// run_moe_prefill's refusals.
+MoeBiasArgs moe_bias_args(const MoeCall& c) {
+    MoeBiasArgs a;
+    static_cast<MoePlanArgs&>(a) = moe_kernel_args<MoePlanArgs>(c);
+    a.ws = (int32_t*)c.ws;
+    a.bias = c.bias_gate; a.bias_stride = (long)c.bias_stride;
+    return a;
+}
+
+int run_moe_prefill_bias(MoeCall& c) {
+    c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
+    const int rc = moe_front(c, false, MOE_PREFILL_MIN_R);
+    if (rc != QG_GO) return rc;
+    return hip_status(launch_moe_prefill_bias(moe_bias_args(c), c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_batch_bias, qg_moe_batch_bias_config: Q4_K / Q6_K / MXFP4 (c.biased), run_moe_batch's refusals.
+int run_moe_batch_bias(MoeCall& c) {
+    c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
+    const int rc = moe_front(c, false, MOE_BATCH_MIN_R);
+    if (rc != QG_GO) return rc;
+    const int R = moe_batch_rows(c.slots, c.n_expert, c.K, c.wtype);
+    if (!moe_gemv_route(c) || R == 0 || moe_max_tiles(c.slots, c.n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
+    return hip_status(launch_moe_batch_bias(moe_bias_args(c), c.wtype, c.st, c.describe, c.describe_len));
 }
 
 // qg_gemm_w4a8_moe_glu, qg_moe_glu_config: Q4_K / Q6_K. Its own refusals: a glu_op it does not have, a shape off the
@@ -888,6 +916,56 @@ int qg_mul_mat_id_down_bias_from_view(const qg_tensor_view* as, const qg_tensor_
     if ((rc = bias_view(bias, c, c.bias_gate, c.bias_stride)) != QG_GO) return rc;
     c.st = (hipStream_t)stream;
     return run_moe_down_bias(c);
+}
+
+int qg_gemm_w4a8_moe_prefill_bias(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
+                                  int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
+                                  int N, int K, int wtype, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MoeCall c{A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+              workspace_bytes, (hipStream_t)stream};
+    c.bias_gate = bias; c.bias_stride = bias_stride;
+    return run_moe_prefill_bias(c);
+}
+
+int qg_moe_prefill_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_prefill_bias, T, n_used, n_expert, N, K, wtype, buf, len);
+}
+
+int qg_gemm_w4a8_moe_batch_bias(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
+                                int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
+                                int N, int K, int wtype, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MoeCall c{A_q8_1, a_rows, B_experts, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace,
+              workspace_bytes, (hipStream_t)stream};
+    c.bias_gate = bias; c.bias_stride = bias_stride;
+    return run_moe_batch_bias(c);
+}
+
+int qg_moe_batch_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_batch_bias, T, n_used, n_expert, N, K, wtype, buf, len);
+}
+
+// qg_mul_mat_id_bias_from_view_ws / _batch: the views of qg_mul_mat_id_from_view_ws, then the bias view, then the entry
+static int mul_mat_id_bias_from_view(int (*run)(MoeCall&), const qg_tensor_view* as, const qg_tensor_view* bias,
+                                     const qg_tensor_view* b, const qg_tensor_view* ids, const qg_tensor_view* out, void* ws,
+                                     size_t ws_bytes, qg_stream_t stream) {
+    MoeCall c;
+    int rc = mul_mat_id_view(as, b, ids, out, c);
+    if (rc != QG_GO) return rc;
+    if ((rc = bias_view(bias, c, c.bias_gate, c.bias_stride)) != QG_GO) return rc;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    return run(c);
+}
+
+int qg_mul_mat_id_bias_from_view_ws(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                    const qg_tensor_view* ids, qg_tensor_view* out, void* workspace, size_t workspace_bytes,
+                                    qg_stream_t stream) {
+    return mul_mat_id_bias_from_view(run_moe_prefill_bias, as, bias, b, ids, out, workspace, workspace_bytes, stream);
+}
+
+int qg_mul_mat_id_bias_from_view_batch(const qg_tensor_view* as, const qg_tensor_view* bias, const qg_tensor_view* b,
+                                       const qg_tensor_view* ids, qg_tensor_view* out, void* workspace, size_t workspace_bytes,
+                                       qg_stream_t stream) {
+    return mul_mat_id_bias_from_view(run_moe_batch_bias, as, bias, b, ids, out, workspace, workspace_bytes, stream);
 }
 
 void qg_release_workspaces(void) { release_workspaces(); }

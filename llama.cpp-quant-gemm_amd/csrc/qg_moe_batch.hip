@@ -1,5 +1,6 @@
 // qg_moe_batch.hip — the expert-grouped decode GEMV (qg_gemm_w4a8_moe_batch, ggml's mul_mat_id for batched decode),
-// families "moeb:q4k_gemv" and "moeb:q6k_gemv". DESIGN.md 3e.
+// families "moeb:q4k_gemv" and "moeb:q6k_gemv". DESIGN.md 3e. And its biased twin qg_gemm_w4a8_moe_batch_bias with MXFP4
+// experts beside them, family "moeb:mxfp4_gemv" (DESIGN.md 3j): kernels of its own further down, these untouched.
 //
 // Two launches on the caller's stream, no allocation, no synchronisation, the host never reads ids:
 //  1. moe_plan_kernel (qg_moe_plan.hip) with tiles of R = 2, 4 or 8 rows: the T * n_used slots counting-sorted by
@@ -74,6 +75,49 @@ template <int MT, int LPR, int WGS, bool ONE> __global__ __launch_bounds__(WGS) 
 #undef QG_KQ_ABLK
 #undef QG_KQ_DECLARE_TILE
 
+// ---- the biased entry (qg_gemm_w4a8_moe_batch_bias): kernels beside the two above, which stay ----------
+// MXFP4 alone: Q4_K / Q6_K run the two kernels above as they are and then launch_moe_bias_add (qg_moe_plan.hpp), so each
+// K-quant body stays included once in this file. The same prologue and hooks on MoeBiasArgs. The body's last statement is `QG_KQ_OUT(m) = acc[m]`, run by the lane
+// that holds the row's reduced sum: here the hook names a MoebOut, whose assignment stores the sum plus the expert's
+// bias at the lane's row -- one rounded addition after the reduction (BIAS = false: no load, no pointer test).
+template <bool BIAS> struct MoebOut {
+    float* c;
+    const float* b;
+    __device__ __forceinline__ void operator=(float v) const {
+        if constexpr (BIAS) *c = v + *b;
+        else *c = v;
+    }
+};
+#define QG_KQ_DECLARE_TILE
+#define QG_KQ_ABLK(g) A + ((long)mt.arows[(g) / nb] * nb + ((g) - (g) / nb * nb)) * 9
+#define QG_KQ_OUT(m) MoebOut<BIAS>{C + (long)srt[m] * ldc + row, BIAS ? bias_e + row : nullptr}
+#define QG_MOEB_PROLOGUE                                                                          \
+    constexpr int RPB_ = (WGS / 64) * (64 / LPR);                                                 \
+    const int tile = xcd_tile_x();                                                                \
+    MoeTile mt;                                                                                   \
+    if (!moeb_tile<RPB_, WGS>(a, tile, mt)) return;                                               \
+    const uint32_t* __restrict__ A = static_cast<const uint32_t*>(a.A);                           \
+    const uint8_t* __restrict__ B = static_cast<const uint8_t*>(a.B) + (long)mt.e * a.estride;    \
+    const float* __restrict__ bias_e = BIAS ? a.bias + (long)mt.e * a.bias_stride : nullptr;      \
+    const int M = mt.rows, N = a.N, K = a.K;                                                      \
+    void* __restrict__ out = a.C;                                                                 \
+    const long ldc = a.ldc;                                                                       \
+    constexpr bool SUMI = false;                                                                  \
+    int srt[MT];                                                                                  \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) srt[m] = mt.sorted[min(m, mt.rows - 1)];
+
+// MXFP4: the body of mxfp4_gemv_kernel (qg_mxfp4_gemv.hip) at the LPR, WGS and ONE of the single M = 1 call
+// (kq_gemv_form_units(K / 32)); an LDS record is one block. The expert's matrix starts at any byte.
+template <int MT, int LPR, int WGS, bool ONE, bool BIAS>
+__global__ __launch_bounds__(WGS) void mxfp4_moeb_kernel(const MoeBiasArgs a) {
+    QG_MOEB_PROLOGUE
+#include "qg_mxfp4_gemv_body.inc"
+}
+#undef QG_MOEB_PROLOGUE
+#undef QG_KQ_OUT
+#undef QG_KQ_ABLK
+#undef QG_KQ_DECLARE_TILE
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 using Launch = MoeLaunch<MoePlanArgs>;
 
@@ -113,17 +157,62 @@ template <int WT> hipError_t moeb_r(const Launch& L) {
     return hipErrorInvalidValue;
 }
 
+// The biased entry. Q4_K / Q6_K: the launch of the entry beside it, kernels and all, then the bias add where there is one.
+using BiasLaunch = MoeLaunch<MoeBiasArgs>;
+
+template <int WT, int MT> hipError_t moeb_bias_mt(const BiasLaunch& L) {
+    const MoeBiasArgs& a = L.a;
+    if constexpr (WT != QG_TYPE_MXFP4) {
+        const hipError_t e = moeb_mt<WT, MT>(Launch{a, L.st, L.describe, L.describe_len});
+        return e != hipSuccess || L.describe || !a.bias ? e : launch_moe_bias_add(a, L.st);
+    }
+    return kq_gemv_form_units(a.K / QK, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+        constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
+        constexpr bool ONE = one;
+        const size_t lds = (size_t)MT * moe_batch_row_lds(a.K, WT);
+        const int gy = (int)moe_max_tiles(a.slots, a.n_expert, MT);
+        if (L.describe) {
+            describe_line(L.describe, L.describe_len, "moeb:mxfp4_gemv R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", MT, LPR, WGS,
+                          (int)ONE, (a.N + RPB - 1) / RPB, gy, lds);
+            return hipSuccess;
+        }
+        int rsh = 0;
+        while ((1 << rsh) < MT) ++rsh;
+        const hipError_t e = launch_moe_plan_rows(a, rsh, L.st);
+        if (e != hipSuccess) return e;
+        static std::atomic<unsigned long long> done[2];
+        if (a.bias) return moe_enqueue(mxfp4_moeb_kernel<MT, LPR, WGS, ONE, true>, L, RPB, gy, WGS, lds, done[0]);
+        else return moe_enqueue(mxfp4_moeb_kernel<MT, LPR, WGS, ONE, false>, L, RPB, gy, WGS, lds, done[1]);
+    });
+}
+
+template <int WT> hipError_t moeb_bias_r(const BiasLaunch& L) {
+    switch (moe_batch_rows(L.a.slots, L.a.n_expert, L.a.K, WT)) {
+        case 2: return moeb_bias_mt<WT, 2>(L);
+        case 4: return moeb_bias_mt<WT, 4>(L);
+        case 8: return moeb_bias_mt<WT, 8>(L);
+    }
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
+
+// Bytes of the LDS records of one gathered row: K / 256 super-block records, or K / 32 block records for MXFP4 (48 B).
+size_t moe_batch_row_lds(int K, int wtype) {
+    if (wtype == QG_TYPE_MXFP4) return (size_t)(K / QK) * MXFP4_REC_DW * 4;
+    return (size_t)(K / SB_ELEMS) * kq_gemv_rec_dw(wtype) * 4;
+}
 
 // Rows per tile. The expected rows per expert, per = ceil(slots / n_expert), rounded up to the body's MT = 2 / 4 / 8
 // (a tile costs one pass over the expert whatever its rows; a larger MT than the rows need only adds registers and LDS),
 // then halved until the R records of K / 256 super-blocks fit 160 KiB (Q4_K: R = 8 up to K = 15360, R = 4 up to 30976;
-// Q6_K: 17152 and 34304). The thresholds are these by construction; profiles/moe_batch/README.md says what has been
+// Q6_K: 17152 and 34304; MXFP4, a 48-B record per block: R = 8 up to K = 13632, R = 4 up to 27296, R = 2 up to 54592).
+// The thresholds are these by construction; profiles/moe_batch/README.md says what has been
 // measured of them.
 int moe_batch_rows(long slots, int n_expert, int K, int wtype) {
     const long per = (slots + n_expert - 1) / n_expert;
     int r = per <= 2 ? 2 : per <= 4 ? 4 : 8;
-    const size_t row = (size_t)(K / SB_ELEMS) * kq_gemv_rec_dw(wtype) * 4;
+    const size_t row = moe_batch_row_lds(K, wtype);
     while (r >= MOE_BATCH_MIN_R && r * row > MOE_BATCH_LDS_MAX) r >>= 1;
     return r >= MOE_BATCH_MIN_R ? r : 0;
 }
@@ -132,6 +221,14 @@ hipError_t launch_moe_batch(const MoePlanArgs& a, int wtype, hipStream_t st, cha
     const Launch L{a, st, describe, describe_len};
     if (wtype == QG_TYPE_Q4_K) return moeb_r<QG_TYPE_Q4_K>(L);
     if (wtype == QG_TYPE_Q6_K) return moeb_r<QG_TYPE_Q6_K>(L);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_moe_batch_bias(const MoeBiasArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    const BiasLaunch L{a, st, describe, describe_len};
+    if (wtype == QG_TYPE_Q4_K) return moeb_bias_r<QG_TYPE_Q4_K>(L);
+    if (wtype == QG_TYPE_Q6_K) return moeb_bias_r<QG_TYPE_Q6_K>(L);
+    if (wtype == QG_TYPE_MXFP4) return moeb_bias_r<QG_TYPE_MXFP4>(L);
     return hipErrorInvalidValue;
 }
 

@@ -57,6 +57,17 @@ static_assert(sizeof(MoePlanArgs) == 88 && offsetof(MoePlanArgs, ws) == 32 && of
                   offsetof(MoePlanArgs, slots) == 84,
               "the kernarg layout");
 
+// The kernel argument of the two biased entries (qg_gemm_w4a8_moe_prefill_bias, _moe_batch_bias): the plan's, which
+// the plan launch and the tile lookup take as it is, then the bias. The shipped kernels keep MoePlanArgs.
+struct MoeBiasArgs : MoePlanArgs {
+    const float* bias;  // [n_expert] rows of N floats, bias_stride floats apart; null: no addition (the BIAS = false kernels)
+    long bias_stride;
+};
+
+// C[s][n] += bias[ids[s]][n] for every slot with a valid id, one launch (qg_moe_prefill.hip): the bias of the Q4_K / Q6_K
+// products in the two biased entries, whose product kernels are the unbiased entries'.
+hipError_t launch_moe_bias_add(const MoeBiasArgs& a, hipStream_t st);
+
 // The plan alone for tiles of 1 << rsh rows (rsh = 1 .. 6), one launch; the workspace's tile region holds
 // moe_max_tiles at that size.
 hipError_t launch_moe_plan_rows(const MoePlanArgs& a, int rsh, hipStream_t st);

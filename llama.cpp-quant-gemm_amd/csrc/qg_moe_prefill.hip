@@ -1,5 +1,6 @@
 // qg_moe_prefill.hip — the expert-grouped MFMA prefill (qg_gemm_w4a8_moe_prefill, ggml's mul_mat_id at prompt
-// sizes), families "moe:q4k_mmq" and "moe:q6k_mmq". DESIGN.md 3d.
+// sizes), families "moe:q4k_mmq" and "moe:q6k_mmq". DESIGN.md 3d. And its biased twin qg_gemm_w4a8_moe_prefill_bias with
+// MXFP4 experts beside them, family "moe:mxfp4_mmq" (DESIGN.md 3j): kernels of its own further down, these untouched.
 //
 // Two launches on the caller's stream, no allocation, no synchronisation, the host never reads ids:
 //  1. moe_plan_kernel (qg_moe_plan.hip) with tiles of R = 16 TT rows: the T * n_used slots counting-sorted by expert id
@@ -212,6 +213,104 @@ template <int TT, int RG> __global__ __launch_bounds__(MMQ_WGS) void q6k_moe_mmq
     moe_reduce_store<TT, RG>(a, mt, smem, acc, ks, rg, r16, q, tile);
 }
 
+// ---- the biased entry (qg_gemm_w4a8_moe_prefill_bias): kernels beside the two above, which stay --------
+// The last loop of moe_reduce_store with the bias: part holds [slice][row group][token][row]; each output is the sum of
+// its KS partials in slice order, then one rounded addition of the expert's bias (BIAS = false: no load, no test).
+template <int TT, int RG, bool BIAS>
+__device__ __forceinline__ void moe_sum_bias_store(const MoeBiasArgs& a, const MoeTile& tl, const float* part, int tile) {
+    constexpr int KS = MMQ_WAVES / RG, PT = TT * 256;
+    const float* bias = BIAS ? a.bias + (long)tl.e * a.bias_stride : nullptr;
+    for (int idx = threadIdx.x; idx < RG * PT; idx += MMQ_WGS) {
+        float sum = part[idx];
+#pragma unroll
+        for (int k = 1; k < KS; ++k) sum += part[k * (RG * PT) + idx];
+        const int g = idx / PT, o = idx - g * PT;
+        const int p = o >> 4, n = tile * (16 * RG) + 16 * g + (o & 15);
+        if (p < tl.rows && n < a.N) {
+            if constexpr (BIAS) sum = sum + bias[n];
+            a.C[(long)tl.sorted[p] * a.ldc + n] = sum;
+        }
+    }
+}
+
+// Q4_K / Q6_K with a bias: the two kernels above as they are, then this one on the finished product (ggml's add_id):
+// slot s = blockIdx.y adds its expert's bias row; a slot whose id names no expert keeps its +0.0f, no bias is read.
+// A launch of its own and not a BIAS form of those kernels: their bodies stay included once per file, their code
+// objects the shipped ones. qg_gemm_w4a8_moe_batch_bias runs it too (launch_moe_bias_add).
+__global__ __launch_bounds__(256) void moe_bias_add_kernel(const MoeBiasArgs a) {
+    const int s = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
+    const int t = s / a.n_used, u = s - t * a.n_used;
+    const int e = a.ids[(long)t * a.ids_stride + u];
+    if ((unsigned)e >= (unsigned)a.n_expert || n >= a.N) return;
+    float* c = a.C + (long)s * a.ldc + n;
+    *c = *c + a.bias[(long)e * a.bias_stride + n];
+}
+
+// MXFP4: mxfp4_mmq_kernel (qg_mxfp4_mmq.hip) on a tile of gathered rows, "moe:mxfp4_mmq". What differs from the two
+// K-quant kernels above:
+//   * a row is K / 32 blocks in groups of 8, the last group of 1 .. 8: the gathered loads clamp the dword index to the
+//     row's last dword as mxfp4_mmq_kernel's do (moe_load_tile has no clamp: K-quant rows are whole super-blocks), so
+//     nothing is read past a gathered row's end; the weight side is the body's own clamp.
+//   * the body leaves lane (r16, q) with weight row r16 x tokens 4q .. 4q + 3, the transpose of the K-quant bodies: the
+//     partials go to part[..][token 16t + 4q + e][row r16], after which the layout is the one moe_sum_bias_store reads.
+//   * the expert's matrix starts at any byte: B + e * estride in 64 bits, the body realigns per block.
+template <int TT, int RG, bool BIAS> __global__ __launch_bounds__(MMQ_WGS) void mxfp4_moe_mmq_kernel(const MoeBiasArgs a) {
+    static_assert(RG == 1 || RG == 4, "row groups per workgroup");
+    static_assert(MXFP4_TOK_DW == TOK_DW, "one activation staging layout");
+    constexpr int W = MMQ_WAVES, KS = W / RG;
+    constexpr int NBUF = RG > 1 ? 2 : 1;
+    constexpr int NR = 16 / RG;
+    constexpr int NT = RG == 1 ? 2 : 1;
+    constexpr int STAGE_DW = KS * NBUF * MXFP4_TILE_DW, PART_DW = W * TT * 256, PT = TT * 256;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[STAGE_DW > PART_DW ? STAGE_DW : PART_DW];
+    MoeTile mt;
+    if (!moe_tile_lookup(a, mt)) return;
+    const int N = a.N, nb = a.K / QK, ngrp = (nb + 7) / 8;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int rg = wave % RG, ks = wave / RG;
+    const int r16 = lane & 15, q = lane >> 4;
+    const int tile = xcd_tile_x();
+    if (mt.e >= a.n_expert) {
+        moe_zero_tile<TT, RG>(a, mt, tile);
+        return;
+    }
+    const int n0 = tile * (16 * RG) + 16 * rg;
+    const int arow = nb * 9;  // dwords per activation row
+    const uint32_t* A = static_cast<const uint32_t*>(a.A);
+    const uint8_t* B = static_cast<const uint8_t*>(a.B) + (long)mt.e * a.estride;
+    // rows past the end are clamped to the last one: loaded and multiplied, never stored
+    const uint8_t* wq = B + (long)min(n0 + r16, N - 1) * ((long)nb * MXFP4_BYTES);  // the row of MFMA lane (r16, q)
+    uint32_t* stage = smem + ks * (NBUF * MXFP4_TILE_DW);
+    MoeRows<TT, RG> rows;
+    rows.load(mt, lane, rg);
+    // moe_load_tile by groups of 8 blocks, the dword index clamped to the row's last dword (a partial last group)
+    auto load_tile = [&](uint32_t (&dst)[NR + NT], int g, int t) {
+        const int c0 = g * MXFP4_TOK_DW;
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            dst[r] = A[(long)__builtin_amdgcn_readlane(rows.rowv[t], NR * rg + r) * arow + min(c0 + lane, arow - 1)];
+        if (RG == 1 || rg < 2) {
+#pragma unroll
+            for (int b = 0; b < NT; ++b) dst[NR + b] = A[(long)rows.tailv[t][b] * arow + min(c0 + 64 + (lane & 7), arow - 1)];
+        }
+    };
+    auto store_tile = [&](const uint32_t (&src)[NR + NT], uint32_t* buf) { moe_store_tile<RG>(src, buf, lane, rg); };
+    constexpr bool SUMI = false;
+    constexpr int m0 = 0, M = 0;
+    constexpr void* out = nullptr;
+#include "qg_mxfp4_mmq_body.inc"
+    // partial tiles as [slice][row group][token][row] (over the staging buffers, once every wave has read its last
+    // tile): lane (r, q) writes row r of tokens 4q .. 4q + 3
+    __syncthreads();
+    float* part = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[(ks * RG + rg) * PT + (16 * t + 4 * q + e) * 16 + r16] = acc[t][e];
+    __syncthreads();
+    moe_sum_bias_store<TT, RG, BIAS>(a, mt, part, tile);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 // (TT, RG) from (T, n_used, n_expert, N, K, the type, CU count) alone: the shipped prefill's rule (kq_mmq_launch_t)
 // with the expected rows per expert, slots / n_expert, in the place of M for the tile's rows, and all the slots in
@@ -260,6 +359,41 @@ template <int WT> hipError_t moe_prefill_t(const Launch& L) {
     return moe_prefill_k<WT, 1, 1>(L);
 }
 
+// The biased entry. Q4_K / Q6_K: the launch of the entry beside it, kernels and all, then moe_bias_add_kernel where there
+// is a bias. MXFP4 takes the
+// general rule of moe_prefill_form (the Q6_K exception is keyed on the type); its thresholds are borrowed from the
+// K-quants, DESIGN.md 3j says what has been measured of them.
+using BiasLaunch = MoeLaunch<MoeBiasArgs>;
+
+template <int WT, int TT, int RG> hipError_t moe_prefill_bias_k(const BiasLaunch& L) {
+    const MoeBiasArgs& a = L.a;
+    if constexpr (WT != QG_TYPE_MXFP4) {
+        const hipError_t e = moe_prefill_k<WT, TT, RG>(Launch{a, L.st, L.describe, L.describe_len});
+        return e != hipSuccess || L.describe || !a.bias ? e : launch_moe_bias_add(a, L.st);
+    }
+    const int gx = (a.N + 16 * RG - 1) / (16 * RG), gy = (int)moe_max_tiles(a.slots, a.n_expert, 16 * TT);
+    if (L.describe) {
+        describe_line(L.describe, L.describe_len, "moe:mxfp4_mmq TT=%d RG=%d KS=%d R=%d grid=%dx%d", TT, RG, MMQ_WAVES / RG,
+                      16 * TT, gx, gy);
+        return hipSuccess;
+    }
+    const hipError_t e = launch_moe_plan(a, TT, L.st);
+    if (e != hipSuccess) return e;
+    if (a.bias)
+        hipLaunchKernelGGL((mxfp4_moe_mmq_kernel<TT, RG, true>), dim3(gx, gy), dim3(MMQ_WGS), 0, L.st, a);
+    else
+        hipLaunchKernelGGL((mxfp4_moe_mmq_kernel<TT, RG, false>), dim3(gx, gy), dim3(MMQ_WGS), 0, L.st, a);
+    return hipGetLastError();
+}
+
+template <int WT> hipError_t moe_prefill_bias_t(const BiasLaunch& L) {
+    const MoeForm f = moe_prefill_form(L.a, WT);
+    if (f.rg == 4) return moe_prefill_bias_k<WT, 4, 4>(L);
+    if (f.tt == 4) return moe_prefill_bias_k<WT, 4, 1>(L);
+    if (f.tt == 2) return moe_prefill_bias_k<WT, 2, 1>(L);
+    return moe_prefill_bias_k<WT, 1, 1>(L);
+}
+
 }  // namespace
 
 int moe_prefill_tt(const MoePlanArgs& a, int wtype) { return moe_prefill_form(a, wtype).tt; }
@@ -272,6 +406,19 @@ hipError_t launch_moe_prefill(const MoePlanArgs& a, int wtype, hipStream_t st, c
     const Launch L{a, st, describe, describe_len};
     if (wtype == QG_TYPE_Q4_K) return moe_prefill_t<QG_TYPE_Q4_K>(L);
     if (wtype == QG_TYPE_Q6_K) return moe_prefill_t<QG_TYPE_Q6_K>(L);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_moe_bias_add(const MoeBiasArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(moe_bias_add_kernel, dim3((a.N + 255) / 256, a.slots), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_prefill_bias(const MoeBiasArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    const BiasLaunch L{a, st, describe, describe_len};
+    if (wtype == QG_TYPE_Q4_K) return moe_prefill_bias_t<QG_TYPE_Q4_K>(L);
+    if (wtype == QG_TYPE_Q6_K) return moe_prefill_bias_t<QG_TYPE_Q6_K>(L);
+    if (wtype == QG_TYPE_MXFP4) return moe_prefill_bias_t<QG_TYPE_MXFP4>(L);
     return hipErrorInvalidValue;
 }
 

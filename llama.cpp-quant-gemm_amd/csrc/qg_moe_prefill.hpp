@@ -13,6 +13,10 @@ hipError_t launch_moe_plan(const MoePlanArgs& a, int tt, hipStream_t st);
 // The caller has checked the type (Q4_K / Q6_K), the bounds of the plan and the workspace.
 hipError_t launch_moe_prefill(const MoePlanArgs& a, int wtype, hipStream_t st, char* describe = nullptr,
                               size_t describe_len = 0);
+// qg_gemm_w4a8_moe_prefill_bias: the same two launches with the per-expert bias added to the finished product, for Q4_K /
+// Q6_K / MXFP4 (family "moe:mxfp4_mmq"). Q4_K / Q6_K with a null bias: launch_moe_prefill's launch itself.
+hipError_t launch_moe_prefill_bias(const MoeBiasArgs& a, int wtype, hipStream_t st, char* describe = nullptr,
+                                   size_t describe_len = 0);
 // tt of the form launch_moe_prefill picks for this shape (qg_debug_moe_prefill_plan runs the plan it would run)
 int moe_prefill_tt(const MoePlanArgs& a, int wtype);
 

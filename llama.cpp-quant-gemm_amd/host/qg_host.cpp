@@ -556,6 +556,33 @@ int qg_gemm_w4a8_moe_down_bias_cpu(const void* A, const void* B, const float* bi
     return QG_OK;
 }
 
+int qg_gemm_w4a8_moe_bias_cpu(const void* A, int a_rows, const void* B, const float* bias, int64_t bias_stride, int n_expert,
+                              const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
+                              int wtype, int threads) {
+    int be;
+    const int bb = bias_block(wtype, be);
+    // the order of qg_gemm_w4a8_moe_prefill_bias / _moe_batch_bias (no workspace here)
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
+    if (bias_stride < 0 || (bias_stride > 0 && bias_stride < N)) return QG_ERR_INVALID_ARG;
+    // the product of qg_gemm_w4a8_moe_cpu (the remaining checks are its own), then one rounded fp32 addition (-ffp-contract=off)
+    const int rc = qg_gemm_w4a8_moe_cpu(A, a_rows, B, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, threads);
+    if (rc != QG_OK || !bias) return rc;
+    if (ldc == 0) ldc = N;
+    if (bias_stride == 0) bias_stride = N;
+    for (int t = 0; t < T; ++t)
+        for (int u = 0; u < n_used; ++u) {
+            const int e = ids[(int64_t)t * ids_stride + u];
+            if (e < 0 || e >= n_expert) continue;  // +0.0f stays: no bias is read
+            float* c = C + ((int64_t)t * n_used + u) * ldc;
+            for (int n = 0; n < N; ++n) c[n] = c[n] + bias[(int64_t)e * bias_stride + n];
+        }
+    return QG_OK;
+}
+
 int qg_dequantize_row_mxfp4_cpu(const void* x, float* y, int64_t k) {
     if (k < 0 || k % QK != 0) return QG_ERR_BAD_K;
     if (k == 0) return QG_OK;

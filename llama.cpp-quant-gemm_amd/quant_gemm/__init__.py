@@ -549,6 +549,56 @@ def moe_down_bias_config(T: int, n_used: int, N: int, K: int, wtype: int = MXFP4
     return _config("qg_moe_down_bias_config", T, n_used, N, K, wtype)
 
 
+def _moe_grouped_bias(sym: str, size_fn, activation_q, experts_q, bias, ids, T, n_used, N, K, wtype, a_rows, workspace, out):
+    """The call of the two expert-grouped _bias entries, which take the same arguments."""
+    _require(wtype in (Q4_K, Q6_K, MXFP4), f"unsupported weight type {wtype}: the entry takes Q4_K, Q6_K and MXFP4")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, experts_q, ids, T, n_used, N, K, wtype, a_rows, out)
+    b, b_stride = _moe_bias(bias, n_expert, N, w.device, "bias")
+    workspace = _moe_workspace(workspace, size_fn(T, n_used, n_expert), w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(getattr(_lib.load(), sym)(_ptr(a), a_rows, _ptr(w), None if b is None else _ptr(b), b_stride, n_expert,
+                                             _ptr(ids), ids_stride, _ptr(out), ldc, T, n_used, N, K, wtype, _ptr(workspace),
+                                             workspace.numel(), _stream(w.device)), sym[3:])
+    return out
+
+
+def gemm_w4a8_moe_prefill_bias(activation_q: torch.Tensor, experts_q: torch.Tensor, bias: torch.Tensor | None,
+                               ids: torch.Tensor, T: int, n_used: int, N: int, K: int, wtype: int = MXFP4, a_rows: int = 1,
+                               workspace: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_prefill`` with a per-expert bias (ggml's add_id) added to the finished product, for Q4_K / Q6_K /
+    MXFP4 experts (qg_gemm_w4a8_moe_prefill_bias): C[t, u, :] = experts_q[e] . activation_q[t, u % a_rows] + bias[e],
+    e = ids[t, u].
+
+    ``experts_q``: [n_expert, N, K/32, 17] for MXFP4 (at any byte address), as ``gemm_w4a8_moe_prefill`` otherwise.
+    ``bias``: float32 [n_expert, N] CUDA tensor (``stride(1) == 1``; a view with a row stride is fine), or None: no add.
+    A slot whose id is outside [0, n_expert) gets zeros, no bias applied. ``workspace``: as ``gemm_w4a8_moe_prefill``
+    (``moe_prefill_workspace_size``)."""
+    return _moe_grouped_bias("qg_gemm_w4a8_moe_prefill_bias", moe_prefill_workspace_size, activation_q, experts_q, bias, ids,
+                             T, n_used, N, K, wtype, a_rows, workspace, out)
+
+
+def moe_prefill_bias_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = MXFP4) -> str:
+    """The launch ``gemm_w4a8_moe_prefill_bias`` makes for this shape ("moe:mxfp4_mmq TT=.. RG=.. KS=.. R=.. grid=XxY",
+    ``moe_prefill_config``'s string for Q4_K / Q6_K); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_prefill_bias_config", T, n_used, n_expert, N, K, wtype)
+
+
+def gemm_w4a8_moe_batch_bias(activation_q: torch.Tensor, experts_q: torch.Tensor, bias: torch.Tensor | None,
+                             ids: torch.Tensor, T: int, n_used: int, N: int, K: int, wtype: int = MXFP4, a_rows: int = 1,
+                             workspace: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_batch`` with a per-expert bias (ggml's add_id) added to the finished product, for Q4_K / Q6_K /
+    MXFP4 experts (qg_gemm_w4a8_moe_batch_bias). Operands as ``gemm_w4a8_moe_prefill_bias``; ``workspace``: as
+    ``gemm_w4a8_moe_batch`` (``moe_batch_workspace_size``). Every product is bit-identical to ``gemm_w4a8_moe``."""
+    return _moe_grouped_bias("qg_gemm_w4a8_moe_batch_bias", moe_batch_workspace_size, activation_q, experts_q, bias, ids,
+                             T, n_used, N, K, wtype, a_rows, workspace, out)
+
+
+def moe_batch_bias_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = MXFP4) -> str:
+    """The launch ``gemm_w4a8_moe_batch_bias`` makes for this shape ("moeb:mxfp4_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY
+    lds=..", ``moe_batch_config``'s string for Q4_K / Q6_K); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_batch_bias_config", T, n_used, n_expert, N, K, wtype)
+
+
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
     """Load-time layout for K/32 not a multiple of 8 (qg_repack_weights): [N, K'/32, bb] uint8,
     the real blocks then zero blocks (K'/32 = round_up(K/32, 8)). Feed it to gemm_w4a8_prepacked."""
@@ -948,4 +998,5 @@ __all__ = [
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
     "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
     "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
+    "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",
 ]

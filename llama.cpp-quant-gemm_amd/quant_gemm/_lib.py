@@ -49,6 +49,10 @@ SIGNATURES = {
     "qg_moe_glu_bias_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_down_bias": ([P, P, P, I64, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
     "qg_moe_down_bias_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_prefill_bias": ([P, I, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, P, SZ, P], I),
+    "qg_moe_prefill_bias_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_batch_bias": ([P, I, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, P, SZ, P], I),
+    "qg_moe_batch_bias_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_workspace_size": ([I, I, I, I], SZ),
     "qg_gemm_w4a8_ws": ([P, P, P, I, I, I, I, P, SZ, P], I),
     "qg_repack_weights_bytes": ([I, I, I], SZ),
@@ -107,6 +111,8 @@ SIGNATURES = {
     "qg_mul_mat_id_down_from_view": ([P, P, P, P, P, P], I),
     "qg_mul_mat_id_glu_bias_from_view": ([P, P, P, P, P, P, P, I, F, F, P], I),
     "qg_mul_mat_id_down_bias_from_view": ([P, P, P, P, P, P, P], I),
+    "qg_mul_mat_id_bias_from_view_ws": ([P, P, P, P, P, P, SZ, P], I),
+    "qg_mul_mat_id_bias_from_view_batch": ([P, P, P, P, P, P, SZ, P], I),
     "qg_validate_view_types": ([P, P, P, I, I, I], I),
     "qg_gemm_fp32": ([P, P, P, I, I, I, P], I),
     "qg_gguf_open": ([ctypes.c_char_p, ctypes.POINTER(P)], I),

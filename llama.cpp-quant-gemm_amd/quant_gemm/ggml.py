@@ -147,6 +147,29 @@ def mul_mat_id_down_bias_from_ggml(experts: TensorView, bias: TensorView | None,
                "qg_mul_mat_id_down_bias_from_view")
 
 
+def _mul_mat_id_bias(sym: str, experts, bias, act, ids, out, workspace: torch.Tensor) -> None:
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(getattr(_lib.load(), sym)(ctypes.byref(experts), None if bias is None else ctypes.byref(bias),
+                                         ctypes.byref(act), ctypes.byref(ids), ctypes.byref(out),
+                                         ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), st), sym)
+
+
+def mul_mat_id_bias_from_ggml_ws(experts: TensorView, bias: TensorView | None, act: TensorView, ids: TensorView,
+                                 out: TensorView, workspace: torch.Tensor) -> None:
+    """``mul_mat_id_from_ggml_ws`` with ggml's add_id folded in, for Q4_K / Q6_K / MXFP4 experts
+    (qg_mul_mat_id_bias_from_view_ws). ``bias``: F32 [N, n_expert] with nb[0] = 4, or None: no add."""
+    _mul_mat_id_bias("qg_mul_mat_id_bias_from_view_ws", experts, bias, act, ids, out, workspace)
+
+
+def mul_mat_id_bias_from_ggml_batch(experts: TensorView, bias: TensorView | None, act: TensorView, ids: TensorView,
+                                    out: TensorView, workspace: torch.Tensor) -> None:
+    """``mul_mat_id_from_ggml_batch`` with ggml's add_id folded in, for Q4_K / Q6_K / MXFP4 experts
+    (qg_mul_mat_id_bias_from_view_batch). ``bias``: F32 [N, n_expert] with nb[0] = 4, or None: no add."""
+    _mul_mat_id_bias("qg_mul_mat_id_bias_from_view_batch", experts, bias, act, ids, out, workspace)
+
+
 def validate_tensor_types(act: TensorView, w: TensorView, out: TensorView, ea: int, ew: int, eo: int) -> bool:
     """include/llama_adapter.h:110-117."""
     return bool(_lib.load().qg_validate_view_types(ctypes.byref(act), ctypes.byref(w), ctypes.byref(out), ea, ew, eo))

@@ -20,6 +20,7 @@ SIGNATURES = {
     "qg_gemm_w8a8_cpu": ([P, P, P, I, I, I], I),
     "qg_gemm_w4a8_cpu_mt": ([P, P, P, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_bias_cpu": ([P, I, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_cpu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_down_cpu": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_bias_cpu": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, I], I),
@@ -166,6 +167,23 @@ def _bias(b: np.ndarray | None, n_expert: int, n: int, what: str):
     if b.ndim != 2 or b.shape[0] != n_expert or b.shape[1] < n:
         raise RuntimeError(f"{what}: a bias must be [n_expert, >= n]")
     return b, b.shape[1]
+
+
+def gemm_w4a8_moe_bias(a_q: np.ndarray, experts_q: np.ndarray, bias: np.ndarray | None, ids: np.ndarray, t: int,
+                       n_used: int, n: int, k: int, wtype: int = 39, a_rows: int = 1, threads: int = 1,
+                       ids_stride: int | None = None) -> np.ndarray:
+    """C[t, n_used, n] of qg_gemm_w4a8_moe_bias_cpu: ``gemm_w4a8_moe`` for Q4_K / Q6_K / MXFP4 experts, then the expert's
+    bias row (float32 [n_expert, >= n], or None: no add) added to every slot with a valid id."""
+    a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    n_expert = experts_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    b, sb = _bias(bias, n_expert, n, "gemm_w4a8_moe_bias_cpu")
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    c = np.empty((t, n_used, n), np.float32)
+    _ok(load().qg_gemm_w4a8_moe_bias_cpu(_p(a_q), a_rows, _p(experts_q), None if b is None else _p(b), sb, n_expert, _p(ids),
+                                         ids_stride, _p(c), n, t, n_used, n, k, wtype, threads), "gemm_w4a8_moe_bias_cpu")
+    return c
 
 
 def gemm_w4a8_moe_glu_bias(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, bias_gate: np.ndarray | None,
