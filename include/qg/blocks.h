@@ -100,7 +100,21 @@ typedef struct {
     uint8_t qs[16];
 } qg_block_mxfp4;
 
+/* ggml's block_iq4_xs (type 23): a super-block of 256 elements = 8 sub-blocks of 32 with 6-bit scales and 4-bit codes
+ * into the non-linear IQ4_NL table, no min term. Sub-block j owns qs[16j .. 16j + 15] in the Q4_0 nibble order:
+ *   element 32j + i (i = 0..15) has the code qs[16j + i] & 15, element 32j + 16 + i the code qs[16j + i] >> 4
+ *   ls_j = ((scales_l[j / 2] >> 4 (j % 2)) & 15) | (((scales_h >> 2j) & 3) << 4)
+ *   value = d * (ls_j - 32) * kv[code],  kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}
+ * 136 bytes = 8 * 17: consecutive super-blocks alternate between 0 and 8 bytes off a 16-B boundary. */
+typedef struct {
+    uint16_t d;          /* fp16 scale of the sub-block scales */
+    uint16_t scales_h;   /* the high 2 bits of the eight 6-bit scales */
+    uint8_t scales_l[4]; /* their low 4 bits, two per byte */
+    uint8_t qs[128];
+} qg_block_iq4_xs;
+
 #ifdef __cplusplus
+static_assert(sizeof(qg_block_iq4_xs) == 136, "block_iq4_xs must be 136 bytes");
 static_assert(sizeof(qg_block_mxfp4) == 17 && alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");
@@ -111,6 +125,7 @@ static_assert(sizeof(qg_block_q5_1) == 24, "block_q5_1 must be 24 bytes");
 static_assert(sizeof(qg_block_q8_0) == 34, "block_q8_0 must be 34 bytes");
 static_assert(sizeof(qg_block_q8_1) == 36, "block_q8_1 must be 36 bytes");
 #else
+_Static_assert(sizeof(qg_block_iq4_xs) == 136, "block_iq4_xs must be 136 bytes");
 _Static_assert(sizeof(qg_block_mxfp4) == 17 && _Alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 _Static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
 _Static_assert(sizeof(qg_block_q6_K) == 210, "block_q6_K must be 210 bytes");

@@ -41,6 +41,7 @@ typedef enum {
     QG_TYPE_Q8_1 = 9,
     QG_TYPE_Q4_K = 12, /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
     QG_TYPE_Q6_K = 14, /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
+    QG_TYPE_IQ4_XS = 23, /* 256-element super-blocks of 136 B, 4-bit codes into a table (qg/blocks.h); see "IQ4_XS weights" below */
     QG_TYPE_I32 = 26,  /* int32 elements: the ids view of qg_mul_mat_id_from_view, nothing else */
     QG_TYPE_MXFP4 = 39 /* 32-element blocks of 17 B, E8M0 scale and E2M1 codes (qg/blocks.h); see "MXFP4 weights" below */
 } qg_type;
@@ -132,6 +133,34 @@ int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, 
  * parities); QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace ->
  * QG_ERR_UNSUPPORTED. Every other entry that takes a wtype returns QG_ERR_UNSUPPORTED for it, as for Q4_K,
  * and qg_tile_weights_bytes / qg_repack_weights_bytes return 0. */
+
+/* ---- IQ4_XS weights (wtype == QG_TYPE_IQ4_XS) ------------------------------------------------
+ * B: block_iq4_xs[N][K/256], ggml's bytes (qg/blocks.h), rows dense: 136 bytes per 256 elements. A 4-bit code indexes
+ *   kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}          (the IQ4_NL table)
+ * and sub-block j (32 elements, the Q4_0 nibble order inside its 16 qs bytes) has the 6-bit scale ls_j (0..63) split
+ * over scales_l and scales_h. Sub-block j of super-block sb meets Q8_1 activation block 8 sb + j:
+ *   sumi(m, n, 8 sb + j) = sum_i kv[code_i] * a_i                (int32, exact)
+ *   C(m, n) = sum_sb d * sum_j d_a(8 sb + j) * float((ls_j - 32) * sumi)
+ * |(ls - 32) * sumi| <= 32 * 32 * 127 * 128 = 16646144 < 2^24: the product is formed in int32 and its conversion is
+ * exact. There is no min term: the Q8_1 block's stored sum s_a is not used. The order of the fp32 operations is the
+ * kernel's; each output is within 2 * (K/32 + W + 2) * 2^-24 * sum(|d d_a (ls - 32) sumi|) of the exact value, W = 0
+ * for the decode GEMV and the host twin and W = 8 for the MFMA prefill (IQ4XS_MMQ_W in csrc/qg_iq4xs.hpp, derived
+ * there), and two launches give identical bits. qg_dequantize gives (d * float(ls - 32)) * float(kv[code]), each
+ * product rounded to fp32.
+ * Taken by: qg_gemm_w4a8, qg_gemm_w4a8_ex, qg_gemm_w4a8_ldc, qg_debug_sumi (sumi[M][N][K/32], before the scale, from
+ * the product's own instantiation), qg_debug_config, qg_select_algo, qg_dequantize, qg_gemm_w4a8_from_view (weights
+ * view: nb[0] = 136, ne[0] = K, dense rows), qg_gemm_w4a8_f32 with a workspace, and qg_gemm_w4a8_moe /
+ * qg_mul_mat_id_from_view (family "moe:iq4xs_gemv"; the expert stride N * K/256 * 136 is a multiple of 8).
+ * QG_ALGO_AUTO: the decode GEMV ("iq4xs_gemv") for M <= 8, the MFMA prefill ("iq4xs_mmq") from M = 9 on; both may be
+ * forced (the GEMV only for M <= 8 and while its LDS records, 304 B per token and super-block, fit 160 KiB). A
+ * captured IQ4_XS GEMV is a plain kernel node: the capture-time merge never considers it.
+ * Validation: K not a positive multiple of 256 -> QG_ERR_BAD_K; A not 4-B aligned or B not 8-B aligned ->
+ * QG_ERR_ALIGN (136 = 8 * 17: every row, expert matrix and row-offset view inside a 32-B aligned GGUF tensor starts
+ * on 8 B; super-blocks alternate between 0 and 8 mod 16, and the kernels rely on 8 B alone); QG_ALGO_RAGGED /
+ * QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace -> QG_ERR_UNSUPPORTED. Every other
+ * entry that takes a wtype (tiled, repacked, prepacked, padded, grouped, strided-batched, _ws, qg_quantize,
+ * qg_gemm_w4a8_moe_prefill, _batch, _glu, _down and the four _bias forms) returns QG_ERR_UNSUPPORTED for it and
+ * launches nothing. There is no IQ4_XS quantizer. */
 
 /* ---- MXFP4 weights (wtype == QG_TYPE_MXFP4) -------------------------------------------------
  * B: block_mxfp4[N][K/32], ggml's bytes (qg/blocks.h), rows dense: 17 bytes per 32 elements, one E8M0 scale byte e
@@ -374,7 +403,7 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  *   e = ids[t * ids_stride + u]
  *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k]      (n < N)
  * B_experts: n_expert dense matrices [N][K/bs] of `wtype`, one after another (ggml's [K, N, n_expert]); any of
- *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K (bs = 256), MXFP4 (bs = 32, 17-byte blocks: experts at any byte).
+ *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K, IQ4_XS (bs = 256), MXFP4 (bs = 32, 17-byte blocks: experts at any byte).
  * A: block_q8_1 [T][a_rows][K/32], a_rows == 1 (gate / up: one row per token, shared by its slots) or
  *    a_rows == n_used (down: one row per slot).
  * ids: int32 in DEVICE memory, read by the kernel; ids_stride >= n_used elements between tokens (ggml's top-k
@@ -390,14 +419,14 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  * C_row, 1, N, K, wtype, stream) called eagerly, so each inherits that product's documented bound; two launches
  * give identical bits.
  * Served shapes: those where QG_ALGO_AUTO at M = 1 picks the decode GEMV of the type ("gemv", "q4k_gemv",
- * "q6k_gemv", "mxfp4_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32 (the five 32-element types;
+ * "q6k_gemv", "iq4xs_gemv", "mxfp4_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32 (the five 32-element types;
  * MXFP4 takes any K/32); LDS records of the activation
- * row beyond 160 KiB (Q4_K: K > 124672, Q6_K: K > 137728, MXFP4: K > 109216, the 32-element types: K > 93568); an expert stride
+ * row beyond 160 KiB (Q4_K: K > 124672, Q6_K and IQ4_XS: K > 137728, MXFP4: K > 109216, the 32-element types: K > 93568); an expert stride
  * N * K/bs * block_bytes off the kernel's weight alignment; more than 65535 slots.
  * Validation, in the order of every entry: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive
  * multiple of bs -> QG_ERR_BAD_K; wtype -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched;
  * a null pointer -> QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A and ids 4 B; B 4 B for the 32-element types,
- * 16 B for Q4_K, 2 B for Q6_K, none for MXFP4). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
+ * 16 B for Q4_K, 2 B for Q6_K, 8 B for IQ4_XS, none for MXFP4). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
  * 0 < ldc < N -> QG_ERR_INVALID_ARG (after the precheck: an empty call is a no-op whatever they are), then the
  * unsupported shapes above.
  * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
@@ -922,8 +951,8 @@ void qg_set_capture_fusion(int on);
 void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
-int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 17 for MXFP4, 0 if unknown */
-int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K / Q6_K, 0 if unknown */
+int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 136 for IQ4_XS, 17 for MXFP4, 0 if unknown */
+int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K / Q6_K / IQ4_XS, 0 if unknown */
 const char* qg_version(void);
 
 #ifdef __cplusplus

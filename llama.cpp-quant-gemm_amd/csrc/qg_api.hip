@@ -11,6 +11,7 @@
 #include <initializer_list>
 
 #include "../../include/qg/qg.h"
+#include "qg_iq4xs.hpp"
 #include "qg_kernels.hpp"
 #include "qg_moe_batch.hpp"
 #include "qg_moe_down.hpp"
@@ -34,6 +35,7 @@ int block_bytes(int t) {
         case QG_TYPE_Q4_K: return 144;
         case QG_TYPE_Q6_K: return 210;
         case QG_TYPE_MXFP4: return MXFP4_BYTES;
+        case QG_TYPE_IQ4_XS: return IQ4XS_BYTES;
     }
     return 0;
 }
@@ -52,11 +54,12 @@ bool is_weight_type(int t) {
     return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
 }
 
-// The super-block types (256 elements: Q4_K, Q6_K): taken by the entries that go through run_product with
+// The super-block types (256 elements: Q4_K, Q6_K, IQ4_XS): taken by the entries that go through run_product with
 // sb_ok; every other entry tests is_weight_type alone and so keeps refusing them.
 bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
 bool is_q6k_type(int t) { return t == QG_TYPE_Q6_K; }
-bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t); }
+bool is_iq4xs_type(int t) { return t == QG_TYPE_IQ4_XS; }
+bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t) || is_iq4xs_type(t); }
 
 // MXFP4 (32 elements in 17 bytes): a route of its own beside the 32-element families and the super-block types,
 // taken by the same entries as the latter (run_product with sb_ok) and by qg_gemm_w4a8_moe; is_weight_type does not
@@ -69,8 +72,9 @@ int block_elems(int t) { return is_sb_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
 
 // Weight pointer alignment of a routed type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
 // super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load; an
-// MXFP4 block is 17 B of bytes, so there is no requirement at all.
-uintptr_t sb_weight_mask(int t) { return is_mxfp4_type(t) ? 0u : is_q6k_type(t) ? 1u : 15u; }
+// MXFP4 block is 17 B of bytes, so there is no requirement at all; an IQ4_XS super-block is 136 = 8 x 17 B and is read
+// with 8-B loads.
+uintptr_t sb_weight_mask(int t) { return is_mxfp4_type(t) ? 0u : is_q6k_type(t) ? 1u : is_iq4xs_type(t) ? 7u : 15u; }
 
 // ---- the one ordered precheck ------------------------------------------------------------------------------
 // The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
@@ -215,6 +219,10 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
 #ifndef QG_MXFP4_GEMV_MAXM
 #define QG_MXFP4_GEMV_MAXM 8
 #endif
+// IQ4_XS keeps the threshold (profiles/iq4xs/ab_iq4xs_threshold.txt, each kernel forced).
+#ifndef QG_IQ4XS_GEMV_MAXM
+#define QG_IQ4XS_GEMV_MAXM 8
+#endif
 struct SbRoute {
     bool (*gemv_eligible)(const GemmArgs&);
     hipError_t (*launch_gemv)(const GemmArgs&, hipStream_t);
@@ -222,15 +230,18 @@ struct SbRoute {
     hipError_t (*launch_mmq)(const GemmArgs&, hipStream_t);
     int maxm;
 };
-constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K
+constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K, IQ4_XS
     {q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, QG_Q4K_GEMV_MAXM},
     {q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, QG_Q6K_GEMV_MAXM},
+    {iq4xs_gemv_eligible, launch_iq4xs_gemv, iq4xs_mmq_eligible, launch_iq4xs_mmq, QG_IQ4XS_GEMV_MAXM},
 };
-// The third route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
+// The fourth route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
 constexpr SbRoute MXFP4_ROUTE = {mxfp4_gemv_eligible, launch_mxfp4_gemv, mxfp4_mmq_eligible, launch_mxfp4_mmq,
                                  QG_MXFP4_GEMV_MAXM};
 // the route of a routed type (is_routed_type holds)
-const SbRoute& sb_route(int t) { return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_q6k_type(t) ? 1 : 0]; }
+const SbRoute& sb_route(int t) {
+    return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_iq4xs_type(t) ? 2 : is_q6k_type(t) ? 1 : 0];
+}
 
 int select_algo_sb(const GemmArgs& g) {
     const SbRoute& r = sb_route(g.wtype);
@@ -458,8 +469,10 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
 int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries: elsewhere it is refused as the 32-element types are)
-    const bool ksb = is_sb_type(c.wtype) || ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
+    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries, IQ4_XS of qg_gemm_w4a8_moe alone: elsewhere they
+    // are refused as the 32-element types are)
+    const bool ksb = (is_sb_type(c.wtype) && (rows_ok || !is_iq4xs_type(c.wtype))) ||
+                     ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
                             {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
@@ -1300,9 +1313,10 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
     const int be = is_sb_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
-    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, is_mxfp4_type(type) ? 0u : 1u}, {y, 3}});
+    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, is_mxfp4_type(type) ? 0u : is_iq4xs_type(type) ? 7u : 1u}, {y, 3}});
     if (rc != QG_GO) return rc;
     if (is_mxfp4_type(type)) return hip_status(launch_dequantize_mxfp4(x, y, k / 32, (hipStream_t)stream));
+    if (is_iq4xs_type(type)) return hip_status(launch_dequantize_iq4xs(x, y, k / 256, (hipStream_t)stream));
     if (is_q6k_type(type)) return hip_status(launch_dequantize_q6k(x, y, k / 256, (hipStream_t)stream));
     if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));

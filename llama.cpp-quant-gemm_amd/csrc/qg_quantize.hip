@@ -15,6 +15,7 @@
 //     which equals the one correct rounding of the definition's Python float (tests/test_oracle.py);
 //     Q8_1 s = sum(x) in element order as variant 0 (the definition's torch.sum order is unspecified)
 #include "qg_common.hpp"
+#include "qg_iq4xs.hpp"
 #include "qg_kernels.hpp"
 #include "qg_q4k.hpp"
 #include "qg_mxfp4.hpp"
@@ -540,6 +541,43 @@ hipError_t launch_dequantize_q6k(const void* x, float* y, int64_t nsb, hipStream
     const int64_t ngrp = nsb * 16;
     hipLaunchKernelGGL(dequantize_q6k_kernel, dim3((unsigned)((ngrp + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
                        ngrp);
+    return hipGetLastError();
+}
+
+// IQ4_XS (qg_iq4xs.hpp): one thread per 32-element sub-block, y = (d * float(ls - 32)) * float(kv[code]) in exactly
+// that operation order (no contraction), so the result can be checked bit for bit. 8-B loads: the header's two dwords
+// (the scales assembled by iq4xs_unpack_scales) and the sub-block's 16 qs bytes; x is 8-B aligned as for the products.
+namespace {
+__global__ __launch_bounds__(256) void dequantize_iq4xs_kernel(const uint8_t* __restrict__ x, float* __restrict__ y,
+                                                              int64_t nsub) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nsub) return;
+    const uint2* b = reinterpret_cast<const uint2*>(x + (g >> 3) * IQ4XS_BYTES);
+    const int j = (int)(g & 7);
+    const uint2 h = b[0];
+    const iq4xs_scales s = iq4xs_unpack_scales(h.x, h.y);
+    const int ls = (int)(((j < 4 ? s.ls[0] : s.ls[1]) >> (8 * (j & 3))) & 0xFFu) - 32;
+    const float dl = h2f(h.x & 0xFFFFu) * (float)ls;
+    const uint2 q0 = b[1 + 2 * j], q1 = b[2 + 2 * j];
+    const uint32_t qs[4] = {q0.x, q0.y, q1.x, q1.y};
+    float* o = y + g * QK;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const uint32_t lo = iq4xs_kv4(qs[t]), hi = iq4xs_kv4(qs[t] >> 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            o[4 * t + i] = dl * (float)(int8_t)(lo >> (8 * i));
+            o[16 + 4 * t + i] = dl * (float)(int8_t)(hi >> (8 * i));
+        }
+    }
+}
+}  // namespace
+
+hipError_t launch_dequantize_iq4xs(const void* x, float* y, int64_t nsb, hipStream_t st) {
+    if (nsb <= 0) return hipSuccess;
+    const int64_t nsub = nsb * 8;
+    hipLaunchKernelGGL(dequantize_iq4xs_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
+                       nsub);
     return hipGetLastError();
 }
 

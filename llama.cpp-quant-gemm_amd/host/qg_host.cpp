@@ -199,6 +199,46 @@ void gemm_rows<FmtQ6_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int
         }
 }
 
+// IQ4_XS (qg/blocks.h: 136-B super-blocks; sub-block j of super-block sb meets activation block 8 sb + j). The product
+// contract of qg.h: sumi in int32, (ls_j - 32) * sumi in int32, one fp32 accumulator per super-block in sub-block
+// order, d applied once, super-blocks summed in order.
+struct FmtIQ4_XS {
+    static constexpr int bytes = 136;
+    // kv[code] of element l (0..31) of sub-block j
+    static int value(const uint8_t* w, int j, int l) {
+        static const int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+        const uint8_t q = w[8 + 16 * j + (l & 15)];
+        return kv[l < 16 ? q & 15 : q >> 4];
+    }
+    // ls_j - 32
+    static int scale(const uint8_t* w, int j) {
+        const unsigned sh = (unsigned)w[2] | ((unsigned)w[3] << 8);
+        return (int)(((w[4 + j / 2] >> (4 * (j % 2))) & 15) | (((sh >> (2 * j)) & 3) << 4)) - 32;
+    }
+};
+template <>
+void gemm_rows<FmtIQ4_XS>(const uint8_t* A, const uint8_t* B, float* C, int M, int N, int K, int j0, int j1) {
+    const int nsb = K / 256;
+    const size_t arow = (size_t)(K / QK) * 36, wrow = (size_t)nsb * FmtIQ4_XS::bytes;
+    for (int i = 0; i < M; ++i)
+        for (int n = j0; n < j1; ++n) {
+            float sum = 0.0f;
+            for (int sb = 0; sb < nsb; ++sb) {
+                const uint8_t* w = B + n * wrow + (size_t)sb * FmtIQ4_XS::bytes;
+                const float d = half_to_float(w);
+                float fd = 0.0f;
+                for (int j = 0; j < 8; ++j) {
+                    const ActBlock a(A + i * arow + (size_t)(8 * sb + j) * 36);
+                    int32_t sumi = 0;
+                    for (int l = 0; l < QK; ++l) sumi += (int32_t)a.qs[l] * FmtIQ4_XS::value(w, j, l);
+                    fd += a.d * (float)(FmtIQ4_XS::scale(w, j) * sumi);
+                }
+                sum += d * fd;
+            }
+            C[(size_t)i * N + n] = sum;
+        }
+}
+
 // Process-wide persistent worker pool: threads are started once (grown on demand) and parked on
 // a condition variable between jobs, so a multi-threaded call costs one wake-up per worker instead
 // of a thread start and join (which dominated a 1-9 ms GEMV at 256 threads). One job at a time
@@ -329,11 +369,12 @@ extern "C" {
 int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int threads) {
     const int rc = check_gemm(A, B, C, M, N, K);
     if (rc != QG_OK) return rc;
-    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K) && K % 256 != 0) return QG_ERR_BAD_K;
+    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS) && K % 256 != 0) return QG_ERR_BAD_K;
     if (M == 0 || N == 0) return QG_OK;
     switch (wtype) {
         case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q6_K: gemm_threads<FmtQ6_K>(A, B, C, M, N, K, threads); return QG_OK;
+        case QG_TYPE_IQ4_XS: gemm_threads<FmtIQ4_XS>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_MXFP4: gemm_threads<FmtMXFP4>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
@@ -346,7 +387,7 @@ int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, in
 
 int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
                          float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
-    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS;
     int bb = 0;
     switch (wtype) {
         case QG_TYPE_Q4_0: bb = FmtQ4_0::bytes; break;
@@ -356,6 +397,7 @@ int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert,
         case QG_TYPE_Q8_0: bb = FmtQ8_0::bytes; break;
         case QG_TYPE_Q4_K: bb = FmtQ4_K::bytes; break;
         case QG_TYPE_Q6_K: bb = FmtQ6_K::bytes; break;
+        case QG_TYPE_IQ4_XS: bb = FmtIQ4_XS::bytes; break;
         case QG_TYPE_MXFP4: bb = FmtMXFP4::bytes; break;
     }
     // the order of qg_gemm_w4a8_moe
