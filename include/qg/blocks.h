@@ -113,7 +113,22 @@ typedef struct {
     uint8_t qs[128];
 } qg_block_iq4_xs;
 
+/* ggml's block_q3_K (type 11): a super-block of 256 elements = 16 groups of 16 with 6-bit scales, 3-bit codes split over
+ * a 2-bit plane and a mask of high bits, no min term. Element e = 128h + 32j + l (h 0..1, j 0..3, l 0..31):
+ *   lo2 = (qs[32h + l] >> 2j) & 3,  hb = (hmask[l] >> (4h + j)) & 1,  q = lo2 - (hb ? 0 : 4)          (-4..3)
+ *   group g = 8h + 2j + l / 16:  sc_g = low4 | high2 << 4,  low4 = g < 8 ? scales[g] & 15 : scales[g - 8] >> 4,
+ *                                high2 = (scales[8 + g % 4] >> 2 (g / 4)) & 3
+ *   value = d * (sc_g - 32) * q
+ * 110 bytes: a multiple of 2, not of 4 -- consecutive super-blocks alternate between 0 and 2 bytes off a dword. */
+typedef struct {
+    uint8_t hmask[32];   /* the codes' high bit */
+    uint8_t qs[64];      /* their low 2 bits */
+    uint8_t scales[12];  /* sixteen 6-bit group scales */
+    uint16_t d;          /* fp16 scale of the group scales */
+} qg_block_q3_K;
+
 #ifdef __cplusplus
+static_assert(sizeof(qg_block_q3_K) == 110 && alignof(qg_block_q3_K) == 2, "block_q3_K must be 110 bytes, alignment 2");
 static_assert(sizeof(qg_block_iq4_xs) == 136, "block_iq4_xs must be 136 bytes");
 static_assert(sizeof(qg_block_mxfp4) == 17 && alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");
@@ -125,6 +140,7 @@ static_assert(sizeof(qg_block_q5_1) == 24, "block_q5_1 must be 24 bytes");
 static_assert(sizeof(qg_block_q8_0) == 34, "block_q8_0 must be 34 bytes");
 static_assert(sizeof(qg_block_q8_1) == 36, "block_q8_1 must be 36 bytes");
 #else
+_Static_assert(sizeof(qg_block_q3_K) == 110 && _Alignof(qg_block_q3_K) == 2, "block_q3_K must be 110 bytes, alignment 2");
 _Static_assert(sizeof(qg_block_iq4_xs) == 136, "block_iq4_xs must be 136 bytes");
 _Static_assert(sizeof(qg_block_mxfp4) == 17 && _Alignof(qg_block_mxfp4) == 1, "block_mxfp4 must be 17 bytes, alignment 1");
 _Static_assert(sizeof(qg_block_q4_K) == 144, "block_q4_K must be 144 bytes");

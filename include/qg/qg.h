@@ -39,6 +39,7 @@ typedef enum {
     QG_TYPE_Q5_1 = 7,
     QG_TYPE_Q8_0 = 8,
     QG_TYPE_Q8_1 = 9,
+    QG_TYPE_Q3_K = 11, /* 256-element super-blocks of 110 B, 3-bit codes (qg/blocks.h); see "Q3_K weights" below */
     QG_TYPE_Q4_K = 12, /* 256-element super-blocks of 144 B (qg/blocks.h); see "Q4_K weights" below */
     QG_TYPE_Q6_K = 14, /* 256-element super-blocks of 210 B (qg/blocks.h); see "Q6_K weights" below */
     QG_TYPE_IQ4_XS = 23, /* 256-element super-blocks of 136 B, 4-bit codes into a table (qg/blocks.h); see "IQ4_XS weights" below */
@@ -161,6 +162,34 @@ int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, 
  * entry that takes a wtype (tiled, repacked, prepacked, padded, grouped, strided-batched, _ws, qg_quantize,
  * qg_gemm_w4a8_moe_prefill, _batch, _glu, _down and the four _bias forms) returns QG_ERR_UNSUPPORTED for it and
  * launches nothing. There is no IQ4_XS quantizer. */
+
+/* ---- Q3_K weights (wtype == QG_TYPE_Q3_K) ----------------------------------------------------
+ * B: block_q3_K[N][K/256], ggml's bytes (qg/blocks.h), rows dense: 110 bytes per 256 elements. Codes q in [-4, 3],
+ * sixteen group scales s_g = sc_g - 32 in [-32, 31]. Q8_1 block b of super-block sb is activation block 8 sb + b and
+ * meets exactly the groups 2b (its first 16 elements) and 2b + 1:
+ *   isum(m, n, 8 sb + b) = s_2b * sum_{l < 16} q_l a_l + s_2b+1 * sum_{l >= 16} q_l a_l   (int32, |isum| <= 2^19: exact in float)
+ *   C(m, n) = sum_sb d * sum_b d_a(8 sb + b) * float(isum)
+ * There is no min term: the Q8_1 block's stored sum s_a is not used. The kernels fold the group scale into the int8
+ * operand ((-q) * s lies in [-128, 124]; csrc/qg_q3k.hpp), so isum comes out of one dot per block. The order of the
+ * fp32 operations is the kernel's; each output is within 2 * (K/32 + W + 2) * 2^-24 * sum(|d d_a isum|) of the exact
+ * value, W = 0 for the decode GEMV and the host twin and W = 7 for the MFMA prefill (Q3K_MMQ_W in csrc/qg_q3k.hpp,
+ * derived there), and two launches give identical bits. qg_dequantize gives (d * float(s_g)) * float(q), each product
+ * rounded to fp32.
+ * Taken by: qg_gemm_w4a8, qg_gemm_w4a8_ex, qg_gemm_w4a8_ldc, qg_debug_sumi (isum[M][N][K/32], from the product's own
+ * instantiation), qg_debug_config, qg_select_algo, qg_dequantize, qg_gemm_w4a8_from_view (weights view: nb[0] = 110,
+ * ne[0] = K, dense rows), qg_gemm_w4a8_f32 with a workspace, and qg_gemm_w4a8_moe / qg_mul_mat_id_from_view (family
+ * "moe:q3k_gemv"; the expert stride N * K/256 * 110 is even, which is all the kernel needs).
+ * QG_ALGO_AUTO: the decode GEMV ("q3k_gemv") for M <= 6, the MFMA prefill ("q3k_mmq") from M = 7 on (measured: the
+ * prefill, one MFMA per block, is ahead from M = 7; profiles/q3k); both may be
+ * forced (the GEMV only for M <= 8 and while its LDS records, 304 B per token and super-block, fit 160 KiB). A
+ * captured Q3_K GEMV is a plain kernel node: the capture-time merge never considers it.
+ * Validation: K not a positive multiple of 256 -> QG_ERR_BAD_K; A not 4-B aligned or B not 2-B aligned ->
+ * QG_ERR_ALIGN (110 = 2 mod 4: super-blocks, and rows with odd K/256, alternate between 0 and 2 bytes off a dword;
+ * every weight load is an aligned dword of a covering span, realigned, and no result depends on bytes outside the
+ * tensor); QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a workspace ->
+ * QG_ERR_UNSUPPORTED. Every other entry that takes a wtype (tiled, repacked, prepacked, padded, grouped,
+ * strided-batched, _ws, qg_quantize, qg_gemm_w4a8_moe_prefill, _batch, _glu, _down and the four _bias forms) returns
+ * QG_ERR_UNSUPPORTED for it and launches nothing. There is no Q3_K quantizer. */
 
 /* ---- MXFP4 weights (wtype == QG_TYPE_MXFP4) -------------------------------------------------
  * B: block_mxfp4[N][K/32], ggml's bytes (qg/blocks.h), rows dense: 17 bytes per 32 elements, one E8M0 scale byte e
@@ -403,7 +432,7 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  *   e = ids[t * ids_stride + u]
  *   C[s * ldc + n] = sum_k B_experts[e][n][k] * A[t * a_rows + (u % a_rows)][k]      (n < N)
  * B_experts: n_expert dense matrices [N][K/bs] of `wtype`, one after another (ggml's [K, N, n_expert]); any of
- *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q4_K, Q6_K, IQ4_XS (bs = 256), MXFP4 (bs = 32, 17-byte blocks: experts at any byte).
+ *    Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 (bs = 32), Q3_K, Q4_K, Q6_K, IQ4_XS (bs = 256), MXFP4 (bs = 32, 17-byte blocks: experts at any byte).
  * A: block_q8_1 [T][a_rows][K/32], a_rows == 1 (gate / up: one row per token, shared by its slots) or
  *    a_rows == n_used (down: one row per slot).
  * ids: int32 in DEVICE memory, read by the kernel; ids_stride >= n_used elements between tokens (ggml's top-k
@@ -419,14 +448,14 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
  * C_row, 1, N, K, wtype, stream) called eagerly, so each inherits that product's documented bound; two launches
  * give identical bits.
  * Served shapes: those where QG_ALGO_AUTO at M = 1 picks the decode GEMV of the type ("gemv", "q4k_gemv",
- * "q6k_gemv", "iq4xs_gemv", "mxfp4_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32 (the five 32-element types;
+ * "q6k_gemv", "iq4xs_gemv", "q3k_gemv", "mxfp4_gemv"), up to 65535 slots. QG_ERR_UNSUPPORTED, nothing launched: odd K/32 (the five 32-element types;
  * MXFP4 takes any K/32); LDS records of the activation
- * row beyond 160 KiB (Q4_K: K > 124672, Q6_K and IQ4_XS: K > 137728, MXFP4: K > 109216, the 32-element types: K > 93568); an expert stride
+ * row beyond 160 KiB (Q4_K: K > 124672, Q6_K, IQ4_XS and Q3_K: K > 137728, MXFP4: K > 109216, the 32-element types: K > 93568); an expert stride
  * N * K/bs * block_bytes off the kernel's weight alignment; more than 65535 slots.
  * Validation, in the order of every entry: a negative T, n_used or N -> QG_ERR_INVALID_ARG; K not a positive
  * multiple of bs -> QG_ERR_BAD_K; wtype -> QG_ERR_UNSUPPORTED; T, n_used or N equal to 0 -> QG_OK, nothing touched;
  * a null pointer -> QG_ERR_INVALID_ARG; alignment -> QG_ERR_ALIGN (A and ids 4 B; B 4 B for the 32-element types,
- * 16 B for Q4_K, 2 B for Q6_K, 8 B for IQ4_XS, none for MXFP4). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
+ * 16 B for Q4_K, 2 B for Q6_K and Q3_K, 8 B for IQ4_XS, none for MXFP4). Then a_rows not in {1, n_used}, ids_stride < n_used, n_expert < 1, ldc < 0 or
  * 0 < ldc < N -> QG_ERR_INVALID_ARG (after the precheck: an empty call is a no-op whatever they are), then the
  * unsupported shapes above.
  * qg_moe_config names the kernel the call would launch (family after "moe:", template parameters, grid) for
@@ -951,8 +980,8 @@ void qg_set_capture_fusion(int on);
 void qg_capture_fusion_stats(uint64_t* merged, uint64_t* nodes);
 int qg_last_hip_error(void);                    /* hipError_t of the last QG_ERR_HIP on this thread */
 int qg_select_algo(int M, int N, int K, int wtype); /* what QG_ALGO_AUTO dispatches to */
-int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 136 for IQ4_XS, 17 for MXFP4, 0 if unknown */
-int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q4_K / Q6_K / IQ4_XS, 0 if unknown */
+int qg_block_bytes(int type);                   /* 18/20/22/24/34/36, 144 for Q4_K, 210 for Q6_K, 136 for IQ4_XS, 110 for Q3_K, 17 for MXFP4, 0 if unknown */
+int qg_block_elems(int type);                   /* 32 for the block types, 256 for Q3_K / Q4_K / Q6_K / IQ4_XS, 0 if unknown */
 const char* qg_version(void);
 
 #ifdef __cplusplus

@@ -45,6 +45,8 @@ int qg_gemm_w8a8_cpu(const void* A_q8_1, const void* B_q8_0, float* C, int M, in
  * fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order.
  * And QG_TYPE_IQ4_XS (K % 256 == 0, else QG_ERR_BAD_K): the IQ4_XS product contract of qg.h, sumi and (ls - 32) * sumi
  * in int32, one fp32 accumulator per super-block in sub-block order, d applied once, super-blocks summed in order (W = 0).
+ * And QG_TYPE_Q3_K (K % 256 == 0, else QG_ERR_BAD_K): the Q3_K product contract of qg.h, isum in int32, one fp32
+ * accumulator per super-block in block order, d applied once, super-blocks summed in order (W = 0).
  * And QG_TYPE_MXFP4 (K % 32 == 0): the MXFP4 product contract of qg.h, sumi in int32, (d_a * scale(e)) * float(sumi)
  * per block, one fp32 accumulator per output, blocks in order (W = 0). Bits are
  * identical for every thread count (threads split the weight rows only). */

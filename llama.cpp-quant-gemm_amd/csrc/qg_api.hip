@@ -12,6 +12,7 @@
 
 #include "../../include/qg/qg.h"
 #include "qg_iq4xs.hpp"
+#include "qg_q3k.hpp"
 #include "qg_kernels.hpp"
 #include "qg_moe_batch.hpp"
 #include "qg_moe_down.hpp"
@@ -36,6 +37,7 @@ int block_bytes(int t) {
         case QG_TYPE_Q6_K: return 210;
         case QG_TYPE_MXFP4: return MXFP4_BYTES;
         case QG_TYPE_IQ4_XS: return IQ4XS_BYTES;
+        case QG_TYPE_Q3_K: return Q3K_BYTES;
     }
     return 0;
 }
@@ -54,12 +56,13 @@ bool is_weight_type(int t) {
     return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
 }
 
-// The super-block types (256 elements: Q4_K, Q6_K, IQ4_XS): taken by the entries that go through run_product with
+// The super-block types (256 elements: Q4_K, Q6_K, IQ4_XS, Q3_K): taken by the entries that go through run_product with
 // sb_ok; every other entry tests is_weight_type alone and so keeps refusing them.
 bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
 bool is_q6k_type(int t) { return t == QG_TYPE_Q6_K; }
 bool is_iq4xs_type(int t) { return t == QG_TYPE_IQ4_XS; }
-bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t) || is_iq4xs_type(t); }
+bool is_q3k_type(int t) { return t == QG_TYPE_Q3_K; }
+bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t) || is_iq4xs_type(t) || is_q3k_type(t); }
 
 // MXFP4 (32 elements in 17 bytes): a route of its own beside the 32-element families and the super-block types,
 // taken by the same entries as the latter (run_product with sb_ok) and by qg_gemm_w4a8_moe; is_weight_type does not
@@ -73,8 +76,10 @@ int block_elems(int t) { return is_sb_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
 // Weight pointer alignment of a routed type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
 // super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load; an
 // MXFP4 block is 17 B of bytes, so there is no requirement at all; an IQ4_XS super-block is 136 = 8 x 17 B and is read
-// with 8-B loads.
-uintptr_t sb_weight_mask(int t) { return is_mxfp4_type(t) ? 0u : is_q6k_type(t) ? 1u : is_iq4xs_type(t) ? 7u : 15u; }
+// with 8-B loads; a Q3_K super-block is 110 B, 2 mod 4 as Q6_K's, and its kernels realign every load likewise.
+uintptr_t sb_weight_mask(int t) {
+    return is_mxfp4_type(t) ? 0u : is_q6k_type(t) || is_q3k_type(t) ? 1u : is_iq4xs_type(t) ? 7u : 15u;
+}
 
 // ---- the one ordered precheck ------------------------------------------------------------------------------
 // The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
@@ -203,7 +208,7 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
     return QG_OK;
 }
 
-// The super-block products (qg_q4k.hpp, qg_q6k.hpp): the decode GEMV up to M = 8, the MFMA prefill from M = 9 on.
+// The super-block products (qg_q4k.hpp, qg_q6k.hpp): the decode GEMV up to M = 8 (Q3_K: 6), the MFMA prefill beyond.
 // Interleaved A/B of Q4_K against a build with the threshold at 4 | 5 (profiles/q4k/ab_q4k_variants.txt,
 // N = K = 4096): M = 5 GEMV 5.82 us, MFMA 7.43; M = 8 GEMV 7.31, MFMA 7.45 — the GEMV keeps M <= 8; Q6_K keeps the
 // threshold ("Q6_K", 3b). The GEMV's LDS records bound M * K (gemv_eligible); beyond that AUTO takes the
@@ -223,6 +228,12 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
 #ifndef QG_IQ4XS_GEMV_MAXM
 #define QG_IQ4XS_GEMV_MAXM 8
 #endif
+// Q3_K moves it to 6 | 7 (profiles/q3k/ab_q3k_threshold.txt, N = K = 4096, each kernel forced): M = 5 GEMV 6.06 us, MFMA
+// 6.56; M = 6 6.46 / 6.55; M = 7 7.24 / 6.58; M = 8 7.56 / 6.59, each beyond the rounds' spread: its prefill needs one MFMA
+// per block and so starts cheaper than the others' (DESIGN.md 3l). The GEMV can still be forced up to M = 8.
+#ifndef QG_Q3K_GEMV_MAXM
+#define QG_Q3K_GEMV_MAXM 6
+#endif
 struct SbRoute {
     bool (*gemv_eligible)(const GemmArgs&);
     hipError_t (*launch_gemv)(const GemmArgs&, hipStream_t);
@@ -230,17 +241,18 @@ struct SbRoute {
     hipError_t (*launch_mmq)(const GemmArgs&, hipStream_t);
     int maxm;
 };
-constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K, IQ4_XS
+constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K, IQ4_XS, Q3_K
     {q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, QG_Q4K_GEMV_MAXM},
     {q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, QG_Q6K_GEMV_MAXM},
     {iq4xs_gemv_eligible, launch_iq4xs_gemv, iq4xs_mmq_eligible, launch_iq4xs_mmq, QG_IQ4XS_GEMV_MAXM},
+    {q3k_gemv_eligible, launch_q3k_gemv, q3k_mmq_eligible, launch_q3k_mmq, QG_Q3K_GEMV_MAXM},
 };
-// The fourth route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
+// The fifth route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
 constexpr SbRoute MXFP4_ROUTE = {mxfp4_gemv_eligible, launch_mxfp4_gemv, mxfp4_mmq_eligible, launch_mxfp4_mmq,
                                  QG_MXFP4_GEMV_MAXM};
 // the route of a routed type (is_routed_type holds)
 const SbRoute& sb_route(int t) {
-    return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_iq4xs_type(t) ? 2 : is_q6k_type(t) ? 1 : 0];
+    return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_q3k_type(t) ? 3 : is_iq4xs_type(t) ? 2 : is_q6k_type(t) ? 1 : 0];
 }
 
 int select_algo_sb(const GemmArgs& g) {
@@ -469,9 +481,9 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
 int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries, IQ4_XS of qg_gemm_w4a8_moe alone: elsewhere they
+    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries, IQ4_XS and Q3_K of qg_gemm_w4a8_moe alone: elsewhere they
     // are refused as the 32-element types are)
-    const bool ksb = (is_sb_type(c.wtype) && (rows_ok || !is_iq4xs_type(c.wtype))) ||
+    const bool ksb = (is_sb_type(c.wtype) && (rows_ok || !(is_iq4xs_type(c.wtype) || is_q3k_type(c.wtype)))) ||
                      ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
@@ -1317,6 +1329,7 @@ int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stre
     if (rc != QG_GO) return rc;
     if (is_mxfp4_type(type)) return hip_status(launch_dequantize_mxfp4(x, y, k / 32, (hipStream_t)stream));
     if (is_iq4xs_type(type)) return hip_status(launch_dequantize_iq4xs(x, y, k / 256, (hipStream_t)stream));
+    if (is_q3k_type(type)) return hip_status(launch_dequantize_q3k(x, y, k / 256, (hipStream_t)stream));
     if (is_q6k_type(type)) return hip_status(launch_dequantize_q6k(x, y, k / 256, (hipStream_t)stream));
     if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));

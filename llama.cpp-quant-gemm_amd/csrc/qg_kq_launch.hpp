@@ -1,6 +1,6 @@
-// qg_kq_launch.hpp — the host side the super-block (Q4_K, Q6_K, IQ4_XS) and the MXFP4 kernels share: instantiation choice,
-// launch and eligibility of the decode GEMV (qg_q4k_gemv.hip, qg_q6k_gemv.hip, qg_iq4xs_gemv.hip, qg_mxfp4_gemv.hip) and
-// of the MFMA prefill (qg_q4k_mmq.hip, qg_q6k_mmq.hip, qg_iq4xs_mmq.hip, qg_mxfp4_mmq.hip). The kernels themselves stay one per type (DESIGN.md,
+// qg_kq_launch.hpp — the host side the super-block (Q4_K, Q6_K, IQ4_XS, Q3_K) and the MXFP4 kernels share: instantiation choice,
+// launch and eligibility of the decode GEMV (qg_q4k_gemv.hip, qg_q6k_gemv.hip, qg_iq4xs_gemv.hip, qg_q3k_gemv.hip, qg_mxfp4_gemv.hip) and
+// of the MFMA prefill (qg_q4k_mmq.hip, qg_q6k_mmq.hip, qg_iq4xs_mmq.hip, qg_q3k_mmq.hip, qg_mxfp4_mmq.hip). The kernels themselves stay one per type (DESIGN.md,
 // "Q4_K": what was tried to share them); within a type a kernel's body is one text, qg_<type>_{gemv,mmq}_body.inc,
 // which the shipped kernel and its expert-indexed / expert-grouped twins (qg_moe.hip, qg_moe_batch.hip,
 // qg_moe_prefill.hip; their plan: qg_moe_plan.hip) all include.
@@ -18,6 +18,7 @@
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
 #include "qg_iq4xs.hpp"
+#include "qg_q3k.hpp"
 #include "qg_q4k.hpp"
 #include "qg_mxfp4.hpp"
 #include "qg_q6k.hpp"
@@ -26,9 +27,11 @@ namespace qg {
 
 // A super-block type by its id: the decode GEMV's LDS record, the family ("q4k" + "_gemv" / "_mmq" in the config lines).
 constexpr int kq_gemv_rec_dw(int wtype) {
-    return wtype == QG_TYPE_Q4_K ? Q4K_REC_DW : wtype == QG_TYPE_IQ4_XS ? IQ4XS_REC_DW : Q6K_REC_DW;
+    return wtype == QG_TYPE_Q4_K ? Q4K_REC_DW : wtype == QG_TYPE_IQ4_XS ? IQ4XS_REC_DW : wtype == QG_TYPE_Q3_K ? Q3K_REC_DW : Q6K_REC_DW;
 }
-constexpr const char* kq_family(int wtype) { return wtype == QG_TYPE_Q4_K ? "q4k" : wtype == QG_TYPE_IQ4_XS ? "iq4xs" : "q6k"; }
+constexpr const char* kq_family(int wtype) {
+    return wtype == QG_TYPE_Q4_K ? "q4k" : wtype == QG_TYPE_IQ4_XS ? "iq4xs" : wtype == QG_TYPE_Q3_K ? "q3k" : "q6k";
+}
 
 // ---- decode GEMV (M <= 8) ------------------------------------------------------------------------------------
 template <class F> inline size_t kq_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / F::REC_ELEMS) * F::REC_DW * 4; }

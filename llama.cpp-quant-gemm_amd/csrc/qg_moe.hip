@@ -1,5 +1,5 @@
 // qg_moe.hip — the expert-indexed decode GEMV (qg_gemm_w4a8_moe, ggml's mul_mat_id), families "moe:gemv",
-// "moe:q4k_gemv", "moe:q6k_gemv", "moe:iq4xs_gemv", "moe:mxfp4_gemv".
+// "moe:q4k_gemv", "moe:q6k_gemv", "moe:iq4xs_gemv", "moe:q3k_gemv", "moe:mxfp4_gemv".
 //
 // One launch computes the T * n_used expert products of a decode step: blockIdx.y is the slot s = t * n_used + u,
 // blockIdx.x its row tile. The workgroup reads its expert id e = ids[t * ids_stride + u] from device memory with one
@@ -15,6 +15,8 @@
 //     (kq_gemv_form, qg_kq_launch.hpp).
 //   * IQ4_XS: iq4xs_moe_body<LPR, WGS, ONE> (qg_iq4xs_gemv_body.inc at one activation row), on the same ladder. The
 //     expert stride N * K/256 * 136 is a multiple of 8, the alignment of every load of the body.
+//   * Q3_K: q3k_moe_body<LPR, WGS, ONE> (qg_q3k_gemv_body.inc at one activation row), on the same ladder. The expert
+//     stride N * K/256 * 110 is any even number of bytes: the body realigns every load by its super-block's address.
 //   * MXFP4: mxfp4_moe_body<LPR, WGS, ONE> (qg_mxfp4_gemv_body.inc at one activation row), the single call's form for
 //     K / 32 units (kq_gemv_form_units). The expert stride N * K/32 * 17 is any number of bytes: the body's loads are
 //     realigned by each block's own address, so an expert at any byte offset is read as the single call reads it.
@@ -27,6 +29,7 @@
 #include "qg_iq4xs.hpp"
 #include "qg_kq_launch.hpp"
 #include "qg_mxfp4.hpp"
+#include "qg_q3k.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
 
@@ -62,6 +65,15 @@ __device__ __forceinline__ void iq4xs_moe_body(const uint32_t* __restrict__ A, c
     constexpr bool SUMI = false;
     constexpr long ldc = 0;
 #include "qg_iq4xs_gemv_body.inc"
+}
+
+template <int LPR, int WGS, bool ONE>
+__device__ __forceinline__ void q3k_moe_body(const uint32_t* __restrict__ A, const uint8_t* __restrict__ B, int N, int K,
+                                             void* __restrict__ out, const int tile) {
+    constexpr int MT = 1, M = 1;
+    constexpr bool SUMI = false;
+    constexpr long ldc = 0;
+#include "qg_q3k_gemv_body.inc"
 }
 
 template <int LPR, int WGS, bool ONE>
@@ -129,6 +141,7 @@ __global__ __launch_bounds__(WGS) void kq_moe_kernel(const MoeArgs a) {
     if (!moe_slot<WGS>(a, RPB, tile, s)) return;
     if constexpr (WT == QG_TYPE_Q4_K) q4k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
     else if constexpr (WT == QG_TYPE_IQ4_XS) iq4xs_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
+    else if constexpr (WT == QG_TYPE_Q3_K) q3k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
     else if constexpr (WT == QG_TYPE_MXFP4) mxfp4_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
     else q6k_moe_body<LPR, WGS, ONE>(s.A, s.B, a.N, a.K, s.C, tile);
 }
@@ -196,7 +209,9 @@ template <int WT> hipError_t moe_kq_launch(const Launch& L) {
 // The row types' LDS records of one activation row must fit (the single call has no such test at M <= 2 and fails
 // in the launch instead); the super-block types' and MXFP4's bound is their gemv_eligible.
 bool moe_lds_ok(int wtype, int K) {
-    if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_MXFP4) return true;
+    if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K ||
+        wtype == QG_TYPE_MXFP4)
+        return true;
     return gemv_lds_bytes<FMT_Q4_0, 2>(1, K) <= MAX_LDS_BYTES;  // (2-block units: the record size is the formats' common one)
 }
 
@@ -211,6 +226,7 @@ hipError_t launch_moe(const MoeArgs& a, int wtype, hipStream_t st, char* describ
         case QG_TYPE_Q4_K: return moe_kq_launch<QG_TYPE_Q4_K>(L);
         case QG_TYPE_Q6_K: return moe_kq_launch<QG_TYPE_Q6_K>(L);
         case QG_TYPE_IQ4_XS: return moe_kq_launch<QG_TYPE_IQ4_XS>(L);
+        case QG_TYPE_Q3_K: return moe_kq_launch<QG_TYPE_Q3_K>(L);
         case QG_TYPE_MXFP4: return moe_kq_launch<QG_TYPE_MXFP4>(L);
     }
     return hipErrorInvalidValue;

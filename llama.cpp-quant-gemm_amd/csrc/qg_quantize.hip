@@ -17,6 +17,7 @@
 #include "qg_common.hpp"
 #include "qg_iq4xs.hpp"
 #include "qg_kernels.hpp"
+#include "qg_q3k.hpp"
 #include "qg_q4k.hpp"
 #include "qg_mxfp4.hpp"
 #include "qg_q6k.hpp"
@@ -578,6 +579,46 @@ hipError_t launch_dequantize_iq4xs(const void* x, float* y, int64_t nsb, hipStre
     const int64_t nsub = nsb * 8;
     hipLaunchKernelGGL(dequantize_iq4xs_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
                        nsub);
+    return hipGetLastError();
+}
+
+// Q3_K (qg_q3k.hpp): one thread per 16-element scale group, y = (d * float(sc - 32)) * float(q) in exactly that
+// operation order (no contraction), so the result can be checked bit for bit. Group g = 8h + 2j + half of a super-block
+// is elements 128h + 32j + 16 half + 0..15: qs[32h + 16 half ..] bit pair j and hmask[16 half ..] bit 4h + j. Realigned
+// loads (q6k_load): x is 2-B aligned as for the products.
+namespace {
+__global__ __launch_bounds__(256) void dequantize_q3k_kernel(const uint8_t* __restrict__ x, float* __restrict__ y,
+                                                            int64_t ngroups) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ngroups) return;
+    const uint8_t* sbp = x + (t >> 4) * Q3K_BYTES;
+    const int g = (int)(t & 15), h = g >> 3, j = (g >> 1) & 3, half = g & 1;
+    const uint32_t sh = (uint32_t)((uintptr_t)sbp & 3);
+    uint32_t qr[5], hr[5], sr[4], qv[4], hm[4], sw[3];
+    q6k_load<4>(sbp + Q3K_QS + 32 * h + 16 * half, qr);
+    q6k_load<4>(sbp + 16 * half, hr);
+    q6k_load<3>(sbp + Q3K_SC, sr);
+    q6k_realign<4>(qr, sh, qv);
+    q6k_realign<4>(hr, sh, hm);
+    q6k_realign<3>(sr, sh, sw);
+    const q3k_scales s = q3k_unpack_scales(sw[0], sw[1], sw[2]);
+    const int sc = (int)((s.sc[g >> 2] >> (8 * (g & 3))) & 0xFFu) - 32;
+    const float dl = h2f((sr[3] >> (8 * sh)) & 0xFFFFu) * (float)sc;
+    float* o = y + t * 16;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t u = ((qv[i] >> (2 * j)) & 0x03030303u) | ((((hm[i] >> (4 * h + j)) & 0x01010101u)) << 2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[4 * i + k] = dl * (float)((int)((u >> (8 * k)) & 7u) - 4);
+    }
+}
+}  // namespace
+
+hipError_t launch_dequantize_q3k(const void* x, float* y, int64_t nsb, hipStream_t st) {
+    if (nsb <= 0) return hipSuccess;
+    const int64_t ngroups = nsb * 16;
+    hipLaunchKernelGGL(dequantize_q3k_kernel, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, st, (const uint8_t*)x, y,
+                       ngroups);
     return hipGetLastError();
 }
 

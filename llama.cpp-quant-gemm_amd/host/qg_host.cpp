@@ -239,6 +239,49 @@ void gemm_rows<FmtIQ4_XS>(const uint8_t* A, const uint8_t* B, float* C, int M, i
         }
 }
 
+// Q3_K (qg/blocks.h: 110-B super-blocks; Q8_1 block b of super-block sb is activation block 8 sb + b and meets the
+// scale groups 2b and 2b + 1). The product contract of qg.h: isum = s_2b * s0 + s_2b+1 * s1 in int32, one fp32
+// accumulator per super-block in block order, d applied once, super-blocks summed in order.
+struct FmtQ3_K {
+    static constexpr int bytes = 110;
+    // the signed code of element 32b + l of a super-block (b = 4h + j)
+    static int value(const uint8_t* w, int b, int l) {
+        const int lo2 = (w[32 + 32 * (b >> 2) + l] >> (2 * (b & 3))) & 3;
+        return lo2 - (((w[l] >> b) & 1) ? 0 : 4);
+    }
+    // sc_g - 32
+    static int scale(const uint8_t* w, int g) {
+        const uint8_t* s = w + 96;
+        const int low4 = g < 8 ? s[g] & 15 : s[g - 8] >> 4;
+        return (low4 | (((s[8 + g % 4] >> (2 * (g / 4))) & 3) << 4)) - 32;
+    }
+};
+template <>
+void gemm_rows<FmtQ3_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int N, int K, int j0, int j1) {
+    const int nsb = K / 256;
+    const size_t arow = (size_t)(K / QK) * 36, wrow = (size_t)nsb * FmtQ3_K::bytes;
+    for (int i = 0; i < M; ++i)
+        for (int n = j0; n < j1; ++n) {
+            float sum = 0.0f;
+            for (int sb = 0; sb < nsb; ++sb) {
+                const uint8_t* w = B + n * wrow + (size_t)sb * FmtQ3_K::bytes;
+                const float d = half_to_float(w + 108);
+                float fd = 0.0f;
+                for (int b = 0; b < 8; ++b) {
+                    const ActBlock a(A + i * arow + (size_t)(8 * sb + b) * 36);
+                    int32_t s0 = 0, s1 = 0;
+                    for (int l = 0; l < 16; ++l) {
+                        s0 += (int32_t)a.qs[l] * FmtQ3_K::value(w, b, l);
+                        s1 += (int32_t)a.qs[l + 16] * FmtQ3_K::value(w, b, l + 16);
+                    }
+                    fd += a.d * (float)(FmtQ3_K::scale(w, 2 * b) * s0 + FmtQ3_K::scale(w, 2 * b + 1) * s1);
+                }
+                sum += d * fd;
+            }
+            C[(size_t)i * N + n] = sum;
+        }
+}
+
 // Process-wide persistent worker pool: threads are started once (grown on demand) and parked on
 // a condition variable between jobs, so a multi-threaded call costs one wake-up per worker instead
 // of a thread start and join (which dominated a 1-9 ms GEMV at 256 threads). One job at a time
@@ -369,12 +412,14 @@ extern "C" {
 int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int threads) {
     const int rc = check_gemm(A, B, C, M, N, K);
     if (rc != QG_OK) return rc;
-    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS) && K % 256 != 0) return QG_ERR_BAD_K;
+    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K) && K % 256 != 0)
+        return QG_ERR_BAD_K;
     if (M == 0 || N == 0) return QG_OK;
     switch (wtype) {
         case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q6_K: gemm_threads<FmtQ6_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_IQ4_XS: gemm_threads<FmtIQ4_XS>(A, B, C, M, N, K, threads); return QG_OK;
+        case QG_TYPE_Q3_K: gemm_threads<FmtQ3_K>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_MXFP4: gemm_threads<FmtMXFP4>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
         case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
@@ -387,7 +432,7 @@ int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, in
 
 int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
                          float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
-    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS;
+    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K;
     int bb = 0;
     switch (wtype) {
         case QG_TYPE_Q4_0: bb = FmtQ4_0::bytes; break;
@@ -398,6 +443,7 @@ int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert,
         case QG_TYPE_Q4_K: bb = FmtQ4_K::bytes; break;
         case QG_TYPE_Q6_K: bb = FmtQ6_K::bytes; break;
         case QG_TYPE_IQ4_XS: bb = FmtIQ4_XS::bytes; break;
+        case QG_TYPE_Q3_K: bb = FmtQ3_K::bytes; break;
         case QG_TYPE_MXFP4: bb = FmtMXFP4::bytes; break;
     }
     // the order of qg_gemm_w4a8_moe

@@ -31,8 +31,8 @@ SIGNATURES = {
     "qg_dequantize_row_mxfp4_cpu": ([P, P, I64], I),
     "qg_fill_step4_cpu": ([ctypes.c_uint, I, I, I, I, I, P, P], I),
 }
-# 12: Q4_K, 14: Q6_K, 23: IQ4_XS, 256-element super-blocks; 39: MXFP4, 32-element blocks of 17 bytes
-BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 12: 144, 14: 210, 23: 136, 39: 17}
+# 11: Q3_K, 12: Q4_K, 14: Q6_K, 23: IQ4_XS, 256-element super-blocks; 39: MXFP4, 32-element blocks of 17 bytes
+BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 11: 110, 12: 144, 14: 210, 23: 136, 39: 17}
 GLU_REGLU, GLU_SWIGLU, GLU_SWIGLU_OAI = 0, 2, 3  # QG_GLU_* of qg.h
 _lib = None
 
@@ -107,7 +107,7 @@ def gemm_w4a8_moe(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, t: in
     stride defaults to the array's row length); an id outside [0, n_expert) gives zeros."""
     a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
     ids = np.ascontiguousarray(ids, np.int32)
-    be = 256 if wtype in (12, 14, 23) else 32
+    be = 256 if wtype in (11, 12, 14, 23) else 32
     n_expert = experts_q.size // (n * (k // be) * BLOCK_BYTES[wtype])
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used
