@@ -25,22 +25,7 @@
 using namespace qg;
 
 namespace qg {
-int block_bytes(int t) {
-    switch (t) {
-        case QG_TYPE_Q4_0: return 18;
-        case QG_TYPE_Q4_1: return 20;
-        case QG_TYPE_Q5_0: return 22;
-        case QG_TYPE_Q5_1: return 24;
-        case QG_TYPE_Q8_0: return 34;
-        case QG_TYPE_Q8_1: return 36;
-        case QG_TYPE_Q4_K: return 144;
-        case QG_TYPE_Q6_K: return 210;
-        case QG_TYPE_MXFP4: return MXFP4_BYTES;
-        case QG_TYPE_IQ4_XS: return IQ4XS_BYTES;
-        case QG_TYPE_Q3_K: return Q3K_BYTES;
-    }
-    return 0;
-}
+int block_bytes(int t) { return weight_type(t).bytes; }
 }  // namespace qg
 
 namespace {
@@ -52,34 +37,13 @@ int hip_status(hipError_t e) {
     return QG_ERR_HIP;
 }
 
-bool is_weight_type(int t) {
-    return t == QG_TYPE_Q4_0 || t == QG_TYPE_Q4_1 || t == QG_TYPE_Q5_0 || t == QG_TYPE_Q5_1 || t == QG_TYPE_Q8_0;
-}
-
-// The super-block types (256 elements: Q4_K, Q6_K, IQ4_XS, Q3_K): taken by the entries that go through run_product with
-// sb_ok; every other entry tests is_weight_type alone and so keeps refusing them.
-bool is_q4k_type(int t) { return t == QG_TYPE_Q4_K; }
-bool is_q6k_type(int t) { return t == QG_TYPE_Q6_K; }
-bool is_iq4xs_type(int t) { return t == QG_TYPE_IQ4_XS; }
-bool is_q3k_type(int t) { return t == QG_TYPE_Q3_K; }
-bool is_sb_type(int t) { return is_q4k_type(t) || is_q6k_type(t) || is_iq4xs_type(t) || is_q3k_type(t); }
-
-// MXFP4 (32 elements in 17 bytes): a route of its own beside the 32-element families and the super-block types,
-// taken by the same entries as the latter (run_product with sb_ok) and by qg_gemm_w4a8_moe; is_weight_type does not
-// know it, so every entry that tests that alone refuses it.
-bool is_mxfp4_type(int t) { return t == QG_TYPE_MXFP4; }
-// the types with a route of their own: their kernels, their K granule, their weight alignment
-bool is_routed_type(int t) { return is_sb_type(t) || is_mxfp4_type(t); }
-
-int block_elems(int t) { return is_sb_type(t) ? 256 : block_bytes(t) ? 32 : 0; }
-
-// Weight pointer alignment of a routed type: Q4_K's 144-B super-blocks are read with 16-B loads; a Q6_K
-// super-block is 210 B, so its fp16 field's 2 B is all a row guarantees and the kernels realign every load; an
-// MXFP4 block is 17 B of bytes, so there is no requirement at all; an IQ4_XS super-block is 136 = 8 x 17 B and is read
-// with 8-B loads; a Q3_K super-block is 110 B, 2 mod 4 as Q6_K's, and its kernels realign every load likewise.
-uintptr_t sb_weight_mask(int t) {
-    return is_mxfp4_type(t) ? 0u : is_q6k_type(t) || is_q3k_type(t) ? 1u : is_iq4xs_type(t) ? 7u : 15u;
-}
+// The table (qg_types.hpp) by id. The 32-element weight types; the types with a route of their own (their kernels, their K
+// granule, their weight alignment: the entries with the routed type's class take them, every other entry tests
+// is_weight_type alone and so refuses them as any type it does not take, at the 32-element granule).
+bool is_weight_type(int t) { return type_in(t, IN_PRODUCT) && !weight_type(t).routed; }
+bool is_routed_type(int t) { return weight_type(t).routed; }
+int block_elems(int t) { return weight_type(t).elems; }
+uintptr_t sb_weight_mask(int t) { return weight_type(t).wmask; }
 
 // ---- the one ordered precheck ------------------------------------------------------------------------------
 // The order every entry documents (qg.h): a negative size is QG_ERR_INVALID_ARG; K not a positive multiple of
@@ -208,56 +172,38 @@ int run_q32(GemmArgs& g, int algo, hipStream_t st) {
     return QG_OK;
 }
 
-// The super-block products (qg_q4k.hpp, qg_q6k.hpp): the decode GEMV up to M = 8 (Q3_K: 6), the MFMA prefill beyond.
-// Interleaved A/B of Q4_K against a build with the threshold at 4 | 5 (profiles/q4k/ab_q4k_variants.txt,
-// N = K = 4096): M = 5 GEMV 5.82 us, MFMA 7.43; M = 8 GEMV 7.31, MFMA 7.45 — the GEMV keeps M <= 8; Q6_K keeps the
-// threshold ("Q6_K", 3b). The GEMV's LDS records bound M * K (gemv_eligible); beyond that AUTO takes the
-// MFMA kernel at any M. Never through launch_or_merge_gemv: a captured super-block GEMV is a plain kernel node.
-#ifndef QG_Q4K_GEMV_MAXM  // (A/B builds: the largest M AUTO sends to the decode GEMV)
-#define QG_Q4K_GEMV_MAXM 8
-#endif
-#ifndef QG_Q6K_GEMV_MAXM
-#define QG_Q6K_GEMV_MAXM 8
-#endif
-// MXFP4 keeps the threshold (profiles/mxfp4/ab_mxfp4_threshold.txt, N = K = 4096, each kernel forced): M = 5 GEMV
-// 5.95 us, MFMA 12.04; M = 8 GEMV 6.99, MFMA 12.08.
-#ifndef QG_MXFP4_GEMV_MAXM
-#define QG_MXFP4_GEMV_MAXM 8
-#endif
-// IQ4_XS keeps the threshold (profiles/iq4xs/ab_iq4xs_threshold.txt, each kernel forced).
-#ifndef QG_IQ4XS_GEMV_MAXM
-#define QG_IQ4XS_GEMV_MAXM 8
-#endif
-// Q3_K moves it to 6 | 7 (profiles/q3k/ab_q3k_threshold.txt, N = K = 4096, each kernel forced): M = 5 GEMV 6.06 us, MFMA
-// 6.56; M = 6 6.46 / 6.55; M = 7 7.24 / 6.58; M = 8 7.56 / 6.59, each beyond the rounds' spread: its prefill needs one MFMA
-// per block and so starts cheaper than the others' (DESIGN.md 3l). The GEMV can still be forced up to M = 8.
-#ifndef QG_Q3K_GEMV_MAXM
-#define QG_Q3K_GEMV_MAXM 6
-#endif
+// The routed products: the decode GEMV up to the row's gemv_maxm (qg_types.hpp: 8, Q3_K 6), the MFMA prefill beyond. The
+// GEMV's LDS records bound M * K (gemv_eligible); beyond that AUTO takes the MFMA kernel at any M. Never through
+// launch_or_merge_gemv: a captured routed GEMV is a plain kernel node.
 struct SbRoute {
+    int id;
     bool (*gemv_eligible)(const GemmArgs&);
     hipError_t (*launch_gemv)(const GemmArgs&, hipStream_t);
     bool (*mmq_eligible)(const GemmArgs&);
     hipError_t (*launch_mmq)(const GemmArgs&, hipStream_t);
-    int maxm;
+    hipError_t (*launch_dequantize)(const void*, float*, int64_t, hipStream_t);
 };
-constexpr SbRoute SB_ROUTES[] = {  // Q4_K, Q6_K, IQ4_XS, Q3_K
-    {q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, QG_Q4K_GEMV_MAXM},
-    {q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, QG_Q6K_GEMV_MAXM},
-    {iq4xs_gemv_eligible, launch_iq4xs_gemv, iq4xs_mmq_eligible, launch_iq4xs_mmq, QG_IQ4XS_GEMV_MAXM},
-    {q3k_gemv_eligible, launch_q3k_gemv, q3k_mmq_eligible, launch_q3k_mmq, QG_Q3K_GEMV_MAXM},
+// parallel to WEIGHT_TYPES: a route per routed row (the others: run_q32, launch_dequantize)
+constexpr SbRoute ROUTES[N_WEIGHT_TYPES] = {
+    {QG_TYPE_Q4_0}, {QG_TYPE_Q4_1}, {QG_TYPE_Q5_0}, {QG_TYPE_Q5_1}, {QG_TYPE_Q8_0}, {QG_TYPE_Q8_1},
+    {QG_TYPE_Q3_K, q3k_gemv_eligible, launch_q3k_gemv, q3k_mmq_eligible, launch_q3k_mmq, launch_dequantize_q3k},
+    {QG_TYPE_Q4_K, q4k_gemv_eligible, launch_q4k_gemv, q4k_mmq_eligible, launch_q4k_mmq, launch_dequantize_q4k},
+    {QG_TYPE_Q6_K, q6k_gemv_eligible, launch_q6k_gemv, q6k_mmq_eligible, launch_q6k_mmq, launch_dequantize_q6k},
+    {QG_TYPE_IQ4_XS, iq4xs_gemv_eligible, launch_iq4xs_gemv, iq4xs_mmq_eligible, launch_iq4xs_mmq, launch_dequantize_iq4xs},
+    {QG_TYPE_MXFP4, mxfp4_gemv_eligible, launch_mxfp4_gemv, mxfp4_mmq_eligible, launch_mxfp4_mmq, launch_dequantize_mxfp4},
 };
-// The fifth route: MXFP4 (qg_mxfp4.hpp), the same two families and the same rules, its kernels' own.
-constexpr SbRoute MXFP4_ROUTE = {mxfp4_gemv_eligible, launch_mxfp4_gemv, mxfp4_mmq_eligible, launch_mxfp4_mmq,
-                                 QG_MXFP4_GEMV_MAXM};
-// the route of a routed type (is_routed_type holds)
-const SbRoute& sb_route(int t) {
-    return is_mxfp4_type(t) ? MXFP4_ROUTE : SB_ROUTES[is_q3k_type(t) ? 3 : is_iq4xs_type(t) ? 2 : is_q6k_type(t) ? 1 : 0];
+constexpr bool routes_match() {
+    for (int i = 0; i < N_WEIGHT_TYPES; ++i)
+        if (ROUTES[i].id != WEIGHT_TYPES[i].id || WEIGHT_TYPES[i].routed != (ROUTES[i].launch_gemv != nullptr)) return false;
+    return true;
 }
+static_assert(routes_match(), "ROUTES runs parallel to WEIGHT_TYPES");
+// the route of a routed type (is_routed_type holds)
+const SbRoute& sb_route(int t) { return ROUTES[weight_type_index(t)]; }
 
 int select_algo_sb(const GemmArgs& g) {
     const SbRoute& r = sb_route(g.wtype);
-    return g.M <= r.maxm && r.gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
+    return g.M <= weight_type(g.wtype).gemv_maxm && r.gemv_eligible(g) ? QG_ALGO_GEMV : QG_ALGO_MFMA;
 }
 
 // A super-block type, or MXFP4, after the precheck.
@@ -467,26 +413,22 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
     return (size_t)moe_plan_layout((long)(T * n_used), (long)n_expert, min_r).total * sizeof(int32_t);
 }
 
-// What the entries check alike, in the order qg.h documents. rows_ok: the entry takes the 32-element types
-// (otherwise one of them is a type it does not take, checked at the 32-element granule as in run_product). min_r: 0,
+// What the entries check alike, in the order qg.h documents. cls: the entry's class (qg_types.hpp): a type whose row
+// does not have it is one the entry does not take, checked at the 32-element granule as in run_product. min_r: 0,
 // or the entry runs a plan in a workspace sized for tiles of min_r rows. up: the entry has a second weights pointer,
 // B_up, checked beside B with the same mask. down: the entry is qg_gemm_w4a8_moe_down: weights stands beside the other
 // pointers (null allowed, 4 B otherwise), w_stride beside ids_stride, and the grid's y is the token, so T is what 65535
-// bounds (slots stays 0). c.biased: the entry is one of the four _bias ones: it takes MXFP4 beside the super-block types,
-// its bias pointers stand beside the other pointers (null allowed, 4 B otherwise), bias_stride and the OAI op's alpha
+// bounds (slots stays 0). c.biased: the entry is one of the four _bias ones: its bias pointers stand beside the other pointers (null allowed, 4 B otherwise), bias_stride and the OAI op's alpha
 // and limit beside ids_stride.
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
 //   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
 //   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
-int moe_front(MoeCall& c, bool rows_ok, int min_r, bool up = false, bool down = false) {
-    // (MXFP4 is a type of qg_gemm_w4a8_moe and the four _bias entries, IQ4_XS and Q3_K of qg_gemm_w4a8_moe alone: elsewhere they
-    // are refused as the 32-element types are)
-    const bool ksb = (is_sb_type(c.wtype) && (rows_ok || !(is_iq4xs_type(c.wtype) || is_q3k_type(c.wtype)))) ||
-                     ((rows_ok || c.biased) && is_mxfp4_type(c.wtype));
+int moe_front(MoeCall& c, unsigned cls, int min_r, bool up = false, bool down = false) {
+    const bool taken = type_in(c.wtype, cls), ksb = taken && is_routed_type(c.wtype);
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
-    const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, ksb || (rows_ok && is_weight_type(c.wtype)),
+    const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, taken,
                             {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
                              {down && c.weights ? c.weights : c.A, 3}, {c.C, 0},
                              {c.biased && c.bias_gate ? c.bias_gate : c.A, 3}, {c.biased && c.bias_up ? c.bias_up : c.A, 3}});
@@ -530,7 +472,7 @@ bool moe_gemv_route(const MoeCall& c) {
 
 // qg_gemm_w4a8_moe, qg_moe_config. Its own refusals: a shape off the decode GEMV, LDS records beyond 160 KiB.
 int run_moe(MoeCall& c) {
-    const int rc = moe_front(c, true, 0);
+    const int rc = moe_front(c, IN_MOE, 0);
     if (rc != QG_GO) return rc;
     if (!moe_gemv_route(c) || !moe_lds_ok(c.wtype, c.K)) return QG_ERR_UNSUPPORTED;
     MoeArgs a = moe_kernel_args<MoeArgs>(c);
@@ -540,7 +482,7 @@ int run_moe(MoeCall& c) {
 
 // qg_gemm_w4a8_moe_prefill, qg_moe_prefill_config and qg_debug_moe_prefill_plan (which stops after the plan): Q4_K / Q6_K.
 int moe_prefill_args(MoeCall& c, MoePlanArgs& a) {
-    const int rc = moe_front(c, false, MOE_PREFILL_MIN_R);
+    const int rc = moe_front(c, IN_MOE_PLAIN, MOE_PREFILL_MIN_R);
     if (rc != QG_GO) return rc;
     a = moe_kernel_args<MoePlanArgs>(c);
     a.ws = (int32_t*)c.ws;
@@ -557,7 +499,7 @@ int run_moe_prefill(MoeCall& c) {
 // qg_gemm_w4a8_moe_batch, qg_moe_batch_config: Q4_K / Q6_K. Its own refusals: a shape off the decode GEMV, K whose
 // records of two rows exceed the LDS (moe_batch_rows), a tile bound beyond 65535.
 int run_moe_batch(MoeCall& c) {
-    const int rc = moe_front(c, false, MOE_BATCH_MIN_R);
+    const int rc = moe_front(c, IN_MOE_PLAIN, MOE_BATCH_MIN_R);
     if (rc != QG_GO) return rc;
     const int R = moe_batch_rows(c.slots, c.n_expert, c.K, c.wtype);
     if (!moe_gemv_route(c) || R == 0 || moe_max_tiles(c.slots, c.n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
@@ -578,7 +520,7 @@ MoeBiasArgs moe_bias_args(const MoeCall& c) {
 
 int run_moe_prefill_bias(MoeCall& c) {
     c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
-    const int rc = moe_front(c, false, MOE_PREFILL_MIN_R);
+    const int rc = moe_front(c, IN_MOE_BIAS, MOE_PREFILL_MIN_R);
     if (rc != QG_GO) return rc;
     return hip_status(launch_moe_prefill_bias(moe_bias_args(c), c.wtype, c.st, c.describe, c.describe_len));
 }
@@ -586,7 +528,7 @@ int run_moe_prefill_bias(MoeCall& c) {
 // qg_gemm_w4a8_moe_batch_bias, qg_moe_batch_bias_config: Q4_K / Q6_K / MXFP4 (c.biased), run_moe_batch's refusals.
 int run_moe_batch_bias(MoeCall& c) {
     c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
-    const int rc = moe_front(c, false, MOE_BATCH_MIN_R);
+    const int rc = moe_front(c, IN_MOE_BIAS, MOE_BATCH_MIN_R);
     if (rc != QG_GO) return rc;
     const int R = moe_batch_rows(c.slots, c.n_expert, c.K, c.wtype);
     if (!moe_gemv_route(c) || R == 0 || moe_max_tiles(c.slots, c.n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
@@ -596,7 +538,7 @@ int run_moe_batch_bias(MoeCall& c) {
 // qg_gemm_w4a8_moe_glu, qg_moe_glu_config: Q4_K / Q6_K. Its own refusals: a glu_op it does not have, a shape off the
 // decode GEMV (the bound on the LDS records is part of that route for the super-block types).
 int run_moe_glu(MoeCall& c) {
-    const int rc = moe_front(c, false, 0, true);
+    const int rc = moe_front(c, IN_MOE_PLAIN, 0, true);
     if (rc != QG_GO) return rc;
     if ((c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU) || !moe_gemv_route(c)) return QG_ERR_UNSUPPORTED;
     MoeGluArgs a;
@@ -610,7 +552,7 @@ int run_moe_glu(MoeCall& c) {
 // GEMV, the records of the token's n_used activation rows and its n_used x RPB products beyond the LDS.
 int run_moe_down(MoeCall& c) {
     c.a_rows = c.n_used;
-    const int rc = moe_front(c, false, 0, false, true);
+    const int rc = moe_front(c, IN_MOE_PLAIN, 0, false, true);
     if (rc != QG_GO) return rc;
     if (!moe_gemv_route(c) || moe_down_form(c.n_used, c.K, c.wtype).lds > MAX_LDS_BYTES) return QG_ERR_UNSUPPORTED;
     MoeDownArgs a;
@@ -625,7 +567,7 @@ int run_moe_down(MoeCall& c) {
 // third op among the known ones.
 int run_moe_glu_bias(MoeCall& c) {
     c.biased = true;
-    const int rc = moe_front(c, false, 0, true);
+    const int rc = moe_front(c, IN_MOE_BIAS, 0, true);
     if (rc != QG_GO) return rc;
     if ((c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU && c.glu_op != QG_GLU_SWIGLU_OAI) || !moe_gemv_route(c))
         return QG_ERR_UNSUPPORTED;
@@ -641,7 +583,7 @@ int run_moe_glu_bias(MoeCall& c) {
 int run_moe_down_bias(MoeCall& c) {
     c.a_rows = c.n_used;
     c.biased = true; c.bias_up = nullptr; c.glu_op = QG_GLU_REGLU;
-    const int rc = moe_front(c, false, 0, false, true);
+    const int rc = moe_front(c, IN_MOE_BIAS, 0, false, true);
     if (rc != QG_GO) return rc;
     if (!moe_gemv_route(c) || moe_down_form(c.n_used, c.K, c.wtype).lds > MAX_LDS_BYTES) return QG_ERR_UNSUPPORTED;
     MoeDownBiasArgs a;
@@ -1306,7 +1248,7 @@ int qg_gemm_w8a8(const void* A, const void* B, float* C, int M, int N, int K, qg
 }
 
 int qg_quantize(int type, int variant, const float* x, void* y, int64_t k, qg_stream_t stream) {
-    const bool type_ok = block_bytes(type) != 0 && !is_routed_type(type);  // (no Q4_K / Q6_K / MXFP4 quantizer)
+    const bool type_ok = type_in(type, IN_QUANTIZE);  // (no quantizer of a routed type)
     const bool variant_ok = variant == 0 || (variant == 1 && type == QG_TYPE_Q8_1) ||
                             (variant == 2 && (type == QG_TYPE_Q8_1 || type == QG_TYPE_Q4_0));
     const int rc = precheck_count(k, 32, type_ok && variant_ok, {{x, 3}, {y, type == QG_TYPE_Q8_1 ? 3u : 1u}});
@@ -1324,14 +1266,11 @@ int qg_quantize_q4_0_definition(const float* x, void* y, int64_t num_elements, q
 }
 
 int qg_dequantize(int type, const void* x, float* y, int64_t k, qg_stream_t stream) {
-    const int be = is_sb_type(type) ? 256 : 32;  // (an unknown type: the 32-element granule, then refused)
-    const int rc = precheck_count(k, be, block_bytes(type) != 0, {{x, is_mxfp4_type(type) ? 0u : is_iq4xs_type(type) ? 7u : 1u}, {y, 3}});
+    const WeightType w = weight_type(type);
+    const int be = w.elems ? w.elems : 32;  // (an unknown type: the 32-element granule, then refused)
+    const int rc = precheck_count(k, be, type_in(type, IN_DEQUANTIZE), {{x, w.dq_mask}, {y, 3}});
     if (rc != QG_GO) return rc;
-    if (is_mxfp4_type(type)) return hip_status(launch_dequantize_mxfp4(x, y, k / 32, (hipStream_t)stream));
-    if (is_iq4xs_type(type)) return hip_status(launch_dequantize_iq4xs(x, y, k / 256, (hipStream_t)stream));
-    if (is_q3k_type(type)) return hip_status(launch_dequantize_q3k(x, y, k / 256, (hipStream_t)stream));
-    if (is_q6k_type(type)) return hip_status(launch_dequantize_q6k(x, y, k / 256, (hipStream_t)stream));
-    if (is_q4k_type(type)) return hip_status(launch_dequantize_q4k(x, y, k / 256, (hipStream_t)stream));
+    if (w.routed) return hip_status(sb_route(type).launch_dequantize(x, y, k / be, (hipStream_t)stream));
     return hip_status(launch_dequantize(type, x, y, k / 32, (hipStream_t)stream));
 }
 

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/qg/qg.h"
+#include "qg_types.hpp"
 
 struct qg_gguf {
     int fd = -1;
@@ -115,18 +116,12 @@ uint64_t tensor_bytes(uint32_t t, const int64_t ne[4], uint32_t n_dims) {
         case QG_TYPE_F32: return n * 4;
         case QG_TYPE_F16: return n * 2;
     }
-    // the types this reader serves: the 32-element blocks, MXFP4 (17-B blocks of 32, what the gpt-oss expert tensors
-    // are stored as), Q4_K (144-B super-blocks of 256), IQ4_XS (136-B super-blocks of 256) and Q3_K (110-B super-blocks of 256). The reader's own
-    // list, not every type qg_block_bytes knows: a Q6_K tensor stays listed with nbytes == 0 and is not readable
-    // (lifting that is a follow-up of its own, DESIGN.md "Q6_K")
-    switch (t) {
-        case QG_TYPE_Q4_0: case QG_TYPE_Q4_1: case QG_TYPE_Q5_0: case QG_TYPE_Q5_1: case QG_TYPE_Q8_0: case QG_TYPE_Q8_1:
-        case QG_TYPE_Q4_K: case QG_TYPE_MXFP4: case QG_TYPE_IQ4_XS: case QG_TYPE_Q3_K: break;
-        default: return 0;
-    }
-    const int bb = qg_block_bytes((int)t), be = qg_block_elems((int)t);
-    if (bb == 0 || be == 0 || ne[0] % be != 0) return 0;
-    return n / (uint64_t)be * (uint64_t)bb;
+    // the types this reader serves (IN_GGUF, qg_types.hpp: MXFP4 is what the gpt-oss expert tensors are stored as). Not
+    // every type qg_block_bytes knows: a Q6_K tensor stays listed with nbytes == 0 and is not readable (lifting that
+    // is a follow-up of its own, DESIGN.md "Q6_K")
+    const qg::WeightType w = qg::weight_type((int)t);
+    if (!(w.entries & qg::IN_GGUF) || ne[0] % w.elems != 0) return 0;
+    return n / (uint64_t)w.elems * (uint64_t)w.bytes;
 }
 
 int parse(qg_gguf* g) {
@@ -170,14 +165,9 @@ int parse(qg_gguf* g) {
         t.type = r.get<uint32_t>();
         t.offset = r.get<uint64_t>();
         t.nbytes = tensor_bytes(t.type, t.ne, t.n_dims);
-        // a Q4_K row is whole super-blocks: ggml cannot have written anything else
-        if (t.type == QG_TYPE_Q4_K && r.ok && t.ne[0] % 256 != 0) return QG_ERR_INVALID_ARG;
-        // so is an IQ4_XS row (136-B super-blocks)
-        if (t.type == QG_TYPE_IQ4_XS && r.ok && t.ne[0] % 256 != 0) return QG_ERR_INVALID_ARG;
-        // and a Q3_K row (110-B super-blocks)
-        if (t.type == QG_TYPE_Q3_K && r.ok && t.ne[0] % 256 != 0) return QG_ERR_INVALID_ARG;
-        // an MXFP4 row is whole 32-element blocks
-        if (t.type == QG_TYPE_MXFP4 && r.ok && t.ne[0] % 32 != 0) return QG_ERR_INVALID_ARG;
+        // a row of a routed type the reader serves is whole blocks: ggml cannot have written anything else
+        const qg::WeightType w = qg::weight_type((int)t.type);
+        if (w.routed && (w.entries & qg::IN_GGUF) && r.ok && t.ne[0] % w.elems != 0) return QG_ERR_INVALID_ARG;
         g->tensors.push_back(std::move(t));
     }
     if (!r.ok) return QG_ERR_INVALID_ARG;

@@ -21,10 +21,11 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 
 namespace qg {
 
-constexpr int IQ4XS_BYTES = 136;
+constexpr int IQ4XS_BYTES = weight_type(QG_TYPE_IQ4_XS).bytes;
 constexpr int IQ4XS_DW = 34;
 
 // The codebook as four table dwords, entries 4t .. 4t + 3 in the bytes of IQ4XS_KV[t].
@@ -88,7 +89,7 @@ constexpr int IQ4XS_UNIT_DW = 10;
 // on. 19 is odd, so the sixteen 16-B bank groups a quarter-wave's reads start in step through all residues before
 // any repeats (72 = 4 x 18 would put records two apart on the same groups); the d_a pair of a unit is one 8-B read at
 // 64 + 2i, which the same stride spreads likewise.
-constexpr int IQ4XS_REC_DW = 76;
+constexpr int IQ4XS_REC_DW = weight_type(QG_TYPE_IQ4_XS).rec_dw;
 
 // MFMA prefill (M >= 9): see qg_iq4xs_mmq.hip. The activation staging in LDS, as the Q4_K / MXFP4 prefill's.
 constexpr int IQ4XS_TOK_DW = 72;                   // one token's 8 blocks of a super-block: 288 B

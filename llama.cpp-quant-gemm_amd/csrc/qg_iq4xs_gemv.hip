@@ -43,13 +43,9 @@ __global__ __launch_bounds__(WGS) void iq4xs_gemv_kernel(const uint32_t* __restr
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct iq4xs_gemv_fmt {
-    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = IQ4XS_REC_DW, UNIT = 64;
-    static constexpr uintptr_t WMASK = 7;  // the 8-B loads
+    static constexpr int WT = QG_TYPE_IQ4_XS;
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return iq4xs_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
-    }
-    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
-        describe_kernel(g, "iq4xs_gemv MT=%d LPR=%d WGS=%d ONE=%d grid=%d lds=%zu", MT, LPR, WGS, one, grid, lds);
     }
 };
 

@@ -106,9 +106,7 @@ __global__ __launch_bounds__(IQ4XS_MMQ_WGS) void iq4xs_mmq_kernel(const uint32_t
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct iq4xs_mmq_fmt {
-    static constexpr const char* NAME = "iq4xs_mmq";
-    static constexpr int WAVES = IQ4XS_MMQ_WAVES, KMULT = SB_ELEMS;
-    static constexpr uintptr_t WMASK = 7;  // the 8-B loads
+    static constexpr int WT = QG_TYPE_IQ4_XS, WAVES = IQ4XS_MMQ_WAVES;
     template <int TT, int RG, bool SUMI> static auto kernel() { return iq4xs_mmq_kernel<TT, RG, SUMI>; }
 };
 

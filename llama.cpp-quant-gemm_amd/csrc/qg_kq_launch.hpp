@@ -1,22 +1,21 @@
-// qg_kq_launch.hpp — the host side the super-block (Q4_K, Q6_K, IQ4_XS, Q3_K) and the MXFP4 kernels share: instantiation choice,
-// launch and eligibility of the decode GEMV (qg_q4k_gemv.hip, qg_q6k_gemv.hip, qg_iq4xs_gemv.hip, qg_q3k_gemv.hip, qg_mxfp4_gemv.hip) and
-// of the MFMA prefill (qg_q4k_mmq.hip, qg_q6k_mmq.hip, qg_iq4xs_mmq.hip, qg_q3k_mmq.hip, qg_mxfp4_mmq.hip). The kernels themselves stay one per type (DESIGN.md,
+// qg_kq_launch.hpp — the host side the routed types' kernels share (the rows of qg_types.hpp with a route: the super-block
+// types and MXFP4): instantiation choice, launch and eligibility of the decode GEMV (qg_<type>_gemv.hip) and of the MFMA
+// prefill (qg_<type>_mmq.hip). The kernels themselves stay one per type (DESIGN.md,
 // "Q4_K": what was tried to share them); within a type a kernel's body is one text, qg_<type>_{gemv,mmq}_body.inc,
 // which the shipped kernel and its expert-indexed / expert-grouped twins (qg_moe.hip, qg_moe_batch.hip,
 // qg_moe_prefill.hip; their plan: qg_moe_plan.hip) all include.
 //
-// A type's file passes a struct F of constants and static functions:
-//   GEMV:  REC_ELEMS and REC_DW (elements and dwords of an LDS record: a token's super-block, or its block for MXFP4;
-//          K is a multiple of REC_ELEMS), UNIT (elements of a lane's unit), WMASK (the low bits of the weights pointer
-//          that must be 0), kernel<MT, LPR, WGS, SUMI, ONE>() and describe(g, MT, LPR, WGS, one, grid, lds), the
-//          qg_debug_config line
-//   MMQ:   NAME (the family, for the qg_debug_config line), WAVES, WMASK, KMULT (K is a multiple of it),
-//          kernel<TT, RG, SUMI>()
-// The expert entries have no F: kq_gemv_form picks their instantiation too, kq_gemv_rec_dw / kq_family name the type.
+// A type's file passes a struct F: WT, its id (the record, the unit, the K granule, the weight alignment and the family
+// name of the qg_debug_config line are its row's, qg_types.hpp), and
+//   GEMV:  kernel<MT, LPR, WGS, SUMI, ONE>(), and NT where the config line names it (Q4_K)
+//   MMQ:   WAVES, kernel<TT, RG, SUMI>()
+// The expert entries have no F: kq_gemv_form picks their instantiation too; kq_row_lds_bytes, kq_row_units and kq_family
+// serve them by the type's id.
 #pragma once
 #include "../../include/qg/qg.h"
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 #include "qg_iq4xs.hpp"
 #include "qg_q3k.hpp"
 #include "qg_q4k.hpp"
@@ -25,16 +24,14 @@
 
 namespace qg {
 
-// A super-block type by its id: the decode GEMV's LDS record, the family ("q4k" + "_gemv" / "_mmq" in the config lines).
-constexpr int kq_gemv_rec_dw(int wtype) {
-    return wtype == QG_TYPE_Q4_K ? Q4K_REC_DW : wtype == QG_TYPE_IQ4_XS ? IQ4XS_REC_DW : wtype == QG_TYPE_Q3_K ? Q3K_REC_DW : Q6K_REC_DW;
-}
-constexpr const char* kq_family(int wtype) {
-    return wtype == QG_TYPE_Q4_K ? "q4k" : wtype == QG_TYPE_IQ4_XS ? "iq4xs" : wtype == QG_TYPE_Q3_K ? "q3k" : "q6k";
-}
+// A routed type by its id: the decode GEMV's LDS record, the family ("q4k" + "_gemv" / "_mmq" in the config lines).
+constexpr int kq_gemv_rec_dw(int wtype) { return weight_type(wtype).rec_dw; }
+constexpr const char* kq_family(int wtype) { return weight_type(wtype).family; }
 
 // ---- decode GEMV (M <= 8) ------------------------------------------------------------------------------------
-template <class F> inline size_t kq_gemv_lds_bytes(int M, int K) { return (size_t)M * (K / F::REC_ELEMS) * F::REC_DW * 4; }
+template <class F> inline size_t kq_gemv_lds_bytes(int M, int K) { return (size_t)M * kq_row_lds_bytes(F::WT, K); }
+template <class F, class = void> struct kq_gemv_nt { static constexpr int value = -1; };
+template <class F> struct kq_gemv_nt<F, std::void_t<decltype(F::NT)>> { static constexpr int value = F::NT; };
 
 // The decode GEMV's instantiation for K, chosen here and nowhere else: fn(LPR, WGS, ONE) as std::integral_constant /
 // bool_constant. The single call below and the expert entries (qg_moe{,_glu,_batch}.hip) launch what it hands them.
@@ -53,13 +50,16 @@ template <class Fn> auto kq_gemv_form_units(int U, Fn&& fn) {
 template <class Fn> auto kq_gemv_form(int K, Fn&& fn) { return kq_gemv_form_units(K / 64, fn); }
 
 template <class F, int MT, bool SUMI> hipError_t kq_gemv_launch_mt(const GemmArgs& g, hipStream_t st) {
-    // (units per row, rounded up: only a unit of several MXFP4 blocks can be partial)
-    return kq_gemv_form_units((g.K + F::UNIT - 1) / F::UNIT, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+    return kq_gemv_form_units(kq_row_units(F::WT, g.K), [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
         const size_t lds = kq_gemv_lds_bytes<F>(g.M, g.K);
         const int grid = (g.N + RPB - 1) / RPB;
         if (g.describe) {
-            F::describe(g, MT, LPR, WGS, (int)one, grid, lds);
+            constexpr int NT = kq_gemv_nt<F>::value;
+            if constexpr (NT >= 0)
+                describe_kernel(g, "%s_gemv MT=%d LPR=%d WGS=%d ONE=%d NT=%d grid=%d lds=%zu", kq_family(F::WT), MT, LPR, WGS, (int)one, NT, grid, lds);
+            else
+                describe_kernel(g, "%s_gemv MT=%d LPR=%d WGS=%d ONE=%d grid=%d lds=%zu", kq_family(F::WT), MT, LPR, WGS, (int)one, grid, lds);
             return hipSuccess;
         }
         auto k = F::template kernel<MT, LPR, WGS, SUMI, one>();
@@ -86,8 +86,9 @@ template <class F> hipError_t kq_gemv_launch(const GemmArgs& g, hipStream_t st) 
 }
 
 template <class F> bool kq_gemv_eligible(const GemmArgs& g) {
-    if (g.M < 1 || g.M > 8 || g.N < 1 || g.K <= 0 || g.K % F::REC_ELEMS != 0) return false;
-    if (((uintptr_t)g.B & F::WMASK) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
+    constexpr WeightType W = weight_type(F::WT);
+    if (g.M < 1 || g.M > 8 || g.N < 1 || g.K <= 0 || g.K % W.rec_elems != 0) return false;
+    if (((uintptr_t)g.B & W.wmask) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
     if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
     return kq_gemv_lds_bytes<F>(g.M, g.K) <= MAX_LDS_BYTES;
 }
@@ -96,7 +97,7 @@ template <class F> bool kq_gemv_eligible(const GemmArgs& g) {
 template <class F, int TT, int RG, bool SUMI> hipError_t kq_mmq_launch_cfg(const GemmArgs& g, hipStream_t st) {
     const int gx = (g.N + 16 * RG - 1) / (16 * RG), gy = (g.M + 16 * TT - 1) / (16 * TT);
     if (g.describe) {
-        describe_kernel(g, "%s TT=%d RG=%d KS=%d grid=%dx%d", F::NAME, TT, RG, F::WAVES / RG, gx, gy);
+        describe_kernel(g, "%s_mmq TT=%d RG=%d KS=%d grid=%dx%d", kq_family(F::WT), TT, RG, F::WAVES / RG, gx, gy);
         return hipSuccess;
     }
     void* out = SUMI ? (void*)g.sumi : (void*)g.C;
@@ -118,8 +119,9 @@ template <class F> hipError_t kq_mmq_launch(const GemmArgs& g, hipStream_t st) {
 }
 
 template <class F> bool kq_mmq_eligible(const GemmArgs& g) {
-    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % F::KMULT != 0) return false;
-    if (((uintptr_t)g.B & F::WMASK) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
+    constexpr WeightType W = weight_type(F::WT);
+    if (g.M < 1 || g.N < 1 || g.K <= 0 || g.K % W.elems != 0) return false;
+    if (((uintptr_t)g.B & W.wmask) != 0 || ((uintptr_t)g.A & 3) != 0) return false;
     if (g.ldc_n != 1 || g.batch != 1 || g.ain != AIN_Q8_1 || g.lay != LAY_ROWS) return false;
     return (g.M + 63) / 64 <= 65535;
 }

@@ -188,14 +188,12 @@ template <int F> hipError_t moe_row(const Launch& L) {
     });
 }
 
-// (MXFP4: a block per unit and per LDS record, where the super-block types have 64 elements and a super-block)
 template <int WT> hipError_t moe_kq_launch(const Launch& L) {
-    constexpr bool MX = WT == QG_TYPE_MXFP4;
-    return kq_gemv_form_units(MX ? (L.a.K / QK + MXFP4_UB - 1) / MXFP4_UB : L.a.K / 64, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+    return kq_gemv_form_units(kq_row_units(WT, L.a.K), [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
-        const size_t lds = MX ? (size_t)(L.a.K / QK) * MXFP4_REC_DW * 4 : (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const size_t lds = kq_row_lds_bytes(WT, L.a.K);
         if (L.describe) {
-            describe_line(L.describe, L.describe_len, "moe:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", MX ? "mxfp4" : kq_family(WT), LPR, WGS,
+            describe_line(L.describe, L.describe_len, "moe:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), LPR, WGS,
                           (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
             return hipSuccess;
         }
@@ -207,11 +205,9 @@ template <int WT> hipError_t moe_kq_launch(const Launch& L) {
 }  // namespace
 
 // The row types' LDS records of one activation row must fit (the single call has no such test at M <= 2 and fails
-// in the launch instead); the super-block types' and MXFP4's bound is their gemv_eligible.
+// in the launch instead); a routed type's bound is its gemv_eligible.
 bool moe_lds_ok(int wtype, int K) {
-    if (wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K ||
-        wtype == QG_TYPE_MXFP4)
-        return true;
+    if (weight_type(wtype).routed) return true;
     return gemv_lds_bytes<FMT_Q4_0, 2>(1, K) <= MAX_LDS_BYTES;  // (2-block units: the record size is the formats' common one)
 }
 

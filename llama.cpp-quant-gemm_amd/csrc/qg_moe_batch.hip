@@ -128,7 +128,7 @@ template <int WT, int MT> hipError_t moeb_mt(const Launch& L) {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
         constexpr bool ONE = one;
         const MoePlanArgs& a = L.a;
-        const size_t lds = (size_t)MT * (a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const size_t lds = (size_t)MT * kq_row_lds_bytes(WT, a.K);
         const int gy = (int)moe_max_tiles(a.slots, a.n_expert, MT);
         if (L.describe) {
             describe_line(L.describe, L.describe_len, "moeb:%s_gemv R=%d LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), MT,
@@ -198,10 +198,7 @@ template <int WT> hipError_t moeb_bias_r(const BiasLaunch& L) {
 }  // namespace
 
 // Bytes of the LDS records of one gathered row: K / 256 super-block records, or K / 32 block records for MXFP4 (48 B).
-size_t moe_batch_row_lds(int K, int wtype) {
-    if (wtype == QG_TYPE_MXFP4) return (size_t)(K / QK) * MXFP4_REC_DW * 4;
-    return (size_t)(K / SB_ELEMS) * kq_gemv_rec_dw(wtype) * 4;
-}
+size_t moe_batch_row_lds(int K, int wtype) { return kq_row_lds_bytes(wtype, K); }
 
 // Rows per tile. The expected rows per expert, per = ceil(slots / n_expert), rounded up to the body's MT = 2 / 4 / 8
 // (a tile costs one pass over the expert whatever its rows; a larger MT than the rows need only adds registers and LDS),

@@ -182,7 +182,8 @@ template <int WT> hipError_t moe_down_launch_t(const MoeLaunch<MoeDownArgs>& L) 
 // ---- qg_gemm_w4a8_moe_down_bias: kernel and host side ---------------------------------------------------------
 // The records of one activation row in dwords: K/256 super-block records, or K/32 block records for MXFP4.
 template <int WT> __host__ __device__ constexpr int down_row_dw(int K) {
-    return WT == QG_TYPE_MXFP4 ? (K / QK) * MXFP4_REC_DW : (K / SB_ELEMS) * kq_gemv_rec_dw(WT);
+    constexpr WeightType W = weight_type(WT);
+    return (K / W.rec_elems) * W.rec_dw;
 }
 
 // The kernel above (its three steps, its barriers) for Q4_K / Q6_K / MXFP4 with the per-expert bias row: a kernel of
@@ -237,15 +238,12 @@ __global__ __launch_bounds__(WGS) void kq_moe_down_bias_kernel(const MoeDownBias
     }
 }
 
-// the units of a row that pick the decode GEMV's form: K / 64, or MXFP4's blocks (moe_kq_launch, qg_moe.hip)
-int down_units(int K, int wtype) { return wtype == QG_TYPE_MXFP4 ? (K / QK + MXFP4_UB - 1) / MXFP4_UB : K / 64; }
-
 template <int WT, int LPR, int WGS, bool ONE, int SWSH> hipError_t moe_down_bias_k(const MoeLaunch<MoeDownBiasArgs>& L) {
     constexpr int RPB = (WGS / 64 >> SWSH) * (64 / LPR);
     const size_t lds = moe_down_form(L.a.n_used, L.a.K, WT).lds;
     if (L.describe) {
         describe_line(L.describe, L.describe_len, "moe_down:%s_gemv LPR=%d WGS=%d ONE=%d SW=%d grid=%dx%d lds=%zu",
-                      WT == QG_TYPE_MXFP4 ? "mxfp4" : kq_family(WT), LPR, WGS, (int)ONE, 1 << SWSH, (L.a.N + RPB - 1) / RPB, L.a.T, lds);
+                      kq_family(WT), LPR, WGS, (int)ONE, 1 << SWSH, (L.a.N + RPB - 1) / RPB, L.a.T, lds);
         return hipSuccess;
     }
     static std::atomic<unsigned long long> done_bias, done_plain;
@@ -254,7 +252,7 @@ template <int WT, int LPR, int WGS, bool ONE, int SWSH> hipError_t moe_down_bias
 }
 
 template <int WT> hipError_t moe_down_bias_launch_t(const MoeLaunch<MoeDownBiasArgs>& L) {
-    return kq_gemv_form_units(down_units(L.a.K, WT), [&](auto lpr, auto wgs, auto one) -> hipError_t {
+    return kq_gemv_form_units(kq_row_units(WT, L.a.K), [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, W = WGS / 64;
         switch (moe_down_swsh(L.a.n_used, W)) {
             case 0: return moe_down_bias_k<WT, LPR, WGS, one, 0>(L);
@@ -274,12 +272,11 @@ template <int WT> hipError_t moe_down_bias_launch_t(const MoeLaunch<MoeDownBiasA
 }  // namespace
 
 MoeDownForm moe_down_form(int n_used, int K, int wtype) {
-    return kq_gemv_form_units(down_units(K, wtype), [&](auto lpr, auto wgs, auto one) -> MoeDownForm {
+    return kq_gemv_form_units(kq_row_units(wtype, K), [&](auto lpr, auto wgs, auto one) -> MoeDownForm {
         constexpr int LPR = lpr, WGS = wgs, W = WGS / 64;
         const int sh = moe_down_swsh(n_used, W);
         MoeDownForm f{LPR, WGS, (int)one, 1 << sh, (W >> sh) * (64 / LPR), SIZE_MAX};
-        const size_t row = wtype == QG_TYPE_MXFP4 ? (size_t)down_row_dw<QG_TYPE_MXFP4>(K) * 4
-                                                  : (size_t)(K / SB_ELEMS) * kq_gemv_rec_dw(wtype) * 4;
+        const size_t row = kq_row_lds_bytes(wtype, K);
         if (n_used >= 0 && (size_t)n_used <= MAX_LDS_BYTES / 4) f.lds = (size_t)n_used * (row + (size_t)f.rpb * 4);
         return f;
     });

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(WGS) void kq_moe_glu_bias_kernel(const MoeGluBiasAr
 template <int WT> hipError_t moe_glu_launch_t(const MoeLaunch<MoeGluArgs>& L) {
     return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
-        const size_t lds = (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const size_t lds = kq_row_lds_bytes(WT, L.a.K);
         if (L.describe) {
             describe_line(L.describe, L.describe_len, "moe_glu:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu", kq_family(WT), LPR,
                           WGS, (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
@@ -232,15 +232,14 @@ template <int WT> hipError_t moe_glu_launch_t(const MoeLaunch<MoeGluArgs>& L) {
     });
 }
 
-// The same form; MXFP4: a block per unit and per LDS record, as moe_kq_launch (qg_moe.hip).
+// The same form by the row's units (kq_row_units: MXFP4's are blocks), as moe_kq_launch (qg_moe.hip).
 template <int WT> hipError_t moe_glu_bias_launch_t(const MoeLaunch<MoeGluBiasArgs>& L) {
-    constexpr bool MX = WT == QG_TYPE_MXFP4;
-    return kq_gemv_form_units(MX ? (L.a.K / QK + MXFP4_UB - 1) / MXFP4_UB : L.a.K / 64, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+    return kq_gemv_form_units(kq_row_units(WT, L.a.K), [&](auto lpr, auto wgs, auto one) -> hipError_t {
         constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR);
-        const size_t lds = MX ? (size_t)(L.a.K / QK) * MXFP4_REC_DW * 4 : (size_t)(L.a.K / SB_ELEMS) * kq_gemv_rec_dw(WT) * 4;
+        const size_t lds = kq_row_lds_bytes(WT, L.a.K);
         if (L.describe) {
             describe_line(L.describe, L.describe_len, "moe_glu:%s_gemv LPR=%d WGS=%d ONE=%d grid=%dx%d lds=%zu",
-                          MX ? "mxfp4" : kq_family(WT), LPR, WGS, (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
+                          kq_family(WT), LPR, WGS, (int)one, (L.a.N + RPB - 1) / RPB, L.a.slots, lds);
             return hipSuccess;
         }
         static std::atomic<unsigned long long> done_bias, done_plain;

@@ -18,10 +18,11 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 
 namespace qg {
 
-constexpr int MXFP4_BYTES = 17;
+constexpr int MXFP4_BYTES = weight_type(QG_TYPE_MXFP4).bytes;
 constexpr int MXFP4_COVER_DW = 5;  // aligned dwords that hold a block, whatever its address
 
 // scale(e) = 2^(e - 128) from its fp32 bits: e = 0 and e = 1 are the subnormals 2^-128 and 2^-127, no NaN code
@@ -61,15 +62,12 @@ __device__ __forceinline__ uint32_t mxfp4_kv4(uint32_t x) {
 // QG_MXFP4_UNIT_BLOCKS (A/B builds): consecutive blocks of a row a lane of the decode GEMV owns per unit, 1 (shipped)
 // or 2: ten loads in flight per unit and a loop-free form up to K = 4096. Two: 3.97 against 3.94 us at M = 1,
 // N = K = 4096, 7.90 against 6.84 at M = 8, 4.59 against 3.68 at 2880 x 2880 (profiles/mxfp4/ab_mxfp4_units.txt).
-#ifndef QG_MXFP4_UNIT_BLOCKS
-#define QG_MXFP4_UNIT_BLOCKS 1
-#endif
 constexpr int MXFP4_UB = QG_MXFP4_UNIT_BLOCKS;
 constexpr int MXFP4_UNIT_DW = MXFP4_UB * MXFP4_COVER_DW;  // raw dwords of a unit: a cover per block
 
 // Decode GEMV (M <= 8): see qg_mxfp4_gemv.hip. LDS per (token, block): the 8 qs dwords, d_a as fp32, 3 pad dwords
 // (12 = 4 x odd: the 16-B reads of lanes on consecutive blocks hit distinct bank groups).
-constexpr int MXFP4_REC_DW = 12;
+constexpr int MXFP4_REC_DW = weight_type(QG_TYPE_MXFP4).rec_dw;
 
 // MFMA prefill (M >= 9): see qg_mxfp4_mmq.hip. The activation staging in LDS, by groups of 8 blocks as the super-block
 // kernels' (the last group of a row may be partial).

@@ -49,13 +49,9 @@ __global__ __launch_bounds__(WGS) void mxfp4_gemv_kernel(const uint32_t* __restr
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct mxfp4_gemv_fmt {
-    static constexpr int REC_ELEMS = QK, REC_DW = MXFP4_REC_DW, UNIT = QK * MXFP4_UB;
-    static constexpr uintptr_t WMASK = 0;  // any byte: every load is realigned
+    static constexpr int WT = QG_TYPE_MXFP4;
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return mxfp4_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
-    }
-    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
-        describe_kernel(g, "mxfp4_gemv MT=%d LPR=%d WGS=%d ONE=%d grid=%d lds=%zu", MT, LPR, WGS, one, grid, lds);
     }
 };
 

@@ -110,9 +110,7 @@ __global__ __launch_bounds__(MXFP4_MMQ_WGS) void mxfp4_mmq_kernel(const uint32_t
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct mxfp4_mmq_fmt {
-    static constexpr const char* NAME = "mxfp4_mmq";
-    static constexpr int WAVES = MXFP4_MMQ_WAVES, KMULT = QK;
-    static constexpr uintptr_t WMASK = 0;  // any byte: every load is realigned
+    static constexpr int WT = QG_TYPE_MXFP4, WAVES = MXFP4_MMQ_WAVES;
     template <int TT, int RG, bool SUMI> static auto kernel() { return mxfp4_mmq_kernel<TT, RG, SUMI>; }
 };
 

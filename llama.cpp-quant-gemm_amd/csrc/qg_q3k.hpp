@@ -30,11 +30,12 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 #include "qg_q6k.hpp"
 
 namespace qg {
 
-constexpr int Q3K_BYTES = 110;
+constexpr int Q3K_BYTES = weight_type(QG_TYPE_Q3_K).bytes;
 constexpr int Q3K_QS = 32, Q3K_SC = 96;  // field offsets (hmask at 0; d follows the scales: one span holds both)
 
 // The sixteen 6-bit scales sc_g (0..63, the bias of 32 still on) from the three dwords of scales[12], four per dword:
@@ -86,7 +87,7 @@ __device__ __forceinline__ uint32_t q3k_lookup(uint32_t u, uint32_t lo, uint32_t
 constexpr int Q3K_UNIT_DW = 22;
 // LDS per (token, super-block): the 8 blocks' qs dwords (64), their d_a as fp32 (8), 4 pad dwords: 76 = 4 x 19, and 19
 // is odd, so the 16-B reads of lanes on consecutive super-blocks start in distinct bank groups (as Q6_K's record).
-constexpr int Q3K_REC_DW = 76;
+constexpr int Q3K_REC_DW = weight_type(QG_TYPE_Q3_K).rec_dw;
 
 // MFMA prefill (M >= 7): see qg_q3k_mmq.hip. The activation staging in LDS, as the other prefills'.
 constexpr int Q3K_TOK_DW = 72;                // one token's 8 blocks of a super-block: 288 B

@@ -44,13 +44,9 @@ __global__ __launch_bounds__(WGS) void q3k_gemv_kernel(const uint32_t* __restric
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q3k_gemv_fmt {
-    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = Q3K_REC_DW, UNIT = 64;
-    static constexpr uintptr_t WMASK = 1;  // 110-B super-blocks: every load is realigned
+    static constexpr int WT = QG_TYPE_Q3_K;
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return q3k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
-    }
-    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
-        describe_kernel(g, "q3k_gemv MT=%d LPR=%d WGS=%d ONE=%d grid=%d lds=%zu", MT, LPR, WGS, one, grid, lds);
     }
 };
 

@@ -109,9 +109,7 @@ __global__ __launch_bounds__(Q3K_MMQ_WGS) void q3k_mmq_kernel(const uint32_t* __
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q3k_mmq_fmt {
-    static constexpr const char* NAME = "q3k_mmq";
-    static constexpr int WAVES = Q3K_MMQ_WAVES, KMULT = SB_ELEMS;
-    static constexpr uintptr_t WMASK = 1;  // 110-B super-blocks: every load is realigned
+    static constexpr int WT = QG_TYPE_Q3_K, WAVES = Q3K_MMQ_WAVES;
     template <int TT, int RG, bool SUMI> static auto kernel() { return q3k_mmq_kernel<TT, RG, SUMI>; }
 };
 

@@ -12,10 +12,11 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 
 namespace qg {
 
-constexpr int Q4K_BYTES = 144;
+constexpr int Q4K_BYTES = weight_type(QG_TYPE_Q4_K).bytes;
 constexpr int Q4K_DW = 36;
 
 // The eight scales and eight mins of one super-block, four bytes per dword:
@@ -38,7 +39,7 @@ template <int J> __host__ __device__ __forceinline__ int q4k_byte(const uint32_t
 
 // Decode GEMV (M <= 8): see qg_q4k_gemv.hip. LDS per (token, super-block): 64 qs dwords, 8 x (d_a, s_a) fp32,
 // 4 pad dwords (84 = 4 x odd: the 16-B reads of lanes on consecutive super-blocks hit distinct bank groups).
-constexpr int Q4K_REC_DW = 84;
+constexpr int Q4K_REC_DW = weight_type(QG_TYPE_Q4_K).rec_dw;
 constexpr int Q4K_UNIT_DW = 12;  // a lane's unit: header (4) + one chunk's qs (8)
 
 // Weight loads: plain, as the row GEMV's product instantiations (NT = false there). 1 (A/B builds): the

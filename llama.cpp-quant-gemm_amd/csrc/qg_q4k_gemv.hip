@@ -47,14 +47,10 @@ __global__ __launch_bounds__(WGS) void q4k_gemv_kernel(const uint32_t* __restric
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q4k_gemv_fmt {
-    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = Q4K_REC_DW, UNIT = 64;
-    static constexpr uintptr_t WMASK = 15;  // the 16-B loads
+    static constexpr int WT = QG_TYPE_Q4_K;
+    static constexpr int NT = QG_Q4K_NT;  // named in the config line
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return q4k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
-    }
-    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
-        describe_kernel(g, "q4k_gemv MT=%d LPR=%d WGS=%d ONE=%d NT=%d grid=%d lds=%zu", MT, LPR, WGS, one, QG_Q4K_NT, grid,
-                        lds);
     }
 };
 

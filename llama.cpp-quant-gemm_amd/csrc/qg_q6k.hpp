@@ -23,10 +23,11 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 
 namespace qg {
 
-constexpr int Q6K_BYTES = 210;
+constexpr int Q6K_BYTES = weight_type(QG_TYPE_Q6_K).bytes;
 constexpr int Q6K_QH = 128, Q6K_SC = 192, Q6K_D = 208;  // field offsets
 
 // NDW dwords of a byte stream that starts at the 2-B aligned address p: NDW + 1 aligned dwords from p & ~3 (pa below),
@@ -56,15 +57,12 @@ template <int C> __device__ __forceinline__ uint32_t q6k_codes(uint32_t a, uint3
 // QG_Q6K_ASUM (A/B builds): how the decode GEMV takes the 32 off the codes. 0: per byte, once per unit (q6k_sub32).
 // 1: the dot runs on the unsigned codes and 32 x the activations' sum over the 16 elements, an exact integer staged
 // with the LDS record, is subtracted per token.
-#ifndef QG_Q6K_ASUM
-#define QG_Q6K_ASUM 0
-#endif
 __device__ __forceinline__ uint32_t q6k_signed(uint32_t u) { return QG_Q6K_ASUM ? u : q6k_sub32(u); }
 
 // Decode GEMV (M <= 8): see qg_q6k_gemv.hip. LDS per (token, super-block): the 8 blocks' qs dwords (64), their d_a
 // as fp32 (8), with QG_Q6K_ASUM the 16 half-block sums x 32 (16), 4 pad dwords (76 / 92 = 4 x odd: the 16-B reads
 // of lanes on consecutive super-blocks hit distinct bank groups).
-constexpr int Q6K_REC_DW = QG_Q6K_ASUM ? 92 : 76;
+constexpr int Q6K_REC_DW = weight_type(QG_TYPE_Q6_K).rec_dw;
 // raw dwords of a unit: the ql and qh pieces (9 each: 32 bytes + the realignment dword), the half's scales (3), d (1)
 constexpr int Q6K_UNIT_DW = 22;
 

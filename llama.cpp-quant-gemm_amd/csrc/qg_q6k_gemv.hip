@@ -59,13 +59,9 @@ __global__ __launch_bounds__(WGS) void q6k_gemv_kernel(const uint32_t* __restric
 
 // instantiation choice, launch and eligibility: qg_kq_launch.hpp
 struct q6k_gemv_fmt {
-    static constexpr int REC_ELEMS = SB_ELEMS, REC_DW = Q6K_REC_DW, UNIT = 64;
-    static constexpr uintptr_t WMASK = 1;  // every load is realigned
+    static constexpr int WT = QG_TYPE_Q6_K;
     template <int MT, int LPR, int WGS, bool SUMI, bool ONE> static auto kernel() {
         return q6k_gemv_kernel<MT, LPR, WGS, SUMI, ONE>;
-    }
-    static void describe(const GemmArgs& g, int MT, int LPR, int WGS, int one, int grid, size_t lds) {
-        describe_kernel(g, "q6k_gemv MT=%d LPR=%d WGS=%d ONE=%d grid=%d lds=%zu", MT, LPR, WGS, one, grid, lds);
     }
 };
 

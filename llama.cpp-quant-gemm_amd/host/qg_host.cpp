@@ -22,6 +22,7 @@
 #include "../../include/qg/blocks.h"
 #include "../../include/qg/qg.h"
 #include "../../include/qg/qg_host.h"
+#include "../csrc/qg_types.hpp"
 
 namespace {
 
@@ -47,7 +48,7 @@ struct ActBlock {
 // Weight formats. `value(p, e)` is element e's stored integer (no offset removed), `term` the
 // per-block fp32 formula in the reference's operation order (see qg_common.hpp's header).
 struct FmtQ4_0 {
-    static constexpr int bytes = 18;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q4_0).bytes;
     static int value(const uint8_t* p, int e) { return e < 16 ? (p[2 + e] & 0x0F) : (p[2 + e - 16] >> 4); }
     static float term(const uint8_t* p, int32_t sumi, const ActBlock& a) {
         const float dw = half_to_float(p);
@@ -55,7 +56,7 @@ struct FmtQ4_0 {
     }
 };
 struct FmtQ4_1 {
-    static constexpr int bytes = 20;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q4_1).bytes;
     static int value(const uint8_t* p, int e) { return e < 16 ? (p[4 + e] & 0x0F) : (p[4 + e - 16] >> 4); }
     static float term(const uint8_t* p, int32_t sumi, const ActBlock& a) {
         const float dw = half_to_float(p), mw = half_to_float(p + 2);
@@ -69,7 +70,7 @@ template <int QH, int QS> inline int q5_value(const uint8_t* p, int e) {
     return nib | (int)(((qh >> e) & 1u) << 4);
 }
 struct FmtQ5_0 {
-    static constexpr int bytes = 22;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q5_0).bytes;
     static int value(const uint8_t* p, int e) { return q5_value<2, 6>(p, e); }
     static float term(const uint8_t* p, int32_t sumi, const ActBlock& a) {
         const float dw = half_to_float(p);
@@ -77,7 +78,7 @@ struct FmtQ5_0 {
     }
 };
 struct FmtQ5_1 {
-    static constexpr int bytes = 24;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q5_1).bytes;
     static int value(const uint8_t* p, int e) { return q5_value<4, 8>(p, e); }
     static float term(const uint8_t* p, int32_t sumi, const ActBlock& a) {
         const float dw = half_to_float(p), mw = half_to_float(p + 2);
@@ -85,7 +86,7 @@ struct FmtQ5_1 {
     }
 };
 struct FmtQ8_0 {
-    static constexpr int bytes = 34;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q8_0).bytes;
     static int value(const uint8_t* p, int e) { return (int)(int8_t)p[2 + e]; }
     static float term(const uint8_t* p, int32_t sumi, const ActBlock& a) {
         const float dw = half_to_float(p);
@@ -121,7 +122,7 @@ template <class F> void gemm_rows(const uint8_t* A, const uint8_t* B, float* C, 
 // 8 sb + j). The product contract of qg.h, in the decode GEMV's operation order: per super-block one fp32 dot
 // accumulator and one min accumulator in sub-block order, d and dmin applied once, super-blocks summed in order.
 struct FmtQ4_K {
-    static constexpr int bytes = 144;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q4_K).bytes;
     static void scale_min(const uint8_t* q, int j, int& sc, int& m) {
         if (j < 4) {
             sc = q[j] & 63;
@@ -163,7 +164,7 @@ void gemm_rows<FmtQ4_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int
 // scale groups 2b and 2b + 1). The product contract of qg.h: isum = scales[2b] * s0 + scales[2b + 1] * s1 in int32,
 // one fp32 accumulator per super-block in block order, d applied once, super-blocks summed in order.
 struct FmtQ6_K {
-    static constexpr int bytes = 210;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q6_K).bytes;
     // the signed code of element 32b + l of a super-block (b = 4h + c)
     static int value(const uint8_t* w, int b, int l) {
         const int h = b >> 2, c = b & 3;
@@ -203,7 +204,7 @@ void gemm_rows<FmtQ6_K>(const uint8_t* A, const uint8_t* B, float* C, int M, int
 // contract of qg.h: sumi in int32, (ls_j - 32) * sumi in int32, one fp32 accumulator per super-block in sub-block
 // order, d applied once, super-blocks summed in order.
 struct FmtIQ4_XS {
-    static constexpr int bytes = 136;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_IQ4_XS).bytes;
     // kv[code] of element l (0..31) of sub-block j
     static int value(const uint8_t* w, int j, int l) {
         static const int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
@@ -243,7 +244,7 @@ void gemm_rows<FmtIQ4_XS>(const uint8_t* A, const uint8_t* B, float* C, int M, i
 // scale groups 2b and 2b + 1). The product contract of qg.h: isum = s_2b * s0 + s_2b+1 * s1 in int32, one fp32
 // accumulator per super-block in block order, d applied once, super-blocks summed in order.
 struct FmtQ3_K {
-    static constexpr int bytes = 110;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_Q3_K).bytes;
     // the signed code of element 32b + l of a super-block (b = 4h + j)
     static int value(const uint8_t* w, int b, int l) {
         const int lo2 = (w[32 + 32 * (b >> 2) + l] >> (2 * (b & 3))) & 3;
@@ -354,7 +355,7 @@ class Pool {
 // product contract of qg.h: sumi in int32, (d_a * scale(e)) * float(sumi) per block, one fp32 accumulator per output,
 // blocks in order.
 struct FmtMXFP4 {
-    static constexpr int bytes = 17;
+    static constexpr int bytes = qg::weight_type(QG_TYPE_MXFP4).bytes;
     static int value(const uint8_t* p, int e) {
         static const int8_t kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
         return kv[e < 16 ? (p[1 + e] & 0x0F) : (p[1 + e - 16] >> 4)];
@@ -405,6 +406,32 @@ int check_gemm(const void* A, const void* B, const float* C, int M, int N, int K
     return QG_OK;
 }
 
+// The one place that names the ten formats: fn(Fmt{}) for wtype; false for an id without one.
+template <class Fn> bool with_fmt(int wtype, Fn&& fn) {
+    switch (wtype) {
+        case QG_TYPE_Q4_0: fn(FmtQ4_0{}); return true;
+        case QG_TYPE_Q4_1: fn(FmtQ4_1{}); return true;
+        case QG_TYPE_Q5_0: fn(FmtQ5_0{}); return true;
+        case QG_TYPE_Q5_1: fn(FmtQ5_1{}); return true;
+        case QG_TYPE_Q8_0: fn(FmtQ8_0{}); return true;
+        case QG_TYPE_Q3_K: fn(FmtQ3_K{}); return true;
+        case QG_TYPE_Q4_K: fn(FmtQ4_K{}); return true;
+        case QG_TYPE_Q6_K: fn(FmtQ6_K{}); return true;
+        case QG_TYPE_IQ4_XS: fn(FmtIQ4_XS{}); return true;
+        case QG_TYPE_MXFP4: fn(FmtMXFP4{}); return true;
+    }
+    return false;
+}
+
+// wtype as an entry of class cls (csrc/qg_types.hpp) sees it: the bytes of a block and the elements it holds; 0 bytes: not
+// a type of the entry, checked at the 32-element granule
+int entry_block(int wtype, unsigned cls, int& elems) {
+    const qg::WeightType w = qg::weight_type(wtype);
+    const bool taken = (w.entries & cls) != 0;
+    elems = taken ? w.elems : QK;
+    return taken ? w.bytes : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -412,49 +439,26 @@ extern "C" {
 int qg_gemm_w4a8_cpu_mt(const void* A, const void* B, float* C, int M, int N, int K, int wtype, int threads) {
     const int rc = check_gemm(A, B, C, M, N, K);
     if (rc != QG_OK) return rc;
-    if ((wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K) && K % 256 != 0)
-        return QG_ERR_BAD_K;
+    const qg::WeightType w = qg::weight_type(wtype);
+    if (w.routed && K % w.elems != 0) return QG_ERR_BAD_K;
     if (M == 0 || N == 0) return QG_OK;
-    switch (wtype) {
-        case QG_TYPE_Q4_K: gemm_threads<FmtQ4_K>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q6_K: gemm_threads<FmtQ6_K>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_IQ4_XS: gemm_threads<FmtIQ4_XS>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q3_K: gemm_threads<FmtQ3_K>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_MXFP4: gemm_threads<FmtMXFP4>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q4_0: gemm_threads<FmtQ4_0>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q4_1: gemm_threads<FmtQ4_1>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q5_0: gemm_threads<FmtQ5_0>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q5_1: gemm_threads<FmtQ5_1>(A, B, C, M, N, K, threads); return QG_OK;
-        case QG_TYPE_Q8_0: gemm_threads<FmtQ8_0>(A, B, C, M, N, K, threads); return QG_OK;
-    }
-    return QG_ERR_UNSUPPORTED;
+    const bool known = with_fmt(wtype, [&](auto fmt) { gemm_threads<decltype(fmt)>(A, B, C, M, N, K, threads); });
+    return known ? QG_OK : QG_ERR_UNSUPPORTED;
 }
 
 int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
                          float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
-    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K || wtype == QG_TYPE_IQ4_XS || wtype == QG_TYPE_Q3_K;
-    int bb = 0;
-    switch (wtype) {
-        case QG_TYPE_Q4_0: bb = FmtQ4_0::bytes; break;
-        case QG_TYPE_Q4_1: bb = FmtQ4_1::bytes; break;
-        case QG_TYPE_Q5_0: bb = FmtQ5_0::bytes; break;
-        case QG_TYPE_Q5_1: bb = FmtQ5_1::bytes; break;
-        case QG_TYPE_Q8_0: bb = FmtQ8_0::bytes; break;
-        case QG_TYPE_Q4_K: bb = FmtQ4_K::bytes; break;
-        case QG_TYPE_Q6_K: bb = FmtQ6_K::bytes; break;
-        case QG_TYPE_IQ4_XS: bb = FmtIQ4_XS::bytes; break;
-        case QG_TYPE_Q3_K: bb = FmtQ3_K::bytes; break;
-        case QG_TYPE_MXFP4: bb = FmtMXFP4::bytes; break;
-    }
+    int be;
+    const int bb = entry_block(wtype, qg::IN_MOE, be);
     // the order of qg_gemm_w4a8_moe
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % (ksb ? 256 : QK) != 0) return QG_ERR_BAD_K;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
     if (!bb) return QG_ERR_UNSUPPORTED;
     if (T == 0 || n_used == 0 || N == 0) return QG_OK;
     if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
     if ((a_rows != 1 && a_rows != n_used) || ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N))
         return QG_ERR_INVALID_ARG;
-    const size_t arow = (size_t)(K / QK) * 36, estride = (size_t)N * (size_t)(K / (ksb ? 256 : QK)) * (size_t)bb;
+    const size_t arow = (size_t)(K / QK) * 36, estride = (size_t)N * (size_t)(K / be) * (size_t)bb;
     if (ldc == 0) ldc = N;
     for (int t = 0; t < T; ++t)
         for (int u = 0; u < n_used; ++u) {
@@ -474,17 +478,18 @@ int qg_gemm_w4a8_moe_cpu(const void* A, int a_rows, const void* B, int n_expert,
 int qg_gemm_w4a8_moe_glu_cpu(const void* A, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op,
                              int threads) {
-    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    int be;
+    const int bb = entry_block(wtype, qg::IN_MOE_PLAIN, be);
     // the order of qg_gemm_w4a8_moe_glu
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % (ksb ? 256 : QK) != 0) return QG_ERR_BAD_K;
-    if (!ksb) return QG_ERR_UNSUPPORTED;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
     if (T == 0 || n_used == 0 || N == 0) return QG_OK;
     if (!A || !B_gate || !B_up || !ids || !C) return QG_ERR_INVALID_ARG;
     if (ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N)) return QG_ERR_INVALID_ARG;
     if (glu_op != QG_GLU_REGLU && glu_op != QG_GLU_SWIGLU) return QG_ERR_UNSUPPORTED;
     const size_t arow = (size_t)(K / QK) * 36;
-    const size_t estride = (size_t)N * (size_t)(K / 256) * (size_t)(wtype == QG_TYPE_Q4_K ? FmtQ4_K::bytes : FmtQ6_K::bytes);
+    const size_t estride = (size_t)N * (size_t)(K / be) * (size_t)bb;
     if (ldc == 0) ldc = N;
     std::vector<float> g((size_t)N), up((size_t)N);
     for (int t = 0; t < T; ++t)
@@ -512,17 +517,18 @@ int qg_gemm_w4a8_moe_glu_cpu(const void* A, const void* B_gate, const void* B_up
 int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
                               const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
                               int wtype, int threads) {
-    const bool ksb = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    int be;
+    const int bb = entry_block(wtype, qg::IN_MOE_PLAIN, be);
     // the order of qg_gemm_w4a8_moe_down
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
-    if (K <= 0 || K % (ksb ? 256 : QK) != 0) return QG_ERR_BAD_K;
-    if (!ksb) return QG_ERR_UNSUPPORTED;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
     if (T == 0 || n_used == 0 || N == 0) return QG_OK;
     if (!A || !B || !ids || !C) return QG_ERR_INVALID_ARG;
     if (ids_stride < n_used || n_expert < 1 || ldc < 0 || (ldc > 0 && ldc < N) || (weights && w_stride < n_used))
         return QG_ERR_INVALID_ARG;
     const size_t arow = (size_t)(K / QK) * 36;
-    const size_t estride = (size_t)N * (size_t)(K / 256) * (size_t)(wtype == QG_TYPE_Q4_K ? FmtQ4_K::bytes : FmtQ6_K::bytes);
+    const size_t estride = (size_t)N * (size_t)(K / be) * (size_t)bb;
     if (ldc == 0) ldc = N;
     std::vector<float> d((size_t)N);
     for (int t = 0; t < T; ++t) {
@@ -542,26 +548,12 @@ int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const 
     return QG_OK;
 }
 
-namespace {
-// the two _bias twins: Q4_K / Q6_K / MXFP4, the bytes of a block and the elements it holds (0: not a type of theirs)
-int bias_block(int wtype, int& elems) {
-    elems = wtype == QG_TYPE_MXFP4 ? QK : 256;
-    switch (wtype) {
-        case QG_TYPE_Q4_K: return FmtQ4_K::bytes;
-        case QG_TYPE_Q6_K: return FmtQ6_K::bytes;
-        case QG_TYPE_MXFP4: return FmtMXFP4::bytes;
-    }
-    elems = QK;
-    return 0;
-}
-}  // namespace
-
 int qg_gemm_w4a8_moe_glu_bias_cpu(const void* A, const void* B_gate, const void* B_up, const float* bias_gate,
                                   const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids,
                                   int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                                   int glu_op, float alpha, float limit, int threads) {
     int be;
-    const int bb = bias_block(wtype, be);
+    const int bb = entry_block(wtype, qg::IN_MOE_BIAS, be);
     // the order of qg_gemm_w4a8_moe_glu_bias
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
     if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
@@ -611,7 +603,7 @@ int qg_gemm_w4a8_moe_down_bias_cpu(const void* A, const void* B, const float* bi
                                    const int32_t* ids, int64_t ids_stride, const float* weights, int64_t w_stride, float* C,
                                    int64_t ldc, int T, int n_used, int N, int K, int wtype, int threads) {
     int be;
-    const int bb = bias_block(wtype, be);
+    const int bb = entry_block(wtype, qg::IN_MOE_BIAS, be);
     // the order of qg_gemm_w4a8_moe_down_bias
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
     if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
@@ -648,7 +640,7 @@ int qg_gemm_w4a8_moe_bias_cpu(const void* A, int a_rows, const void* B, const fl
                               const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
                               int wtype, int threads) {
     int be;
-    const int bb = bias_block(wtype, be);
+    const int bb = entry_block(wtype, qg::IN_MOE_BIAS, be);
     // the order of qg_gemm_w4a8_moe_prefill_bias / _moe_batch_bias (no workspace here)
     if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
     if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;

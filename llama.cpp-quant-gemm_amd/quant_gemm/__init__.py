@@ -30,14 +30,7 @@ QK8_1 = 32
 BLOCK_Q4_0_BYTES = 18
 BLOCK_Q8_1_BYTES = 36
 
-# ggml_type ids (compat/ggml_types.h:199-215)
-Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 2, 3, 6, 7, 8, 9
-Q3_K = 11  # 256-element super-blocks of 110 bytes, 3-bit codes (qg.h "Q3_K weights")
-Q4_K = 12  # 256-element super-blocks of 144 bytes (qg.h "Q4_K weights")
-Q6_K = 14  # 256-element super-blocks of 210 bytes (qg.h "Q6_K weights")
-IQ4_XS = 23  # 256-element super-blocks of 136 bytes, 4-bit codes into a table (qg.h "IQ4_XS weights")
-MXFP4 = 39  # 32-element blocks of 17 bytes: an E8M0 scale byte and E2M1 codes (qg.h "MXFP4 weights")
-BLOCK_BYTES = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210, IQ4_XS: 136, Q3_K: 110, MXFP4: 17}
+from ._types import BLOCK_BYTES, IQ4_XS, MXFP4, Q3_K, Q4_0, Q4_1, Q4_K, Q5_0, Q5_1, Q6_K, Q8_0, Q8_1  # noqa: E402,F401
 GLU_REGLU, GLU_SWIGLU = 0, 2  # QG_GLU_* (numbered as ggml_glu_op): the ops of gemm_w4a8_moe_glu
 GLU_SWIGLU_OAI = 3  # gpt-oss's clamped SwiGLU: gemm_w4a8_moe_glu_bias alone
 ALGO_AUTO, ALGO_GEMV, ALGO_MFMA, ALGO_GENERIC, ALGO_RAGGED = 0, 1, 2, 3, 4

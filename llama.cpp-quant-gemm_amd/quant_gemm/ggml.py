@@ -18,14 +18,8 @@ import torch
 
 from . import _lib
 
-F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
-Q4_K, Q6_K = 12, 14
-IQ4_XS = 23
-Q3_K = 11
-MXFP4 = 39
-I32 = 26  # the ids of mul_mat_id_from_ggml
-_BB = {Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_0: 34, Q8_1: 36, Q4_K: 144, Q6_K: 210, IQ4_XS: 136, Q3_K: 110, MXFP4: 17}
-_BE = {Q4_K: 256, Q6_K: 256, IQ4_XS: 256, Q3_K: 256}  # elements per block where it is not 32 (qg_block_elems)
+from ._types import BLOCK_BYTES as _BB, BLOCK_ELEMS as _BE  # noqa: F401
+from ._types import F16, F32, I32, IQ4_XS, MXFP4, Q3_K, Q4_0, Q4_1, Q4_K, Q5_0, Q5_1, Q6_K, Q8_0, Q8_1  # noqa: F401
 # the block types the GGUF reader serves (its own list: a Q6_K tensor is listed, not readable); views of bytes the
 # caller loaded (view_of) take every type of _BB
 _GGUF_BB = {t: bb for t, bb in _BB.items() if t != Q6_K}
@@ -38,7 +32,7 @@ class TensorView(ctypes.Structure):
 
 def view_of(t: torch.Tensor, qtype: int, k: int) -> TensorView:
     """ggml-ordered view of a dense row-major tensor holding rows of K elements of ``qtype``."""
-    row = k * 4 if qtype == F32 else k * 2 if qtype == F16 else (k // _BE.get(qtype, 32)) * _BB[qtype]
+    row = k * 4 if qtype == F32 else k * 2 if qtype == F16 else (k // _BE[qtype]) * _BB[qtype]
     rows = t.numel() * t.element_size() // row
     v = TensorView()
     v.data, v.type = t.data_ptr(), qtype
@@ -189,7 +183,7 @@ class GGUFTensor:
         while len(dims) > 1 and dims[0] == 1:
             dims = dims[1:]
         if self.type in _GGUF_BB:
-            return tuple(dims[:-1]) + (dims[-1] // _BE.get(self.type, 32), _GGUF_BB[self.type])
+            return tuple(dims[:-1]) + (dims[-1] // _BE[self.type], _GGUF_BB[self.type])
         return tuple(dims)
 
     def __repr__(self) -> str:

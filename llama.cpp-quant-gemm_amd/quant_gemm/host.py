@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from ._types import BLOCK_BYTES, BLOCK_ELEMS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libqg_host.so")
 P, I, I64, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
@@ -31,8 +33,6 @@ SIGNATURES = {
     "qg_dequantize_row_mxfp4_cpu": ([P, P, I64], I),
     "qg_fill_step4_cpu": ([ctypes.c_uint, I, I, I, I, I, P, P], I),
 }
-# 11: Q3_K, 12: Q4_K, 14: Q6_K, 23: IQ4_XS, 256-element super-blocks; 39: MXFP4, 32-element blocks of 17 bytes
-BLOCK_BYTES = {2: 18, 3: 20, 6: 22, 7: 24, 8: 34, 9: 36, 11: 110, 12: 144, 14: 210, 23: 136, 39: 17}
 GLU_REGLU, GLU_SWIGLU, GLU_SWIGLU_OAI = 0, 2, 3  # QG_GLU_* of qg.h
 _lib = None
 
@@ -107,7 +107,7 @@ def gemm_w4a8_moe(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, t: in
     stride defaults to the array's row length); an id outside [0, n_expert) gives zeros."""
     a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
     ids = np.ascontiguousarray(ids, np.int32)
-    be = 256 if wtype in (11, 12, 14, 23) else 32
+    be = BLOCK_ELEMS[wtype]
     n_expert = experts_q.size // (n * (k // be) * BLOCK_BYTES[wtype])
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used
@@ -127,7 +127,7 @@ def gemm_w4a8_moe_glu(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, ids
     ids = np.ascontiguousarray(ids, np.int32)
     if gate_q.size != up_q.size:
         raise RuntimeError("gemm_w4a8_moe_glu_cpu: gate and up experts differ in size")
-    n_expert = gate_q.size // (n * (k // 256) * BLOCK_BYTES[wtype])
+    n_expert = gate_q.size // (n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used
     c = np.empty((t, n_used, n), np.float32)
@@ -145,7 +145,7 @@ def gemm_w4a8_moe_down(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, 
     arrays' row lengths); a slot whose id is outside [0, n_expert) contributes nothing and its weight is not read."""
     a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
     ids = np.ascontiguousarray(ids, np.int32)
-    n_expert = experts_q.size // (n * (k // 256) * BLOCK_BYTES[wtype])
+    n_expert = experts_q.size // (n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used
     if weights is not None:
@@ -176,7 +176,7 @@ def gemm_w4a8_moe_bias(a_q: np.ndarray, experts_q: np.ndarray, bias: np.ndarray 
     bias row (float32 [n_expert, >= n], or None: no add) added to every slot with a valid id."""
     a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
     ids = np.ascontiguousarray(ids, np.int32)
-    n_expert = experts_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    n_expert = experts_q.size // (n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
     b, sb = _bias(bias, n_expert, n, "gemm_w4a8_moe_bias_cpu")
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used
@@ -197,7 +197,7 @@ def gemm_w4a8_moe_glu_bias(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray
     ids = np.ascontiguousarray(ids, np.int32)
     if gate_q.size != up_q.size:
         raise RuntimeError("gemm_w4a8_moe_glu_bias_cpu: gate and up experts differ in size")
-    n_expert = gate_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    n_expert = gate_q.size // (n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
     bg, sg = _bias(bias_gate, n_expert, n, "gemm_w4a8_moe_glu_bias_cpu")
     bu, su = _bias(bias_up, n_expert, n, "gemm_w4a8_moe_glu_bias_cpu")
     if bg is not None and bu is not None and sg != su:
@@ -219,7 +219,7 @@ def gemm_w4a8_moe_down_bias(a_q: np.ndarray, experts_q: np.ndarray, bias: np.nda
     [n_expert, >= n], or None) added to every product ahead of the fold, and Q4_K / Q6_K / MXFP4 experts."""
     a_q, experts_q = np.ascontiguousarray(a_q), np.ascontiguousarray(experts_q)
     ids = np.ascontiguousarray(ids, np.int32)
-    n_expert = experts_q.size // (n * (k // (32 if wtype == 39 else 256)) * BLOCK_BYTES[wtype])
+    n_expert = experts_q.size // (n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
     b, sb = _bias(bias, n_expert, n, "gemm_w4a8_moe_down_bias_cpu")
     if ids_stride is None:
         ids_stride = ids.size // t if t else n_used

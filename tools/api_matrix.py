@@ -17,8 +17,12 @@ The library is driven in a fresh child process with no device visible (HIP_VISIB
 asks the HIP runtime for the device count first and, if it sees one, runs only the launch-free dispatch half:
 a validation regression must show up as a wrong code, never as a kernel launched on a made-up address.
 
-  api_matrix.py --record LIB          write tests/golden/api_matrix.json (the committed grid) from LIB
-  api_matrix.py --check LIB           replay the committed grid against LIB, print the differing cases
+The cases are kept in two fixtures: "base" (tests/golden/api_matrix.json: the 32-element types and Q4_K) and "types"
+(tests/golden/api_matrix_types.json: Q3_K, Q6_K, IQ4_XS and MXFP4 through the same queries and entries, the mul_mat_id
+entries, and every weight id against every entry that takes one).
+
+  api_matrix.py --record LIB [--fixture base|types]   write the fixture (the committed grid) from LIB
+  api_matrix.py --check LIB           replay both committed grids against LIB, print the differing cases
   api_matrix.py --compare A.so B.so   run the full grid live against both, print the differing cases
 """
 from __future__ import annotations
@@ -35,12 +39,18 @@ import sys
 import zlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(REPO, "tests", "golden", "api_matrix.json")
+GOLDENS = {"base": os.path.join(REPO, "tests", "golden", "api_matrix.json"),
+           "types": os.path.join(REPO, "tests", "golden", "api_matrix_types.json")}
 
 ERR_HIP = -5
 TYPES = [2, 3, 6, 7, 8, 12, 9, 99]  # the weight formats, Q4_K, Q8_1 (not a weight format), an unknown id
 W32 = (2, 3, 6, 7, 8)
 ALGOS = [0, 1, 2, 3, 4]
+# The types with a route of their own, as qg.h documents them: K granule, weight-pointer alignment (activations: 4 B).
+ROUTED = {12: (256, 16), 14: (256, 2), 11: (256, 2), 23: (256, 8), 39: (32, 0)}
+NEW_TYPES = (11, 14, 23, 39)  # the "types" fixture's share of them
+# every weight id qg.h names (F32, F16 and I32 among them: never a weight format), and an unknown one
+ALL_IDS = (0, 1, 2, 3, 6, 7, 8, 9, 11, 12, 14, 23, 26, 39, 99)
 
 # ---- the grids -------------------------------------------------------------------------------------------
 FULL = dict(M=[0, 1, 2, 3, 4, 5, 8, 9, 16, 32, 33, 64, 65, 128, 512], N=[1, 31, 64, 4000, 4096, 11008, 32000],
@@ -49,12 +59,14 @@ FULL = dict(M=[0, 1, 2, 3, 4, 5, 8, 9, 16, 32, 33, 64, 65, 128, 512], N=[1, 31, 
 # and 512 (the large-M kernel's tiles), K/32 odd (288, 4128), K = 4096 | 8192 (one-unit GEMV forms), K/32 = 256 |
 # 257 (8192 | 8224, tiled decode), N = 8192 (row-count split of the GEMV grid) and an N that is no multiple of a tile
 COMMITTED = dict(M=[0, 1, 2, 4, 5, 8, 9, 64, 65, 512], N=[4000, 8192], K=[288, 4096, 4128, 8192, 8224])
+# the "types" fixture: M = 6 | 7 (Q3_K GEMV | MFMA) and 8 | 9 (the others), K = 256 (one super-block), 288 (MXFP4 alone)
+COMMITTED_TYPES = dict(M=[0, 1, 2, 4, 5, 6, 7, 8, 9, 64, 65, 512], N=[4000, 8192], K=[256, 288, 4096, 4128, 8192, 8224])
 
 
-def dispatch_cases(grid):
+def dispatch_cases(grid, types=TYPES):
     """(entry, args) of the launch-free queries; sumi innermost (it must not change the answer)."""
     mnk = list(itertools.product(grid["M"], grid["N"], grid["K"]))
-    for t in TYPES:
+    for t in types:
         for a in ALGOS:
             for m, n, k in mnk:
                 for s in (0, 1):
@@ -75,31 +87,33 @@ def dispatch_cases(grid):
 # w workspace pointer (with `z` its byte count), c element count (int64), q type / v variant of qg_quantize,
 # st stream. `types`: the weight types the entry accepts. `gran`: its K granule for a type.
 class Entry:
-    def __init__(self, name, spec, types=W32, fixed_type=None, q4k=None, ws_need=None, k_free=False):
+    def __init__(self, name, spec, types=W32, fixed_type=None, ws_need=None, k_free=False):
         self.name, self.types, self.fixed_type, self.ws_need, self.k_free = name, types, fixed_type, ws_need, k_free
         self.params = [p.split(":") for p in spec.split()]
-        self.q4k = q4k  # pointer alignments when the type is Q4_K (entries that take it)
+
+    def routed(self, args):  # the call's type is a routed one and the entry takes it: its granule and alignments hold
+        wt = args.get("wtype", self.fixed_type)
+        return wt in ROUTED and wt in self.types
 
     def align(self, pname, args):
-        if self.q4k and args.get("wtype") == 12:
-            return self.q4k.get(pname, 0)
+        if self.routed(args):
+            return {"A": 4, "B": ROUTED[args["wtype"]][1]}.get(pname, 0)
         for p in self.params:
             if p[0] == pname:
                 return int(p[1][1:] or 0)
         return 0
 
     def gran(self, args):
-        return 256 if args.get("wtype", self.fixed_type) == 12 and 12 in self.types else 32
+        return ROUTED[args["wtype"]][0] if self.routed(args) else 32
 
 
 PROD = "A:p0 B:p2 C:p0 M:n N:n K:k"
-Q4K_AL = {"A": 4, "B": 16}
-ALL = W32 + (12,)
+ALL = W32 + tuple(ROUTED)
 ENTRIES = [
-    Entry("qg_gemm_w4a8", PROD + " wtype:t st", ALL, q4k=Q4K_AL),
-    Entry("qg_gemm_w4a8_ex", PROD + " wtype:t algo:a st", ALL, q4k=Q4K_AL),
-    Entry("qg_gemm_w4a8_ldc", PROD + " ldc:l wtype:t algo:a st", ALL, q4k=Q4K_AL),
-    Entry("qg_debug_sumi", PROD + " wtype:t algo:a st", ALL, q4k=Q4K_AL),
+    Entry("qg_gemm_w4a8", PROD + " wtype:t st", ALL),
+    Entry("qg_gemm_w4a8_ex", PROD + " wtype:t algo:a st", ALL),
+    Entry("qg_gemm_w4a8_ldc", PROD + " ldc:l wtype:t algo:a st", ALL),
+    Entry("qg_debug_sumi", PROD + " wtype:t algo:a st", ALL),
     Entry("qg_gemm_q4_0_q8_1_w4a8", PROD + " st", fixed_type=2),
     Entry("qg_gemm_w8a8", PROD + " st", fixed_type=8),
     Entry("qg_gemm_w4a8_strided_batched", "A:p0 sA:s4 B:p2 sB:s2 C:p0 sC:s0 batch:b M:n N:n K:k wtype:t st"),
@@ -125,7 +139,7 @@ ENTRIES = [
     Entry("qg_gemm_w4a16_ws", "A:p4 B:p2 C:p0 M:n N:n K:k ws:w wsb:z st", fixed_type=2),
     Entry("qg_gemm_w8a16_ws", "A:p4 B:p2 C:p0 M:n N:n K:k ws:w wsb:z st", fixed_type=8),
     # fused activation quantization: without a workspace X needs 16 B (qg.h); Q4_K needs the workspace
-    Entry("qg_gemm_w4a8_f32", "A:p16 B:p2 C:p0 M:n N:n K:k wtype:t ws:w wsb:z st", ALL, q4k=Q4K_AL, ws_need="f32"),
+    Entry("qg_gemm_w4a8_f32", "A:p16 B:p2 C:p0 M:n N:n K:k wtype:t ws:w wsb:z st", ALL, ws_need="f32"),
     Entry("qg_gemm_q4_0_fp16_fused", "B:p2 A:p16 C:p0 M:n N:n K:k st", fixed_type=2),
     Entry("qg_gemm_q4_0_fp16_fused_ws", "B:p2 A:p16 C:p0 M:n N:n K:k ws:w wsb:z st", fixed_type=2, ws_need="f32"),
     Entry("qg_gemm_fp32", "A:p4 B:p4 C:p4 M:n N:n K:n st", fixed_type=0, k_free=True),
@@ -181,13 +195,12 @@ def would_launch(e, a):
         return False
     wt = a.get("wtype", a.get("type", e.fixed_type))
     if "type" in a:  # qg_quantize / qg_dequantize
-        ok = (2, 3, 6, 7, 8, 9) if e.name == "qg_quantize" else (2, 3, 6, 7, 8, 9, 12)
-        if wt not in ok:
+        if wt not in (2, 3, 6, 7, 8, 9) + (() if e.name == "qg_quantize" else tuple(ROUTED)):
             return False
-        gran = 256 if wt == 12 else 32
+        gran = ROUTED[wt][0] if wt in ROUTED else 32
         if e.name == "qg_quantize" and a["variant"] not in ((0, 1, 2) if wt == 9 else (0, 2) if wt == 2 else (0,)):
             return False
-        yal = {"y": 4 if wt == 9 else 2} if e.name == "qg_quantize" else {}
+        yal = {"y": 4 if wt == 9 else 2} if e.name == "qg_quantize" else {"x": ROUTED[wt][1] or 1} if wt in (23, 39) else {}
     else:
         if wt not in e.types and e.fixed_type is None:
             return False
@@ -196,7 +209,7 @@ def would_launch(e, a):
     if not e.k_free and (a[kname] <= 0 or a[kname] % gran):
         return False
     if a.get("algo", 0) not in (0,):  # an explicit algo can be refused for the shape: keep those cases out only
-        if wt == 12 and a["algo"] in (3, 4):  # where the refusal is certain
+        if wt in ROUTED and a["algo"] in (3, 4):  # where the refusal is certain
             return False
     for n in names:
         kd = kind_of(e, n)
@@ -214,14 +227,14 @@ def would_launch(e, a):
             return False
         if kd[0] == "s" and n != "st" and a["batch"] > 1 and int(kd[1:]) and a[n] % int(kd[1:]):
             return False
-    if e.ws_need == "f32" and wt == 12 and (a.get("ws", 0) == 0 or a["wsb"] < ws_need(e, a) or a["ws"] % 4):
+    if e.ws_need == "f32" and wt in ROUTED and (a.get("ws", 0) == 0 or a["wsb"] < ws_need(e, a) or a["ws"] % 4):
         return False
     if e.ws_need == "f32" and a.get("ws") and a["ws"] % 4 and a["M"] > 4:
         return False
     return True
 
 
-def defects(e, full):
+def defects(e, full, type_ids=TYPES):
     """Single defects of an entry: (class, {param: value}). Classes order the precedence pairs."""
     out = []
     base = baseline(e)
@@ -235,7 +248,7 @@ def defects(e, full):
         elif kd in ("k", "c"):
             out += [("badk", {name: v}) for v in ((-32, 0, 33, 32, 288) if full else (-32, 0, 33, 288))]
         elif kd in ("t", "q"):
-            out += [("type", {name: t}) for t in (TYPES + [0, 1, 5] if kd == "q" else TYPES) if t != base[name]]
+            out += [("type", {name: t}) for t in (list(type_ids) + [0, 1, 5] if kd == "q" else type_ids) if t != base[name]]
         elif kd == "v":
             out += [("type", {name: v}) for v in (1, 2, 3)]
         elif kd == "a":
@@ -268,14 +281,21 @@ def ws_need(e, a):
     return max(rows, 0) * max(a["K"] // 32, 0) * 36
 
 
-def entry_cases(e, full):
+def entry_cases(e, full, around=None):
+    """around = None: the defects around a 32-element call, a Q4_K call and the workspace shapes; else around a call of
+    each routed type of `around` (the entries that take them), with every named id as the type defect."""
     base = baseline(e)
-    ds = defects(e, full)
-    variants = [base]
-    if e.q4k:  # the same defects around a Q4_K call
-        variants.append(dict(base, wtype=12))
-    if e.ws_need:  # shapes at which the workspace is what decides: K/32 odd, or more rows than the fused GEMV takes
-        variants.append(dict(base, K=288, M=9, wsb="need"))
+    takes_routed = 12 in e.types and "wtype" in base
+    if around is None:
+        ds = defects(e, full)
+        variants = [base]
+        if takes_routed:  # the same defects around a Q4_K call
+            variants.append(dict(base, wtype=12))
+        if e.ws_need:  # shapes at which the workspace is what decides: K/32 odd, or more rows than the fused GEMV takes
+            variants.append(dict(base, K=288, M=9, wsb="need"))
+    else:
+        ds = defects(e, full, ALL_IDS)
+        variants = [dict(base, wtype=t) for t in around] if takes_routed else []
     seen = set()
     for vi, v in enumerate(variants):
         combos = [(d,) for d in ds]
@@ -414,11 +434,163 @@ def call_grouped(lib, spec):
     return lib.qg_gemm_w4a8_grouped(None if null_items else items, top["count"], top["M"], top["K"], top["wtype"], None)
 
 
-def status_cases(full):
+# ---- the mul_mat_id entries: named arguments, one defect at a time and in pairs ---------------------------------
+# name -> (the parameters in call order, the weight types the entry takes); qg.h: qg_gemm_w4a8_moe takes every weight
+# type, the plain expert entries Q4_K / Q6_K, the _bias entries MXFP4 beside them.
+MOE_HEAD = "A a_rows B n_expert ids ids_stride C ldc T n_used N K wtype"
+MOE_BIAS_HEAD = "A a_rows B bias bias_stride n_expert ids ids_stride C ldc T n_used N K wtype"
+MOE_ENTRIES = {
+    "qg_gemm_w4a8_moe": (MOE_HEAD + " st", ALL),
+    "qg_gemm_w4a8_moe_prefill": (MOE_HEAD + " ws wsb st", (12, 14)),
+    "qg_gemm_w4a8_moe_batch": (MOE_HEAD + " ws wsb st", (12, 14)),
+    "qg_gemm_w4a8_moe_glu": ("A B B_up n_expert ids ids_stride C ldc T n_used N K wtype glu_op st", (12, 14)),
+    "qg_gemm_w4a8_moe_down": ("A B n_expert ids ids_stride weights w_stride C ldc T n_used N K wtype st", (12, 14)),
+    "qg_gemm_w4a8_moe_glu_bias": ("A B B_up bias bias_up bias_stride n_expert ids ids_stride C ldc T n_used N K wtype glu_op "
+                                  "alpha limit st", (12, 14, 39)),
+    "qg_gemm_w4a8_moe_down_bias": ("A B bias bias_stride n_expert ids ids_stride weights w_stride C ldc T n_used N K wtype st",
+                                   (12, 14, 39)),
+    "qg_gemm_w4a8_moe_prefill_bias": (MOE_BIAS_HEAD + " ws wsb st", (12, 14, 39)),
+    "qg_gemm_w4a8_moe_batch_bias": (MOE_BIAS_HEAD + " ws wsb st", (12, 14, 39)),
+    "qg_debug_moe_prefill_plan": ("ids ids_stride T n_used n_expert a_rows N K wtype counts sorted ws wsb st", (12, 14)),
+}
+MOE_GOOD = dict(A=1 << 12, a_rows=1, B=1 << 20, B_up=1 << 21, n_expert=4, ids=1 << 22, ids_stride=2, weights=1 << 23, w_stride=2,
+                C=1 << 24, ldc=0, T=2, n_used=2, N=4, K=256, ws=1 << 25, wsb=1 << 30, bias=1 << 26, bias_up=1 << 27,
+                bias_stride=0, glu_op=0, alpha=1.702, limit=7.0, counts=1 << 28, sorted=1 << 29, st=None)
+MOE_REQUIRED, MOE_OPTIONAL = ("A", "B", "B_up", "ids", "C", "counts", "sorted"), ("weights", "bias", "bias_up")
+
+
+def moe_settled(name, a):
+    """The tool's own reading of qg.h: is this call certain to be refused or empty? Only such calls are made."""
+    types = MOE_ENTRIES[name][1]
+    if min(a["T"], a["n_used"], a["N"]) < 0:
+        return True
+    taken = a["wtype"] in types
+    gran, wal = ROUTED[a["wtype"]] if taken and a["wtype"] in ROUTED else (32, 4)
+    if a["K"] <= 0 or a["K"] % gran or not taken or 0 in (a["T"], a["n_used"], a["N"]):
+        return True
+    if any(a[p] == 0 for p in MOE_REQUIRED if p in a):
+        return True
+    if any(a[p] % al for p, al in (("A", 4), ("ids", 4), ("B", wal or 1), ("B_up", wal or 1), ("weights", 4), ("bias", 4),
+                                   ("bias_up", 4)) if p in a):
+        return True
+    if a.get("a_rows", 1) not in (1, a["n_used"]) or a["ids_stride"] < a["n_used"] or a["n_expert"] < 1 or \
+            a.get("ldc", 0) < 0 or 0 < a.get("ldc", 0) < a["N"] or (a.get("weights") and a["w_stride"] < a["n_used"]):
+        return True
+    if "bias_stride" in a and (a["bias_stride"] < 0 or 0 < a["bias_stride"] < a["N"]):
+        return True
+    if a.get("glu_op") == 3 and "alpha" in a and not (abs(a["alpha"]) < 1e30 and 0 < a["limit"] < 1e30):
+        return True
+    if "ws" in a and (a["ws"] == 0 or a["ws"] % 16 or a["wsb"] <= 16 or a["n_expert"] > 4096):
+        return True
+    if "glu_op" in a and a["glu_op"] not in ((0, 2, 3) if "alpha" in a else (0, 2)):
+        return True
+    return (a["T"] if "w_stride" in a else a["T"] * a["n_used"]) > 65535
+
+
+def moe_defects(params, full):
+    out = []
+    for p in params:
+        if p in ("T", "n_used", "N"):
+            out += [("neg", {p: -1}), ("empty", {p: 0})]
+        elif p == "K":
+            out += [("badk", {p: v}) for v in (-32, 0, 33, 32, 288)]
+        elif p == "wtype":
+            out += [("type", {p: t}) for t in ALL_IDS]
+        elif p in MOE_REQUIRED + MOE_OPTIONAL:
+            out += [("null", {p: 0})] + [("align", {p: MOE_GOOD[p] + o}) for o in ((1, 2, 4, 8) if p in ("B", "B_up") or full else (2,))]
+        elif p == "a_rows":
+            out += [("arg", {p: 0}), ("arg", {p: 3}), ("arg", {p: 2})]
+        elif p in ("ids_stride", "w_stride", "bias_stride", "ldc"):
+            out += [("arg", {p: 1}), ("arg", {p: -1})]
+        elif p == "n_expert":
+            out += [("arg", {p: 0}), ("arg", {p: -1}), ("shape", {p: 4097})]
+        elif p == "ws":
+            out += [("ws", {p: 0}), ("ws", {p: MOE_GOOD[p] + 1}), ("ws", {p: MOE_GOOD[p] + 8})]
+        elif p == "wsb":
+            out += [("ws", {p: 0}), ("ws", {p: 16})]
+        elif p == "glu_op":
+            out += [("shape", {p: v}) for v in (1, 2, 3, 7)]
+        elif p == "alpha":
+            out += [("arg", {p: float("inf")}), ("arg", {p: float("nan")})]
+        elif p == "limit":
+            out += [("arg", {p: 0.0}), ("arg", {p: -1.0}), ("arg", {p: float("nan")})]
+    return out + [("shape", {"T": 70000})]
+
+
+def moe_cases(full):
+    """Every defect alone and every pair of defects of two classes (full: every pair), around a call of each type the
+    entry takes (and around the OAI op of the GLU entry that has it)."""
+    for name, (spec, types) in MOE_ENTRIES.items():
+        params = spec.split()
+        ds = moe_defects(params, full)
+        variants = [dict(wtype=t) for t in types] + ([dict(wtype=39, glu_op=3)] if "alpha" in params else [])
+        seen = set()
+        for v in variants:
+            combos = [(d,) for d in ds] + [(d1, d2) for d1, d2 in itertools.combinations(ds, 2)
+                                           if not set(d1[1]) & set(d2[1]) and (full or d1[0] != d2[0])]
+            for combo in combos:
+                a = {p: MOE_GOOD[p] for p in params if p != "wtype"}
+                a.update(v)
+                for _, ch in combo:
+                    a.update(ch)
+                key = tuple(a[p] for p in params)
+                if moe_settled(name, a) and repr(key) not in seen:
+                    seen.add(repr(key))
+                    yield name, key
+
+
+def type_by_entry_cases():
+    """Every named weight id against every entry that has a type argument, at K = 32, 256 and 288 with the first pointer
+    null: QG_ERR_BAD_K tells the granule the type is checked at, then QG_ERR_UNSUPPORTED a type the entry refuses and
+    QG_ERR_INVALID_ARG (the pointer) one it takes."""
+    for t in ALL_IDS:
+        for k in (32, 256, 288):
+            for e in ENTRIES:
+                tname = next((p[0] for p in e.params if len(p) > 1 and p[1] in ("t", "q")), None)
+                if tname:
+                    a = dict(baseline(e), **{tname: t, ("K" if "K" in baseline(e) else "k"): k})
+                    a[next(p[0] for p in e.params if len(p) > 1 and p[1][0] == "p")] = 0
+                    yield e.name, tuple(a[p[0]] for p in e.params)
+            for name, (spec, _) in MOE_ENTRIES.items():
+                params = spec.split()
+                a = dict({p: MOE_GOOD[p] for p in params if p != "wtype"}, wtype=t, K=k)
+                a[params[0]] = 0
+                yield name, tuple(a[p] for p in params)
+            yield "qg_gemm_w4a8_grouped", (("item", 0, (("A", 0),)), ("top", (("K", k), ("wtype", t))))
+
+
+MOE_CONFIGS = ("qg_moe_config", "qg_moe_glu_config", "qg_moe_down_config", "qg_moe_glu_bias_config", "qg_moe_down_bias_config")
+MOE_PLAN_CONFIGS = ("qg_moe_prefill_config", "qg_moe_batch_config", "qg_moe_prefill_bias_config", "qg_moe_batch_bias_config")
+
+
+def moe_config_cases(grid):
+    """The launch-free qg_moe*_config queries: every named id, a decode and a prefill-size router."""
+    for t in ALL_IDS:
+        for (T, n_used, n_expert), n, k in itertools.product(((1, 2, 4), (64, 8, 128)), grid["N"], grid["K"]):
+            for name in MOE_CONFIGS:
+                yield name, (T, n_used, n, k, t)
+            for name in MOE_PLAN_CONFIGS:
+                yield name, (T, n_used, n_expert, n, k, t)
+
+
+def status_cases(full, fixture="base"):
+    if fixture == "types":
+        for e in ENTRIES:
+            yield from entry_cases(e, full, NEW_TYPES)
+        yield from moe_cases(full)
+        yield from type_by_entry_cases()
+        return
     for e in ENTRIES:
         yield from entry_cases(e, full)
     yield from view_cases(full)
     yield from grouped_cases()
+
+
+def all_dispatch_cases(full, fixture="base"):
+    if fixture == "types":
+        grid = FULL if full else COMMITTED_TYPES
+        return list(dispatch_cases(grid, NEW_TYPES)) + list(moe_config_cases(grid))
+    return list(dispatch_cases(FULL if full else COMMITTED))
 
 
 def case_digest(cases):
@@ -467,7 +639,7 @@ def run_dispatch(lib, cases):
     out = []
     for name, args in cases:
         fn = getattr(lib, name)
-        if name.startswith("qg_debug_config"):
+        if name.endswith("_config") or name.startswith("qg_debug_config"):
             st = fn(*args, buf, 512)
             out.append([st, buf.value.decode()])
         else:
@@ -487,19 +659,19 @@ def run_status(lib, cases):
     return out
 
 
-def child_main(path, full):
+def child_main(path, full, fixture):
     ndev = visible_devices()  # before any library call
     lib = load_library(path)
-    grid = FULL if full else COMMITTED
-    res = {"devices": ndev, "dispatch": run_dispatch(lib, list(dispatch_cases(grid)))}
+    res = {"devices": ndev, "dispatch": run_dispatch(lib, all_dispatch_cases(full, fixture))}
     if ndev == 0:
-        res["status"] = run_status(lib, list(status_cases(full)))
+        res["status"] = run_status(lib, list(status_cases(full, fixture)))
     json.dump(res, sys.stdout)
 
 
-def run_child(path, full):
+def run_child(path, full, fixture="base"):
     env = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(path)] + (["--full"] if full else [])
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(path), "--fixture", fixture] + \
+        (["--full"] if full else [])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True)
     if p.returncode != 0:
         raise RuntimeError(f"api_matrix child failed ({p.returncode}) for {path}:\n{p.stderr[-2000:]}")
@@ -515,11 +687,12 @@ def unpack(blob):
     return json.loads(zlib.decompress(base64.b64decode(blob)))
 
 
-def record(path):
-    res = run_child(path, full=False)
+def record(path, fixture="base"):
+    GOLDEN = GOLDENS[fixture]
+    res = run_child(path, False, fixture)
     if res["devices"]:
         raise SystemExit("a device is visible to the child: the status half was not run, nothing recorded")
-    dcases, scases = list(dispatch_cases(COMMITTED)), list(status_cases(False))
+    dcases, scases = all_dispatch_cases(False, fixture), list(status_cases(False, fixture))
     launched = [c for c, r in zip(scases, res["status"]) if r == ERR_HIP]
     for c in launched[:40]:
         print("reached a launch (fix the grid):", c)
@@ -539,13 +712,13 @@ def record(path):
     return 1 if launched else 0
 
 
-def check(path):
-    """Replay the committed grid against `path`; returns (differences, skipped_status_reason)."""
-    fix = json.load(open(GOLDEN))
-    dcases, scases = list(dispatch_cases(COMMITTED)), list(status_cases(False))
+def check(path, fixture="base"):
+    """Replay a committed grid against `path`; returns (differences, skipped_status_reason, the fixture)."""
+    fix = json.load(open(GOLDENS[fixture]))
+    dcases, scases = all_dispatch_cases(False, fixture), list(status_cases(False, fixture))
     assert (len(dcases), case_digest(dcases)) == (fix["dispatch_cases"], fix["dispatch_digest"]), "dispatch grid changed"
     assert (len(scases), case_digest(scases)) == (fix["status_cases"], fix["status_digest"]), "status grid changed"
-    res = run_child(path, full=False)
+    res = run_child(path, False, fixture)
     want = [fix["results"][i] for i in unpack(fix["dispatch"])]
     diffs = [("dispatch", c, w, g) for c, w, g in zip(dcases, want, res["dispatch"]) if w != g]
     skipped = None
@@ -557,8 +730,12 @@ def check(path):
 
 
 def compare(a, b):
-    ra, rb = run_child(a, full=True), run_child(b, full=True)
-    dcases, scases = list(dispatch_cases(FULL)), list(status_cases(True))
+    return max(compare_fixture(a, b, fixture) for fixture in GOLDENS)
+
+
+def compare_fixture(a, b, fixture):
+    ra, rb = run_child(a, True, fixture), run_child(b, True, fixture)
+    dcases, scases = all_dispatch_cases(True, fixture), list(status_cases(True, fixture))
     diffs = [("dispatch", c, x, y) for c, x, y in zip(dcases, ra["dispatch"], rb["dispatch"]) if x != y]
     n = len(dcases)
     if "status" in ra and "status" in rb:
@@ -570,7 +747,7 @@ def compare(a, b):
         print("status half not run: a device is visible")
     for d in diffs[:200]:
         print("DIFF", *d)
-    print(f"{n} cases compared ({len(dcases)} dispatch), {len(diffs)} differences")
+    print(f"{fixture}: {n} cases compared ({len(dcases)} dispatch), {len(diffs)} differences")
     return 1 if diffs else 0
 
 
@@ -581,19 +758,23 @@ def main():
     ap.add_argument("--compare", nargs=2, metavar=("A.so", "B.so"))
     ap.add_argument("--child", metavar="LIB", help=argparse.SUPPRESS)
     ap.add_argument("--full", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--fixture", choices=list(GOLDENS), default="base")
     a = ap.parse_args()
     if a.child:
-        return child_main(a.child, a.full)
+        return child_main(a.child, a.full, a.fixture)
     if a.record:
-        return record(a.record)
+        return record(a.record, a.fixture)
     if a.compare:
         return compare(*a.compare)
     if a.check:
-        diffs, skipped, _ = check(a.check)
-        for d in diffs[:200]:
-            print("DIFF", *d)
-        print(f"{len(diffs)} differences" + (f"; {skipped}" if skipped else ""))
-        return 1 if diffs else 0
+        total = 0
+        for fixture in GOLDENS:
+            diffs, skipped, _ = check(a.check, fixture)
+            for d in diffs[:200]:
+                print("DIFF", *d)
+            print(f"{fixture}: {len(diffs)} differences" + (f"; {skipped}" if skipped else ""))
+            total += len(diffs)
+        return 1 if total else 0
     ap.error("nothing to do")
 
 

@@ -16,9 +16,13 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llama.cpp-quant-gemm_amd"))
 
-ROW_TYPES, KQ_TYPES = (2, 3, 6, 7, 8), (12, 14)
+ROW_TYPES, KQ_TYPES = (2, 3, 6, 7, 8), (11, 12, 14, 23, 39)  # KQ_TYPES: every routed type
 ROW_K = (64, 96, 256, 512, 1024, 2048, 2304, 4096, 4128, 4352, 8192, 11008, 14336, 16384)
 KQ_K = tuple(sorted({k for k in ROW_K if k % 256 == 0} | {768}))
+MX_K = tuple(sorted(set(ROW_K) | set(KQ_K)))  # MXFP4: K a multiple of 32 and not of 256 too (a partial unit)
+# the mul_mat_id queries: (T, n_used, N, K, wtype), and with n_expert after n_used
+MOE_CONFIGS = ("qg_moe_config", "qg_moe_glu_config", "qg_moe_down_config", "qg_moe_glu_bias_config", "qg_moe_down_bias_config")
+MOE_PLAN_CONFIGS = ("qg_moe_batch_config", "qg_moe_prefill_config", "qg_moe_batch_bias_config", "qg_moe_prefill_bias_config")
 NS = (1, 300, 4096, 8192, 20000)
 MOE = ((1, 2, 4), (3, 2, 8), (64, 8, 128))  # (T, n_used, n_expert)
 W16_TYPES = (2, 8)
@@ -33,9 +37,9 @@ def main():
     import quant_gemm
     import quant_gemm._lib as L
     lib = ctypes.CDLL(args.lib) if args.lib else L.load()
-    for name in ("qg_debug_config", "qg_moe_config", "qg_moe_batch_config", "qg_moe_glu_config", "qg_moe_down_config",
-                 "qg_moe_prefill_config", "qg_group_config", "qg_w16_config", "qg_select_algo", "qg_set_group_affine", "qg_block_bytes"):
-        if name == "qg_moe_down_config" and not hasattr(lib, name):
+    for name in MOE_CONFIGS + MOE_PLAN_CONFIGS + ("qg_debug_config", "qg_group_config", "qg_w16_config", "qg_select_algo",
+                                                  "qg_set_group_affine", "qg_block_bytes"):
+        if name in MOE_CONFIGS + MOE_PLAN_CONFIGS and not hasattr(lib, name):
             continue  # --lib: a build from before the entry
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = L.SIGNATURES[name]
@@ -45,25 +49,26 @@ def main():
         rc = getattr(lib, entry)(*a, buf, 256)
         return f'{entry} {" ".join(map(str, a))} -> {rc} "{buf.value.decode()}"'
 
+    ks_of = lambda t: ROW_K if t in ROW_TYPES else MX_K if t == 39 else KQ_K
     for t in ROW_TYPES + KQ_TYPES:
-        for k in (ROW_K if t in ROW_TYPES else KQ_K):
+        for k in ks_of(t):
             for n in NS:
                 for m in range(1, 9):
                     print(line("qg_debug_config", m, n, k, t, 0, 0), f"qg_select_algo={lib.qg_select_algo(m, n, k, t)}")
                 for T, n_used, n_expert in MOE:
-                    print(line("qg_moe_config", T, n_used, n, k, t))
-                    print(line("qg_moe_glu_config", T, n_used, n, k, t))
-                    if hasattr(lib, "qg_moe_down_config"):
-                        print(line("qg_moe_down_config", T, n_used, n, k, t))
-                    print(line("qg_moe_batch_config", T, n_used, n_expert, n, k, t))
-                    print(line("qg_moe_prefill_config", T, n_used, n_expert, n, k, t))
+                    for entry in MOE_CONFIGS:
+                        if hasattr(lib, entry):
+                            print(line(entry, T, n_used, n, k, t))
+                    for entry in MOE_PLAN_CONFIGS:
+                        if hasattr(lib, entry):
+                            print(line(entry, T, n_used, n_expert, n, k, t))
     # grouped launches on addresses nothing dereferences: 2 and 8 equal items (an affine progression), one mixed-N group
     a, w, c = 1 << 40, 2 << 40, 3 << 40
     for mode in (0, 1, 2):
         lib.qg_set_group_affine(mode)
         for t in ROW_TYPES + KQ_TYPES:
             bb = lib.qg_block_bytes(t)
-            for k in (ROW_K if t in ROW_TYPES else KQ_K):
+            for k in ks_of(t):
                 wbytes = lambda n: n * (k // 32) * bb
                 groups = {f"{cnt}x4096": [(a, w + i * wbytes(4096), c + i * 4096 * 4, 4096, 0) for i in range(cnt)] for cnt in (2, 8)}
                 groups["4096+11008"] = [(a, w, c, 4096, 0), (a, w + wbytes(4096), c + 4096 * 4, 11008, 0)]

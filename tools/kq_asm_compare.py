@@ -6,7 +6,7 @@
 --drop w16s_kernel:2 leaves the parent's third integer / bool template argument of w16s_kernel out of the pairing key: for
 a result that removed that template parameter.
 
-Pairs the kernels of qg_q{4,6}k_{gemv,mmq}, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_down, qg_moe_plan, qg_gemv,
+Pairs the kernels of qg_{q4k,q6k,mxfp4,iq4xs,q3k}_{gemv,mmq}, qg_quantize, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_down, qg_moe_plan, qg_gemv,
 qg_gemv_q4_0 .. qg_gemv_q8_0, qg_capture_fuse and qg_w4a16 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
 does not have is skipped there; one only the result has is a new file: NEW <file>, its kernels not paired), and compares the instruction text from each kernel's label to its end (symbol names, labels' function
 numbers and comments normalised away) and the kernel-resource-usage remarks. Prints one line per file of the result and every pair
@@ -19,7 +19,7 @@ from pathlib import Path
 
 FILES = ["qg_q4k_gemv", "qg_q4k_mmq", "qg_q6k_gemv", "qg_q6k_mmq", "qg_moe", "qg_moe_prefill", "qg_moe_batch", "qg_moe_glu",
          "qg_moe_down", "qg_moe_plan", "qg_gemv", "qg_gemv_q4_0", "qg_gemv_q4_1", "qg_gemv_q5_0", "qg_gemv_q5_1", "qg_gemv_q8_0", "qg_capture_fuse",
-         "qg_w4a16"]
+         "qg_w4a16", "qg_mxfp4_gemv", "qg_mxfp4_mmq", "qg_iq4xs_gemv", "qg_iq4xs_mmq", "qg_q3k_gemv", "qg_q3k_mmq", "qg_quantize"]
 RES = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 
 
@@ -31,7 +31,8 @@ def key(sym):
         i += len(m.group())
         name = sym[i : i + int(m.group())]
         i += len(name)
-    return (name,) + tuple(re.findall(r"L[ib](\d+)E", sym))
+    # (last: the type template arguments and the parameter list, which tell apart kernels that differ in a type alone)
+    return (name,) + tuple(re.findall(r"L[ib](\d+)E", sym)) + (re.sub(r"L[ib]\d+E", "", sym[i:]),)
 
 
 def masked(lines):
