@@ -606,9 +606,9 @@ int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype
  * qg_moe_config for the same N, K and type; the op is no part of the launch's shape), launch-free; the same status
  * codes for the shape.
  * Standing against the three-kernel sequence (MI355X, uniform router): DESIGN.md 3f, profiles/moe_glu/.
- * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, a Q8_1-quantized output for the down
- * product, fused forms of the prefill and batch entries. (The weighted sum over experts after down:
- * qg_gemm_w4a8_moe_down below.) */
+ * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, fused forms of the prefill and batch
+ * entries. (The weighted sum over experts after down: qg_gemm_w4a8_moe_down below; the Q8_1 rows it reads, written by
+ * this product's kernel: qg_gemm_w4a8_moe_glu_q8_1 below.) */
 #define QG_GLU_REGLU  0   /* numbered as ggml's enum ggml_glu_op */
 #define QG_GLU_SWIGLU 2
 int qg_gemm_w4a8_moe_glu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
@@ -665,12 +665,55 @@ int qg_moe_glu_config(int T, int n_used, int N, int K, int wtype, char* buf, siz
  * sequence's time; keep qg_gemm_w4a8_moe and the caller's sum there. In all but one class the launch takes longer than
  * the sequence's product launch alone (1.01 .. 1.40 of it captured): what it saves is the two elementwise kernels and
  * the round trip of the T * n_used * N floats, not time in the product.
- * Not built: the five 32-element types, FP32 input quantized in the prologue, a Q8_1-writing GLU ahead of it, fused
- * forms of the prefill and batch entries. */
+ * Not built: the five 32-element types, FP32 input quantized in the prologue, fused forms of the prefill and batch
+ * entries. (A Q8_1-writing GLU ahead of it: qg_gemm_w4a8_moe_glu_q8_1 below.) */
 int qg_gemm_w4a8_moe_down(const void* A_q8_1, const void* B_experts, int n_expert, const int32_t* ids, int64_t ids_stride,
                           const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
                           int wtype, qg_stream_t stream);
 int qg_moe_down_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- fused gate / up with its GLU, written as Q8_1 rows: the input of qg_gemm_w4a8_moe_down in one launch ----
+ * Between qg_gemm_w4a8_moe_glu and qg_gemm_w4a8_moe_down a caller runs qg_quantize_q8_1 on the T * n_used * N floats the
+ * first has just written. This entry is qg_gemm_w4a8_moe_glu with that quantizer inside its kernel: the floats are
+ * never written, and a Q4_K / Q6_K MoE FFN block at decode is THREE calls: quantize x, this, moe_down.
+ * A, B_gate, B_up, n_expert, ids, ids_stride, wtype (QG_TYPE_Q4_K / QG_TYPE_Q6_K) and glu_op (QG_GLU_REGLU /
+ * QG_GLU_SWIGLU) are exactly those of qg_gemm_w4a8_moe_glu. H_q8_1: block_q8_1 [T][n_used][N/32], dense, 4-B aligned:
+ * precisely the A operand of qg_gemm_w4a8_moe_down (whose K is this N). There is no ldc.
+ * Bytes: the output is byte for byte what qg_quantize_q8_1 writes for the float output of qg_gemm_w4a8_moe_glu on the
+ * same arguments. g and u carry that entry's bits (the same decode GEMV body text at the same LPR, WGS, ONE), the op is
+ * its op, and a block of 32 consecutive rows is quantized as qg_quantize_q8_1 does: d = amax / 127 correctly rounded,
+ * id = 1 / d (0 where d is 0), q = clamp(roundf(x * id), -128, 127), s the fp32 sum of the 32 values accumulated in
+ * element order, d and s stored as f16 (round to nearest even). Two launches give identical bytes.
+ * A slot whose id is outside [0, n_expert) reads no weight byte and writes N/32 blocks of 36 zero bytes (the
+ * quantizer's bytes for 32 x +0.0f).
+ * ONE launch, a single kernel node when captured. The host never reads ids; no device allocation, no synchronisation.
+ * Validation: the order and the codes of qg_gemm_w4a8_moe_glu, with H_q8_1 where C stood (null -> QG_ERR_INVALID_ARG,
+ * off 4 B -> QG_ERR_ALIGN) and no ldc. T, n_used or N equal to 0 -> QG_OK, nothing touched. The entry's own refusals
+ * come last, QG_ERR_UNSUPPORTED with nothing launched: a glu_op other than QG_GLU_REGLU / QG_GLU_SWIGLU; a shape that
+ * QG_ALGO_AUTO at M = 1 does not send to the type's decode GEMV; an LDS need beyond 160 KiB, here the records and the
+ * workgroup's QB finished values, 4 QB bytes behind them (at the record sizes of Q4_K and Q6_K the largest K is the
+ * float entry's: 124672 and 137728); N not a multiple of 32.
+ * qg_moe_glu_q8_1_config names the launch, launch-free, with the same status codes for the shape:
+ *   "moe_glu_q8:q4k_gemv LPR=.. WGS=.. ONE=.. P=.. grid=XxY lds=.."  (or q6k_gemv)
+ * LPR, WGS, ONE: those of qg_moe_glu_config. A workgroup owns QB = max(32, RPB) rows of its slot, a whole number of
+ * Q8_1 blocks, RPB = (WGS / 64) * (64 / LPR) the float entry's rows per workgroup: P = QB / RPB product passes (2 at
+ * K >= 4096, where RPB is 16; 1 below), X = ceil(N / QB), Y = T * n_used, lds = the records + 4 QB.
+ * Which to use (measured on an MI355X with a uniform router against qg_gemm_w4a8_moe_glu followed by qg_quantize_q8_1 on
+ * one stream, per slot, DESIGN.md 3m, profiles/moe_glu_q8/ab_moe_glu_q8.txt): this entry at Qwen3-MoE's shape (N x K =
+ * 768 x 2048, 8 of 128 experts) at T = 1, both types (0.89 Q4_K, 0.91 Q6_K of the two calls' time captured; 0.76 eager),
+ * and at T = 8 for Q6_K (0.96 captured and eager) and for Q4_K eager (0.89). It is NOT ahead beyond the spread for Q4_K
+ * at T = 8 captured (1.01), nor at Mixtral's shape (14336 x 4096, 2 of 8), where a workgroup runs two passes on half the
+ * grid and the weight stream is the time: captured 1.00 .. 1.02 (Q4_K) and 1.03 .. 1.08 (Q6_K) of the two calls' time,
+ * eager 1.04 .. 1.09 (Q6_K), 1.00 (Q4_K, T = 8) and 0.97 (Q4_K, T = 1, the one class ahead there); keep the two calls
+ * there. The launch takes 1.01 .. 1.15 of the float entry's launch alone captured: what it saves is the quantizer's
+ * launch and the round trip of the T * n_used * N floats, not time in the product.
+ * Not built: the biased / MXFP4 twin (qg_gemm_w4a8_moe_glu_bias with Q8_1 rows), a view entry
+ * (qg_mul_mat_id_glu_from_view with a Q8_1 destination), FP32 input quantized in the prologue, a row stride for
+ * H_q8_1, the prefill / batch entries, the five 32-element types. */
+int qg_gemm_w4a8_moe_glu_q8_1(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                              int64_t ids_stride, void* H_q8_1, int T, int n_used, int N, int K, int wtype, int glu_op,
+                              qg_stream_t stream);
+int qg_moe_glu_q8_1_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- the two fused FFN entries with per-expert bias, gpt-oss's clamped SwiGLU and MXFP4 experts ----
  * A gpt-oss FFN block is g = gate_e(x) + bg[e], u = up_e(x) + bu[e], h = swiglu_oai(g, u), d = down_e(h) + bd[e],

@@ -70,6 +70,13 @@ int qg_gemm_w4a8_moe_glu_cpu(const void* A_q8_1, const void* B_gate, const void*
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                              int glu_op, int threads);
 
+/* Host twin of qg_gemm_w4a8_moe_glu_q8_1 (qg.h): qg_gemm_w4a8_moe_glu_cpu into dense floats, then
+ * qg_quantize_row_q8_1_cpu on them: H_q8_1 is block_q8_1 [T][n_used][N/32] in host memory. The entry's validation codes
+ * in its order (H_q8_1 where C stood, no alignment asked; N not a multiple of 32 is QG_ERR_UNSUPPORTED, last). */
+int qg_gemm_w4a8_moe_glu_q8_1_cpu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                                  int64_t ids_stride, void* H_q8_1, int T, int n_used, int N, int K, int wtype, int glu_op,
+                                  int threads);
+
 /* Host twin of qg_gemm_w4a8_moe_down (qg.h): the same arguments with `ids` and `weights` in host memory, and `threads`
  * as above. d_u has the bits of qg_gemm_w4a8_moe_cpu at a_rows = n_used; the fold is the same: acc = +0.0f, then
  * acc = acc + weights[t * w_stride + u] * d_u in ascending u, one rounded fp32 operation each, an id outside

@@ -419,18 +419,19 @@ size_t moe_ws_bytes(int64_t T, int64_t n_used, int64_t n_expert, int min_r) {
 // B_up, checked beside B with the same mask. down: the entry is qg_gemm_w4a8_moe_down: weights stands beside the other
 // pointers (null allowed, 4 B otherwise), w_stride beside ids_stride, and the grid's y is the token, so T is what 65535
 // bounds (slots stays 0). c.biased: the entry is one of the four _bias ones: its bias pointers stand beside the other pointers (null allowed, 4 B otherwise), bias_stride and the OAI op's alpha
-// and limit beside ids_stride.
+// and limit beside ids_stride. cmask: the low bits of C that must be zero (qg_gemm_w4a8_moe_glu_q8_1, whose output, Q8_1
+// blocks, stands where C does).
 //   1. the precheck; 2. a_rows, ids_stride, n_expert, ldc: QG_ERR_INVALID_ARG;
 //   3. the workspace: null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG;
 //   4. QG_ERR_UNSUPPORTED: more than 65535 slots (the grid's y, and the plan's bound), more than 4096 experts in a plan,
 //      an expert stride off the kernel's weight alignment.
 // QG_GO: ldc, estride and slots are set; go on with what only the entry refuses. ids is never read here.
-int moe_front(MoeCall& c, unsigned cls, int min_r, bool up = false, bool down = false) {
+int moe_front(MoeCall& c, unsigned cls, int min_r, bool up = false, bool down = false, uintptr_t cmask = 0) {
     const bool taken = type_in(c.wtype, cls), ksb = taken && is_routed_type(c.wtype);
     const uintptr_t wmask = ksb ? sb_weight_mask(c.wtype) : 3u;
     const int rc = precheck({c.T, c.n_used, c.N}, c.K, ksb ? block_elems(c.wtype) : 32, taken,
                             {{c.A, 3}, {c.B, wmask}, {up ? c.B_up : c.B, wmask}, {c.ids, 3},
-                             {down && c.weights ? c.weights : c.A, 3}, {c.C, 0},
+                             {down && c.weights ? c.weights : c.A, 3}, {c.C, cmask},
                              {c.biased && c.bias_gate ? c.bias_gate : c.A, 3}, {c.biased && c.bias_up ? c.bias_up : c.A, 3}});
     if (rc != QG_GO) return rc;
     if ((c.a_rows != 1 && c.a_rows != c.n_used) || c.ids_stride < c.n_used || c.n_expert < 1 || c.ldc < 0 ||
@@ -546,6 +547,21 @@ int run_moe_glu(MoeCall& c) {
     a.ids_stride = (long)c.ids_stride; a.ldc = (long)c.ldc; a.estride = c.estride; a.arow = (long)(c.K / 32) * 36;
     a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots; a.glu_op = c.glu_op;
     return hip_status(launch_moe_glu(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
+// qg_gemm_w4a8_moe_glu_q8_1, qg_moe_glu_q8_1_config: Q4_K / Q6_K; c.C is H_q8_1 (4 B), c.ldc is 0. run_moe_glu's refusals,
+// then the records with the workgroup's finished values beyond the LDS, and N that is not whole Q8_1 blocks.
+int run_moe_glu_q8(MoeCall& c) {
+    const int rc = moe_front(c, IN_MOE_PLAIN, 0, true, false, 3);
+    if (rc != QG_GO) return rc;
+    if ((c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU) || !moe_gemv_route(c) ||
+        moe_glu_q8_lds_bytes(c.wtype, c.K) > MAX_LDS_BYTES || c.N % 32 != 0)
+        return QG_ERR_UNSUPPORTED;
+    MoeGluQ8Args a;
+    a.A = c.A; a.B_gate = c.B; a.B_up = c.B_up; a.ids = c.ids; a.H = reinterpret_cast<uint32_t*>(c.C);
+    a.ids_stride = (long)c.ids_stride; a.estride = c.estride; a.arow = (long)(c.K / 32) * 36;
+    a.n_used = c.n_used; a.n_expert = c.n_expert; a.N = c.N; a.K = c.K; a.slots = c.slots; a.glu_op = c.glu_op;
+    return hip_status(launch_moe_glu_q8(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
 // qg_gemm_w4a8_moe_down, qg_moe_down_config: Q4_K / Q6_K, a_rows = n_used. Its own refusals: a shape off the decode
@@ -790,6 +806,19 @@ int qg_gemm_w4a8_moe_glu(const void* A_q8_1, const void* B_gate, const void* B_u
 
 int qg_moe_glu_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
     return moe_config(run_moe_glu, T, n_used, 1, N, K, wtype, buf, len);
+}
+
+int qg_gemm_w4a8_moe_glu_q8_1(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                              int64_t ids_stride, void* H_q8_1, int T, int n_used, int N, int K, int wtype, int glu_op,
+                              qg_stream_t stream) {
+    MoeCall c{A_q8_1, 1, B_gate, n_expert, ids, ids_stride, static_cast<float*>(H_q8_1), 0, T, n_used, N, K, wtype, nullptr, 0,
+              (hipStream_t)stream};
+    c.B_up = B_up; c.glu_op = glu_op;
+    return run_moe_glu_q8(c);
+}
+
+int qg_moe_glu_q8_1_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_glu_q8, T, n_used, 1, N, K, wtype, buf, len);
 }
 
 int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,

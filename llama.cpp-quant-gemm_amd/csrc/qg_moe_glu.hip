@@ -17,9 +17,12 @@
 // The arguments travel by value (no device allocation, capture-safe); the host never reads ids.
 // qg_gemm_w4a8_moe_glu_bias (the same with per-expert bias rows, gpt-oss's clamped SwiGLU and MXFP4 experts, family
 // "moe_glu:mxfp4_gemv" beside the two above) is kq_moe_glu_bias_kernel below: the same structure in a kernel of its own.
+// qg_gemm_w4a8_moe_glu_q8_1 (the same g, u and op, written as the Q8_1 rows qg_gemm_w4a8_moe_down reads, families
+// "moe_glu_q8:q4k_gemv", "moe_glu_q8:q6k_gemv") is kq_moe_glu_q8_kernel: its own work split, described there.
 #include "../../include/qg/qg.h"
 #include "qg_kq_launch.hpp"
 #include "qg_moe_glu.hpp"
+#include "qg_quant_block.hpp"
 #include "qg_q4k.hpp"
 #include "qg_q6k.hpp"
 
@@ -216,6 +219,117 @@ __global__ __launch_bounds__(WGS) void kq_moe_glu_bias_kernel(const MoeGluBiasAr
     }
 }
 
+// ---- qg_gemm_w4a8_moe_glu_q8_1: the GLU that writes the Q8_1 rows qg_gemm_w4a8_moe_down reads ------------------
+// A Q8_1 block is 32 consecutive output rows, and a row's reduced sums live in one lane of some wave, so the kernel has
+// a work split of its own: a workgroup owns QB = max(32, RPB) rows of its slot, a whole number of blocks.
+//   RPB = 64 (K < 1024)          one pass, two blocks        (P = 1)
+//   RPB = 32 (1024 <= K < 4096)  one pass, one block         (P = 1)
+//   RPB = 16 (K >= 4096)         two passes, row tiles 2x and 2x + 1 of the float entry's grid, one block (P = 2)
+// The first gate pass stages the activation row (the body's prologue and its barrier); every later product, the up pass
+// and at P = 2 the second tile's gate and up, reads the same records (QG_KQ_A_STAGED): one staging for up to four
+// products and no barrier between them. After each (gate, up) pair the lane that holds the row's reduced sums writes
+// glu(g, u) into h[QB], floats behind the records; g and u have the bits of kq_moe_glu_kernel (the same body text at the
+// same LPR, WGS, ONE, the same glu()). One workgroup-uniform barrier, then wave b quantizes block b, a value per lane
+// (both halves of the wave hold the same 32 values, so every cross-lane step has all 64 lanes live):
+//   amax   a 32-lane butterfly of maxima: four DPP steps within the 16-lane rows, one exchange across them (max is
+//          exact in any order);
+//   d, id, q  div127, the correctly rounded reciprocal and roundf_rc of qg_quant_block.hpp on the lane's value;
+//   s      the contract is the sum in element order: 32 dependent fp32 adds over h[0..31], read from LDS as broadcasts
+//          (every lane runs the chain; a tree would change bits);
+//   bytes  four quad-broadcast DPP moves pack a quad's four bytes into its dword; lane i = 1..8 fetches the dword of
+//          quad i - 1, lane 0 holds f16(d) | f16(s) << 16: the block's 36 bytes leave as nine dword stores of nine lanes.
+// N % 32 == 0, so a block is never partial; a block at or beyond N / 32 (the second block of the last 64-row workgroup)
+// is skipped. An id out of range stores the workgroup's live blocks as zero dwords (the quantizer's bytes for 32 x
+// +0.0f) and returns before any weight address is formed.
+// The kernel is compiled without the packed fp32 instructions (v_pk_mul_f32 and its kin), as the IQ4_XS and Q3_K files are
+// (Makefile); by attribute and not by a flag on the file, which would move the code of the kernels above. The host pass
+// does not know the feature.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QG_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define QG_NO_PK_F32
+#endif
+
+template <int CTRL> __device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+
+// Block `hb` (32 floats in LDS, written before the workgroup's barrier) -> its nine dwords at `dst`; a whole wave.
+__device__ __forceinline__ void quantize_q8_1_block_wave(const float* __restrict__ hb, uint32_t* __restrict__ dst, int lane) {
+    const float v = hb[lane & 31];
+    float m = fabsf(v);
+    m = fmaxf(m, dpp_f<0xB1>(m));   // quad_perm [1,0,3,2]
+    m = fmaxf(m, dpp_f<0x4E>(m));   // quad_perm [2,3,0,1]
+    m = fmaxf(m, dpp_f<0x141>(m));  // row_half_mirror: the other quad of the 8 lanes
+    m = fmaxf(m, dpp_f<0x140>(m));  // row_mirror: the other 8 lanes of the row
+    m = fmaxf(m, __shfl_xor(m, 16));
+    const float amax = fmaxf(0.0f, m);
+    float sum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float4 x = *reinterpret_cast<const float4*>(hb + 4 * j);
+        sum += x.x;
+        sum += x.y;
+        sum += x.z;
+        sum += x.w;
+    }
+    const float d = div127(amax);
+    const float id = d > 0.0f ? 1.0f / d : 0.0f;
+    const uint32_t q = (uint32_t)max(-128, min(127, roundf_rc(v * id))) & 0xFFu;
+    const uint32_t quad = dpp_u<0x00>(q) | (dpp_u<0x55>(q) << 8) | (dpp_u<0xAA>(q) << 16) | (dpp_u<0xFF>(q) << 24);
+    const uint32_t qs = (uint32_t)__shfl((int)quad, (4 * (lane - 1)) & 31);
+    const uint32_t out = lane == 0 ? (f2h_bits(d) | (f2h_bits(sum) << 16)) : qs;
+    if (lane < 9) dst[lane] = out;
+}
+
+template <int WT, int LPR, int WGS, bool ONE>
+__global__ __launch_bounds__(WGS) QG_NO_PK_F32 void kq_moe_glu_q8_kernel(const MoeGluQ8Args a) {
+    constexpr int RPW = 64 / LPR, RPB = (WGS / 64) * RPW;
+    constexpr int P = RPB < 32 ? 32 / RPB : 1, QB = P * RPB, NBLK = QB / 32;
+    static_assert(QB % 32 == 0 && NBLK <= WGS / 64, "a wave per block");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int x = xcd_tile_x();  // the workgroup's QB rows within the slot
+    const int slot = blockIdx.y;
+    const int t = slot / a.n_used, us = slot - t * a.n_used;
+    const int e = a.ids[(long)t * a.ids_stride + us];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nblk = a.N >> 5;
+    const int live = min(NBLK, nblk - x * NBLK);  // >= 1: the grid has ceil(nblk / NBLK) workgroups per slot
+    uint32_t* H = a.H + ((long)slot * nblk + (long)x * NBLK) * 9;
+    if ((unsigned)e >= (unsigned)a.n_expert) {
+        for (int i = tid; i < live * 9; i += WGS) H[i] = 0u;
+        return;
+    }
+    const uint32_t* A = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.A) + (long)t * a.arow);
+    const long eoff = (long)e * a.estride;
+    const uint8_t* Bg = static_cast<const uint8_t*>(a.B_gate) + eoff;
+    const uint8_t* Bu = static_cast<const uint8_t*>(a.B_up) + eoff;
+    float* h = reinterpret_cast<float*>(lds + kq_row_lds_bytes(WT, a.K) / 4);  // [QB]
+    const int local = wave * RPW + lane / LPR;  // the body's row of this lane within a pass
+    const bool holder = lane % LPR == LPR - 1;
+    float g, u;
+    if constexpr (WT == QG_TYPE_Q4_K) {
+        g = q4k_glu_product<LPR, WGS, ONE>(A, Bg, a.N, a.K, x * P);
+        u = q4k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, x * P);
+    } else {
+        g = q6k_glu_product<LPR, WGS, ONE>(A, Bg, a.N, a.K, x * P);
+        u = q6k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, x * P);
+    }
+    if (holder) h[local] = glu(g, u, a.glu_op);  // a row >= N (a block that is skipped) holds glu(0, 0)
+    if constexpr (P == 2) {
+        if constexpr (WT == QG_TYPE_Q4_K) {
+            g = q4k_glu_product_staged<LPR, WGS, ONE>(Bg, a.N, a.K, x * P + 1);
+            u = q4k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, x * P + 1);
+        } else {
+            g = q6k_glu_product_staged<LPR, WGS, ONE>(Bg, a.N, a.K, x * P + 1);
+            u = q6k_glu_product_staged<LPR, WGS, ONE>(Bu, a.N, a.K, x * P + 1);
+        }
+        if (holder) h[RPB + local] = glu(g, u, a.glu_op);
+    }
+    __syncthreads();
+    if (wave < live) quantize_q8_1_block_wave(h + 32 * wave, H + 9 * wave, lane);
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------
 // The single M = 1 call's LPR, WGS and ONE (kq_gemv_form, qg_kq_launch.hpp), on the decode entry's grid.
 template <int WT> hipError_t moe_glu_launch_t(const MoeLaunch<MoeGluArgs>& L) {
@@ -249,7 +363,32 @@ template <int WT> hipError_t moe_glu_bias_launch_t(const MoeLaunch<MoeGluBiasArg
     });
 }
 
+// The same form on the grid of QB-row workgroups: halved where a workgroup runs two passes, the float entry's otherwise.
+template <int WT> hipError_t moe_glu_q8_launch_t(const MoeLaunch<MoeGluQ8Args>& L) {
+    return kq_gemv_form(L.a.K, [&](auto lpr, auto wgs, auto one) -> hipError_t {
+        constexpr int LPR = lpr, WGS = wgs, RPB = (WGS / 64) * (64 / LPR), P = RPB < 32 ? 32 / RPB : 1, QB = P * RPB;
+        const size_t lds = moe_glu_q8_lds_bytes(WT, L.a.K);
+        if (L.describe) {
+            describe_line(L.describe, L.describe_len, "moe_glu_q8:%s_gemv LPR=%d WGS=%d ONE=%d P=%d grid=%dx%d lds=%zu",
+                          kq_family(WT), LPR, WGS, (int)one, P, (L.a.N + QB - 1) / QB, L.a.slots, lds);
+            return hipSuccess;
+        }
+        static_assert(QB == moe_glu_q8_rows(LPR == 64 ? 4096 : LPR == 16 ? 1024 : 256), "moe_glu_q8_rows names QB");
+        static std::atomic<unsigned long long> done;
+        return moe_enqueue(kq_moe_glu_q8_kernel<WT, LPR, WGS, one>, L, QB, L.a.slots, WGS, lds, done);
+    });
+}
+
 }  // namespace
+
+hipError_t launch_moe_glu_q8(const MoeGluQ8Args& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
+    const MoeLaunch<MoeGluQ8Args> L{a, st, describe, describe_len};
+    switch (wtype) {
+        case QG_TYPE_Q4_K: return moe_glu_q8_launch_t<QG_TYPE_Q4_K>(L);
+        case QG_TYPE_Q6_K: return moe_glu_q8_launch_t<QG_TYPE_Q6_K>(L);
+    }
+    return hipErrorInvalidValue;
+}
 
 hipError_t launch_moe_glu_bias(const MoeGluBiasArgs& a, int wtype, hipStream_t st, char* describe, size_t describe_len) {
     const MoeLaunch<MoeGluBiasArgs> L{a, st, describe, describe_len};

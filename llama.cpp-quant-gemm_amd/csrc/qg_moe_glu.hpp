@@ -3,6 +3,7 @@
 #pragma once
 #include "qg_common.hpp"
 #include "qg_kernels.hpp"
+#include "qg_types.hpp"
 
 namespace qg {
 
@@ -34,5 +35,23 @@ struct MoeGluBiasArgs : MoeGluArgs {
 // launch_moe_glu's has, glu_op among the three.
 hipError_t launch_moe_glu_bias(const MoeGluBiasArgs& a, int wtype, hipStream_t st, char* describe = nullptr,
                                size_t describe_len = 0);
+
+// qg_gemm_w4a8_moe_glu_q8_1: the slot of MoeGluArgs with glu(g) * u quantized to Q8_1 inside the kernel: slot s writes
+// the N / 32 blocks H + s * (N / 32) * 9 dwords, the A operand of qg_gemm_w4a8_moe_down. A kernel argument of its own.
+struct MoeGluQ8Args {
+    const void* A;       // block_q8_1 [T][K/32]
+    const void* B_gate;  // n_expert matrices [N][K/256], estride bytes apart
+    const void* B_up;
+    const int32_t* ids;  // device memory
+    uint32_t* H;         // block_q8_1 [T][n_used][N/32], dense
+    long ids_stride, estride, arow;  // elements, bytes, bytes of one activation row
+    int n_used, n_expert, N, K, slots, glu_op;
+};
+// The rows a workgroup owns (a whole number of Q8_1 blocks) and the launch's dynamic LDS: the activation row's records
+// and the workgroup's QB finished values behind them.
+constexpr int moe_glu_q8_rows(int K) { return K >= 1024 ? 32 : 64; }  // max(32, RPB) of kq_gemv_form(K)
+constexpr size_t moe_glu_q8_lds_bytes(int wtype, int K) { return kq_row_lds_bytes(wtype, K) + 4 * (size_t)moe_glu_q8_rows(K); }
+// wtype Q4_K / Q6_K. The caller has checked what launch_moe_glu's has, N % 32 == 0 and the LDS bound.
+hipError_t launch_moe_glu_q8(const MoeGluQ8Args& a, int wtype, hipStream_t st, char* describe = nullptr, size_t describe_len = 0);
 
 }  // namespace qg

@@ -514,6 +514,26 @@ int qg_gemm_w4a8_moe_glu_cpu(const void* A, const void* B_gate, const void* B_up
     return QG_OK;
 }
 
+int qg_gemm_w4a8_moe_glu_q8_1_cpu(const void* A, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                                  int64_t ids_stride, void* H, int T, int n_used, int N, int K, int wtype, int glu_op,
+                                  int threads) {
+    int be;
+    const int bb = entry_block(wtype, qg::IN_MOE_PLAIN, be);
+    // the order of qg_gemm_w4a8_moe_glu_q8_1: the float entry's with H where C stood, then N in whole Q8_1 blocks
+    if (T < 0 || n_used < 0 || N < 0) return QG_ERR_INVALID_ARG;
+    if (K <= 0 || K % be != 0) return QG_ERR_BAD_K;
+    if (!bb) return QG_ERR_UNSUPPORTED;
+    if (T == 0 || n_used == 0 || N == 0) return QG_OK;
+    if (!A || !B_gate || !B_up || !ids || !H) return QG_ERR_INVALID_ARG;
+    if (ids_stride < n_used || n_expert < 1) return QG_ERR_INVALID_ARG;
+    if ((glu_op != QG_GLU_REGLU && glu_op != QG_GLU_SWIGLU) || N % QK != 0) return QG_ERR_UNSUPPORTED;
+    // the GLU twin into dense floats, then the quantizer twin on them
+    std::vector<float> h((size_t)T * (size_t)n_used * (size_t)N);
+    const int rc = qg_gemm_w4a8_moe_glu_cpu(A, B_gate, B_up, n_expert, ids, ids_stride, h.data(), N, T, n_used, N, K, wtype,
+                                            glu_op, threads);
+    return rc != QG_OK ? rc : qg_quantize_row_q8_1_cpu(h.data(), H, (int64_t)h.size());
+}
+
 int qg_gemm_w4a8_moe_down_cpu(const void* A, const void* B, int n_expert, const int32_t* ids, int64_t ids_stride,
                               const float* weights, int64_t w_stride, float* C, int64_t ldc, int T, int n_used, int N, int K,
                               int wtype, int threads) {

@@ -224,10 +224,11 @@ def gemm_w4a8_grouped(activations_q, weights_q, Ns, M: int, K: int, wtype: int =
 
 
 def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: int, wtype: int, a_rows: int, out,
-                  per_token: bool = False):
+                  per_token: bool = False, q8_out: bool = False):
     """What the mul_mat_id wrappers check alike, after the weight type: the contiguous operands, n_expert,
     ids_stride, ``out`` (allocated unless given) and its ldc. per_token: ``out`` is [T, N], a row per token
-    (gemm_w4a8_moe_down), not [T, n_used, N]."""
+    (gemm_w4a8_moe_down), not [T, n_used, N]. q8_out: ``out`` is the dense uint8 [T, n_used, N/32, 36] of
+    gemm_w4a8_moe_glu_q8_1, and there is no ldc (0)."""
     be = block_elems(wtype)
     _require(K % be == 0, f"K must be divisible by {be}, got {K}")
     _require(a_rows in (1, n_used), f"a_rows must be 1 or n_used, got {a_rows}")
@@ -243,6 +244,15 @@ def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: 
     ids_stride = ids.stride(0) if T > 1 else n_used
     _require(ids_stride >= n_used, "ids row stride below n_used")
     a, w = activation_q.contiguous(), experts_q.contiguous()
+    if q8_out:
+        _require(N % 32 == 0, f"N must be divisible by 32, got {N}")
+        if out is None:
+            out = torch.empty((T, n_used, N // 32, 36), dtype=torch.uint8, device=w.device)
+        else:
+            _require(out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (T, n_used, N // 32, 36)
+                     and out.is_contiguous(), "bad out tensor: contiguous uint8 [T, n_used, N/32, 36]")
+            _require(out.device == w.device, "out must be on the experts' device")
+        return a, w, n_expert, ids_stride, out, 0
     if per_token:
         if out is None:
             out = torch.empty((T, N), dtype=torch.float32, device=w.device)
@@ -419,6 +429,37 @@ def moe_glu_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> st
     """The launch ``gemm_w4a8_moe_glu`` makes for this shape ("moe_glu:q4k_gemv LPR=.. WGS=.. ONE=.. grid=XxY lds=..", the
     LPR / WGS / ONE of ``moe_config``); nothing is launched. Raises where the shape is not served."""
     return _config("qg_moe_glu_config", T, n_used, N, K, wtype)
+
+
+def gemm_w4a8_moe_glu_q8_1(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor, ids: torch.Tensor, T: int,
+                           n_used: int, N: int, K: int, wtype: int = Q4_K, glu_op: int = GLU_SWIGLU,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_glu`` with its result written as Q8_1 rows, in ONE launch (qg_gemm_w4a8_moe_glu_q8_1): uint8
+    [T, n_used, N/32, 36], byte for byte ``quantize_q8_1(gemm_w4a8_moe_glu(...))`` and so the ``activation_q`` of
+    ``gemm_w4a8_moe_down`` (whose K is this N). With it a Q4_K / Q6_K MoE FFN block at decode is three calls: quantize x,
+    this, ``gemm_w4a8_moe_down``.
+
+    Operands, ``ids`` and ``glu_op``: as ``gemm_w4a8_moe_glu``. ``N`` must be a multiple of 32. ``out``: optional
+    contiguous uint8 [T, n_used, N/32, 36] on the experts' device, at a 4-byte address. A slot whose id is outside
+    [0, n_expert) is N/32 blocks of zero bytes. Shapes the decode GEMV does not serve raise."""
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the Q8_1-writing gate / up entry takes Q4_K and Q6_K")
+    _require(glu_op in (GLU_REGLU, GLU_SWIGLU), f"unsupported glu_op {glu_op}")
+    a, w, n_expert, ids_stride, out, _ = _moe_operands(activation_q, gate_q, ids, T, n_used, N, K, wtype, 1, out, q8_out=True)
+    _require(up_q.is_cuda and up_q.dtype == torch.uint8 and up_q.device == w.device and up_q.numel() == w.numel(),
+             "Up experts must be a CUDA uint8 tensor of the gate experts' size, on their device")
+    up = up_q.contiguous()
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_glu_q8_1(_ptr(a), _ptr(w), _ptr(up), n_expert, _ptr(ids), ids_stride, _ptr(out),
+                                                         T, n_used, N, K, wtype, glu_op, _stream(w.device)),
+                   "gemm_w4a8_moe_glu_q8_1")
+    return out
+
+
+def moe_glu_q8_1_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_glu_q8_1`` makes for this shape ("moe_glu_q8:q4k_gemv LPR=.. WGS=.. ONE=.. P=.. grid=XxY
+    lds=..": the LPR / WGS / ONE of ``moe_glu_config``, P the product passes of a workgroup, X = ceil(N / max(32, rows
+    per workgroup))); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_glu_q8_1_config", T, n_used, N, K, wtype)
 
 
 def gemm_w4a8_moe_down(activation_q: torch.Tensor, experts_q: torch.Tensor, ids: torch.Tensor,
@@ -991,6 +1032,7 @@ __all__ = [
     "gemm_w4a8_moe", "moe_config",
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
+    "gemm_w4a8_moe_glu_q8_1", "moe_glu_q8_1_config",
     "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
     "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
     "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",

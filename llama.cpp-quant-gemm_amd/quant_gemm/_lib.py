@@ -43,6 +43,8 @@ SIGNATURES = {
     "qg_moe_batch_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_glu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, P], I),
     "qg_moe_glu_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_glu_q8_1": ([P, P, P, I, P, I64, P, I, I, I, I, I, I, P], I),
+    "qg_moe_glu_q8_1_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_down": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
     "qg_moe_down_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_glu_bias": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, P], I),

@@ -24,6 +24,7 @@ SIGNATURES = {
     "qg_gemm_w4a8_moe_cpu": ([P, I, P, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_bias_cpu": ([P, I, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_cpu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, I], I),
+    "qg_gemm_w4a8_moe_glu_q8_1_cpu": ([P, P, P, I, P, I64, P, I, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_down_cpu": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
     "qg_gemm_w4a8_moe_glu_bias_cpu": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, I], I),
     "qg_gemm_w4a8_moe_down_bias_cpu": ([P, P, P, I64, I, P, I64, P, I64, P, I64, I, I, I, I, I, I], I),
@@ -134,6 +135,24 @@ def gemm_w4a8_moe_glu(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, ids
     _ok(load().qg_gemm_w4a8_moe_glu_cpu(_p(a_q), _p(gate_q), _p(up_q), n_expert, _p(ids), ids_stride, _p(c), n, t, n_used, n,
                                         k, wtype, glu_op, threads), "gemm_w4a8_moe_glu_cpu")
     return c
+
+
+def gemm_w4a8_moe_glu_q8_1(a_q: np.ndarray, gate_q: np.ndarray, up_q: np.ndarray, ids: np.ndarray, t: int, n_used: int,
+                           n: int, k: int, wtype: int = 12, glu_op: int = GLU_SWIGLU, threads: int = 1,
+                           ids_stride: int | None = None) -> np.ndarray:
+    """uint8 [t, n_used, n/32, 36] of qg_gemm_w4a8_moe_glu_q8_1_cpu: ``quantize_q8_1(gemm_w4a8_moe_glu(...))``, the
+    Q8_1 rows ``gemm_w4a8_moe_down`` reads. Arguments as ``gemm_w4a8_moe_glu``; ``n`` a multiple of 32."""
+    a_q, gate_q, up_q = np.ascontiguousarray(a_q), np.ascontiguousarray(gate_q), np.ascontiguousarray(up_q)
+    ids = np.ascontiguousarray(ids, np.int32)
+    if gate_q.size != up_q.size:
+        raise RuntimeError("gemm_w4a8_moe_glu_q8_1_cpu: gate and up experts differ in size")
+    n_expert = gate_q.size // max(1, n * (k // BLOCK_ELEMS[wtype]) * BLOCK_BYTES[wtype])
+    if ids_stride is None:
+        ids_stride = ids.size // t if t else n_used
+    h = np.empty((t, n_used, n // 32, 36), np.uint8)
+    _ok(load().qg_gemm_w4a8_moe_glu_q8_1_cpu(_p(a_q), _p(gate_q), _p(up_q), n_expert, _p(ids), ids_stride, _p(h), t, n_used,
+                                             n, k, wtype, glu_op, threads), "gemm_w4a8_moe_glu_q8_1_cpu")
+    return h
 
 
 def gemm_w4a8_moe_down(a_q: np.ndarray, experts_q: np.ndarray, ids: np.ndarray, weights: np.ndarray | None, t: int,

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Compare the GEMV / K-quant / expert kernels of two `make asm` outputs (csrc/Makefile), instantiation by instantiation.
 
-    python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR [--drop KERNEL:POS ...]
+    python tools/kq_asm_compare.py PARENT_ASM_DIR RESULT_ASM_DIR [--drop KERNEL:POS ...] [--new KERNEL ...]
 
 --drop w16s_kernel:2 leaves the parent's third integer / bool template argument of w16s_kernel out of the pairing key: for
-a result that removed that template parameter.
+a result that removed that template parameter. --new kq_moe_glu_q8_kernel names a kernel the result adds to a file both
+sides have: its instantiations are counted (NEW <kernel>: n instantiations) and not paired.
 
 Pairs the kernels of qg_{q4k,q6k,mxfp4,iq4xs,q3k}_{gemv,mmq}, qg_quantize, qg_moe, qg_moe_prefill, qg_moe_batch, qg_moe_glu, qg_moe_down, qg_moe_plan, qg_gemv,
 qg_gemv_q4_0 .. qg_gemv_q8_0, qg_capture_fuse and qg_w4a16 by their name and integer / bool template arguments across the whole file set (a kernel may have moved between files; a file one side
@@ -73,10 +74,10 @@ def resources(txt):
     return out
 
 
-def main(parent, result, drop=()):
+def main(parent, result, drop=(), new=()):
     """drop: (kernel name, position) pairs — that integer / bool template argument is left out of the PARENT's key (the
     result removed the parameter, so its mangled names no longer carry it)."""
-    side = []
+    side, added = [], {}
     for d in (Path(parent), Path(result)):
         side.append({})
         for f in FILES:
@@ -93,8 +94,13 @@ def main(parent, result, drop=()):
                     if kk[0] == name:
                         kk = kk[: 1 + pos] + kk[2 + pos :]
                 assert kk not in side[-1], (f, s, "two kernels with one key")
+                if len(side) == 2 and kk[0] in new:
+                    added[kk[0]] = added.get(kk[0], 0) + 1
+                    continue
                 side[-1][kk] = (f, s, k[s], r[s])
     assert side[1].keys() <= side[0].keys(), ("only in the result", sorted(side[1].keys() - side[0].keys()))
+    for name in sorted(added):
+        print(f"NEW {name}: {added[name]} instantiations, none paired")
     bad = 0
     for f in FILES:
         for kk in sorted(side[0].keys() - side[1].keys()):
@@ -118,5 +124,6 @@ def main(parent, result, drop=()):
 
 if __name__ == "__main__":
     drops = [(a.split(":")[0], int(a.split(":")[1])) for i, a in enumerate(sys.argv[1:]) if sys.argv[i] == "--drop"]
-    dirs = [a for i, a in enumerate(sys.argv[1:]) if a != "--drop" and sys.argv[i] != "--drop"]
-    sys.exit(main(*dirs[:2], drop=drops))
+    news = [a for i, a in enumerate(sys.argv[1:]) if sys.argv[i] == "--new"]
+    dirs = [a for i, a in enumerate(sys.argv[1:]) if a not in ("--drop", "--new") and sys.argv[i] not in ("--drop", "--new")]
+    sys.exit(main(*dirs[:2], drop=drops, new=news))
