@@ -606,8 +606,8 @@ int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype
  * qg_moe_config for the same N, K and type; the op is no part of the launch's shape), launch-free; the same status
  * codes for the shape.
  * Standing against the three-kernel sequence (MI355X, uniform router): DESIGN.md 3f, profiles/moe_glu/.
- * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, fused forms of the prefill and batch
- * entries. (The weighted sum over experts after down: qg_gemm_w4a8_moe_down below; the Q8_1 rows it reads, written by
+ * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, a fused form of the batch entry. (At
+ * prompt sizes: qg_gemm_w4a8_moe_glu_prefill below. The weighted sum over experts after down: qg_gemm_w4a8_moe_down below; the Q8_1 rows it reads, written by
  * this product's kernel: qg_gemm_w4a8_moe_glu_q8_1 below.) */
 #define QG_GLU_REGLU  0   /* numbered as ggml's enum ggml_glu_op */
 #define QG_GLU_SWIGLU 2
@@ -715,6 +715,48 @@ int qg_gemm_w4a8_moe_glu_q8_1(const void* A_q8_1, const void* B_gate, const void
                               qg_stream_t stream);
 int qg_moe_glu_q8_1_config(int T, int n_used, int N, int K, int wtype, char* buf, size_t len);
 
+/* ---- fused gate / up with its GLU at prompt sizes: expert-grouped MFMA, one plan, no intermediate tensor ----
+ * At prompt sizes the first half of a Q4_K / Q6_K MoE FFN block was qg_gemm_w4a8_moe_prefill twice on the same ids and
+ * activations (gate, then up) and the caller's GLU on the two results. This entry is that sequence in two launches: the
+ * plan of qg_gemm_w4a8_moe_prefill once, then one MFMA kernel in which every gathered activation tile is staged in LDS
+ * once and meets the gate and the up weights of its expert, the op applied where g and u are finished. Neither g nor u
+ * is written to memory. The function is qg_gemm_w4a8_moe_glu's:
+ *   C[s * ldc + n] = glu_op(g) * u,  g, u the products of token t's row with expert ids[t * ids_stride + u] of B_gate and
+ *   of B_up; QG_GLU_REGLU and QG_GLU_SWIGLU in the expressions given there, one rounded operation per step, expf.
+ * A: block_q8_1 [T][K/32], one row per token (no a_rows). B_gate, B_up: n_expert dense matrices [N][K/256] each, both of
+ * `wtype`, QG_TYPE_Q4_K or QG_TYPE_Q6_K (every other id: QG_ERR_UNSUPPORTED); they may alias. ids, ids_stride, C, ldc
+ * (0 = N): those of qg_gemm_w4a8_moe. A slot whose id is outside [0, n_expert) writes N times +0.0f and reads no weight.
+ * workspace: that of qg_gemm_w4a8_moe_prefill: device memory, 16-B aligned, at least
+ * qg_gemm_w4a8_moe_prefill_workspace_size(T, n_used, n_expert) bytes, its content arbitrary; the same limits (65535 slots,
+ * 4096 experts). The host never reads ids; no device allocation, no synchronisation: capture-safe, and a replayed graph
+ * follows the ids it finds in the buffer.
+ * Bits: g and u are the values qg_gemm_w4a8_moe_prefill gives on B_gate and on B_up for the same arguments, bit for bit
+ * (the kernel runs at that entry's RG, and an output's arithmetic depends on its activation row, its weight row and KS =
+ * 8 / RG alone), so QG_GLU_REGLU equals the sequence bit for bit. Two launches give identical bits.
+ * Validation: the order of qg_gemm_w4a8_moe_prefill with B_up beside B_gate (null -> QG_ERR_INVALID_ARG; off the type's
+ * alignment, 16 B for Q4_K and 2 B for Q6_K -> QG_ERR_ALIGN): sizes, K, type, empty (QG_OK, nothing touched), pointers,
+ * alignment; ids_stride, n_expert, ldc -> QG_ERR_INVALID_ARG; the workspace (null QG_ERR_INVALID_ARG, off 16 B
+ * QG_ERR_ALIGN, too small QG_ERR_INVALID_ARG); more than 65535 slots or 4096 experts -> QG_ERR_UNSUPPORTED; last, a
+ * glu_op other than QG_GLU_REGLU / QG_GLU_SWIGLU -> QG_ERR_UNSUPPORTED, nothing launched.
+ * qg_moe_glu_prefill_config names the launch, launch-free, with the same status codes for the shape:
+ *   "moe_glu:q4k_mmq TT=.. RG=.. KS=.. R=.. grid=XxY"  (or q6k_mmq)
+ * RG and KS are those of qg_moe_prefill_config for the shape; TT is 1 (tiles of R = 16 rows: two matrices' decoded
+ * super-blocks and two accumulator sets leave no registers for more without scratch); X = ceil(N / (16 RG)), Y the
+ * host's upper bound on the tiles, floor(slots / R) + min(n_expert + 1, slots).
+ * Which to use (measured on an MI355X with a uniform router against qg_gemm_w4a8_moe_prefill on gate, on up, and torch's
+ * silu(g) * u on the same operands, SwiGLU, captured; eager within 0.01 of every ratio; DESIGN.md 3n,
+ * profiles/moe_glu_prefill/ab_moe_glu_prefill.txt). This entry for Q6_K where the sequence runs its (1, 1) form too:
+ * Qwen3-MoE gate/up (N x K = 768 x 2048, 8 of 128 experts) at T = 16, 64 and 256 (0.82, 0.83, 0.82 of the sequence's
+ * time) and Mixtral gate/up (14336 x 4096, 2 of 8) at T = 16 and 64 (0.89, 0.88). It is NOT ahead, keep the sequence:
+ * Q6_K once the sequence takes 64-row tiles (Mixtral T = 256: 1.15, T = 1024: 1.43; Qwen3-MoE T = 1024: 1.10), and Q4_K
+ * everywhere (Mixtral 1.25, 1.29, 1.03, 1.27 at T = 16, 64, 256, 1024; Qwen3-MoE 1.03, 1.06, 1.08, 1.00): Q4_K's own
+ * (1, 1) kernel fits two workgroups on a CU, the fused one (196 VGPRs) one.
+ * Not built: the Q8_1-writing form, MXFP4 / bias / the clamped SwiGLU, the batch (moeb) form, the five 32-element types. */
+int qg_gemm_w4a8_moe_glu_prefill(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                                 int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                                 int glu_op, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_glu_prefill_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
+
 /* ---- the two fused FFN entries with per-expert bias, gpt-oss's clamped SwiGLU and MXFP4 experts ----
  * A gpt-oss FFN block is g = gate_e(x) + bg[e], u = up_e(x) + bu[e], h = swiglu_oai(g, u), d = down_e(h) + bd[e],
  * y = sum_u w[t,u] * d_u. These two entries are qg_gemm_w4a8_moe_glu and qg_gemm_w4a8_moe_down above with the bias rows
@@ -803,7 +845,7 @@ int qg_moe_down_bias_config(int T, int n_used, int N, int K, int wtype, char* bu
  * qg_moe_batch_config (the bias is no part of the launch's shape); for MXFP4 "moe:mxfp4_mmq TT=.. RG=.. KS=.. R=..
  * grid=XxY" and "moeb:mxfp4_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=..".
  * A gpt-oss FFN block at prompt size: quantize, qg_gemm_w4a8_moe_prefill_bias twice (gate, up), the caller's clamped
- * SwiGLU, quantize, qg_gemm_w4a8_moe_prefill_bias (down, a_rows = n_used), the caller's weighted sum.
+ * SwiGLU (qg_gemm_w4a8_moe_glu_prefill serves Q4_K / Q6_K without bias and the two plain ops, not MXFP4 or this op), quantize, qg_gemm_w4a8_moe_prefill_bias (down, a_rows = n_used), the caller's weighted sum.
  * Which entry for which T (measured on an MI355X at gpt-oss's N = K = 2880, MXFP4, uniform router, captured, against
  * qg_gemm_w4a8_moe plus torch's gathered bias add on the same operands; DESIGN.md 3j,
  * profiles/moe_id_bias/ab_moe_id_bias.txt). 4 of 32 experts: qg_gemm_w4a8_moe_batch_bias from T = 8 (0.89 of the
@@ -942,6 +984,11 @@ int qg_mul_mat_id_from_view_batch(const qg_tensor_view* as, const qg_tensor_view
  * as_gate in type, ne or nb. */
 int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
                                 const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, qg_stream_t stream);
+/* The same views and the same refusals, always through qg_gemm_w4a8_moe_glu_prefill with the caller's workspace (of
+ * qg_gemm_w4a8_moe_prefill_workspace_size(T, n_used, n_expert) bytes): the fused pair for a prompt. */
+int qg_mul_mat_id_glu_from_view_ws(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
+                                   const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, void* workspace,
+                                   size_t workspace_bytes, qg_stream_t stream);
 /* The down product of an MoE FFN block with the weighted sum over the token's experts on views, mapped onto
  * qg_gemm_w4a8_moe_down: out[t] = sum_u weights[t, u] * (as[ids[t, u]] x b[t, u]).
  *   as, ids: as in qg_mul_mat_id_from_view; b: Q8_1, ne = [K, n_used, T], dense;

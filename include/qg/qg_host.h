@@ -65,7 +65,8 @@ int qg_gemm_w4a8_moe_cpu(const void* A_q8_1, int a_rows, const void* B_experts, 
  * formulas, one rounded fp32 operation each, with libm's expf: QG_GLU_REGLU (g > 0 ? g : 0.0f) * u, QG_GLU_SWIGLU
  * (g / (1.0f + expf(-g))) * u. An id outside [0, n_expert) gives N times +0.0f. The same validation codes (wtype other
  * than Q4_K / Q6_K and a glu_op other than these two are QG_ERR_UNSUPPORTED; no alignment is asked); no shape is
- * unsupported. */
+ * unsupported. It is the host twin of qg_gemm_w4a8_moe_glu_prefill as well: that entry computes this function at prompt
+ * sizes (its g and u then have the MFMA family's bits, not this twin's). */
 int qg_gemm_w4a8_moe_glu_cpu(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
                              int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                              int glu_op, int threads);

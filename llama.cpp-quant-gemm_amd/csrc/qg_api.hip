@@ -17,6 +17,7 @@
 #include "qg_moe_batch.hpp"
 #include "qg_moe_down.hpp"
 #include "qg_moe_glu.hpp"
+#include "qg_moe_glu_prefill.hpp"
 #include "qg_moe_prefill.hpp"
 #include "qg_mxfp4.hpp"
 #include "qg_q4k.hpp"
@@ -549,6 +550,20 @@ int run_moe_glu(MoeCall& c) {
     return hip_status(launch_moe_glu(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
+// qg_gemm_w4a8_moe_glu_prefill, qg_moe_glu_prefill_config: Q4_K / Q6_K, one activation row per token. run_moe_prefill's
+// refusals with B_up beside B, then its own, last: a glu_op it does not have.
+int run_moe_glu_prefill(MoeCall& c) {
+    c.a_rows = 1;
+    const int rc = moe_front(c, IN_MOE_PLAIN, MOE_PREFILL_MIN_R, true);
+    if (rc != QG_GO) return rc;
+    if (c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU) return QG_ERR_UNSUPPORTED;
+    MoeGluPrefillArgs a;
+    static_cast<MoePlanArgs&>(a) = moe_kernel_args<MoePlanArgs>(c);
+    a.ws = (int32_t*)c.ws;
+    a.B_up = c.B_up; a.glu_op = c.glu_op;
+    return hip_status(launch_moe_glu_prefill(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
 // qg_gemm_w4a8_moe_glu_q8_1, qg_moe_glu_q8_1_config: Q4_K / Q6_K; c.C is H_q8_1 (4 B), c.ldc is 0. run_moe_glu's refusals,
 // then the records with the workgroup's finished values beyond the LDS, and N that is not whole Q8_1 blocks.
 int run_moe_glu_q8(MoeCall& c) {
@@ -833,6 +848,34 @@ int qg_mul_mat_id_glu_from_view(const qg_tensor_view* as_gate, const qg_tensor_v
     c.ws = nullptr; c.ws_bytes = 0; c.st = (hipStream_t)stream;
     c.B_up = as_up->data; c.glu_op = glu_op;
     return run_moe_glu(c);
+}
+
+int qg_gemm_w4a8_moe_glu_prefill(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
+                                 int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
+                                 int glu_op, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MoeCall c{A_q8_1, 1, B_gate, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace, workspace_bytes,
+              (hipStream_t)stream};
+    c.B_up = B_up; c.glu_op = glu_op;
+    return run_moe_glu_prefill(c);
+}
+
+int qg_moe_glu_prefill_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_glu_prefill, T, n_used, n_expert, N, K, wtype, buf, len);
+}
+
+int qg_mul_mat_id_glu_from_view_ws(const qg_tensor_view* as_gate, const qg_tensor_view* as_up, const qg_tensor_view* b,
+                                   const qg_tensor_view* ids, qg_tensor_view* out, int glu_op, void* workspace,
+                                   size_t workspace_bytes, qg_stream_t stream) {
+    if (!as_up) return QG_ERR_INVALID_ARG;
+    MoeCall c;
+    const int rc = mul_mat_id_view(as_gate, b, ids, out, c);
+    if (rc != QG_GO) return rc;
+    if (c.a_rows != 1 || as_up->type != as_gate->type || memcmp(as_up->ne, as_gate->ne, sizeof as_up->ne) != 0 ||
+        memcmp(as_up->nb, as_gate->nb, sizeof as_up->nb) != 0)
+        return QG_ERR_UNSUPPORTED;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.st = (hipStream_t)stream;
+    c.B_up = as_up->data; c.glu_op = glu_op;
+    return run_moe_glu_prefill(c);
 }
 
 int qg_gemm_w4a8_moe_down(const void* A_q8_1, const void* B_experts, int n_expert, const int32_t* ids, int64_t ids_stride,

@@ -19,5 +19,8 @@ hipError_t launch_moe_prefill_bias(const MoeBiasArgs& a, int wtype, hipStream_t 
                                    size_t describe_len = 0);
 // tt of the form launch_moe_prefill picks for this shape (qg_debug_moe_prefill_plan runs the plan it would run)
 int moe_prefill_tt(const MoePlanArgs& a, int wtype);
+// rg of that form: launch_moe_glu_prefill (qg_moe_glu_prefill.hip) takes the same one, so that its g and u have this
+// entry's bits
+int moe_prefill_rg(const MoePlanArgs& a, int wtype);
 
 }  // namespace qg

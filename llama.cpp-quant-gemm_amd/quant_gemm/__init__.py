@@ -431,6 +431,39 @@ def moe_glu_config(T: int, n_used: int, N: int, K: int, wtype: int = Q4_K) -> st
     return _config("qg_moe_glu_config", T, n_used, N, K, wtype)
 
 
+def gemm_w4a8_moe_glu_prefill(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor, ids: torch.Tensor,
+                              T: int, n_used: int, N: int, K: int, wtype: int = Q4_K, glu_op: int = GLU_SWIGLU,
+                              workspace: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_glu`` at prompt sizes (qg_gemm_w4a8_moe_glu_prefill): the slots are sorted by expert id once and
+    every tile of an expert's rows meets its gate and its up matrix in one MFMA kernel, which applies ``glu_op`` and
+    stores C[t, u, :] = glu_op(g) * u, float32 [T, n_used, N]. It replaces two ``gemm_w4a8_moe_prefill`` calls and the
+    activation kernel between them and the down product; g and u have the bits of those calls, never written.
+
+    The operands, ``glu_op`` and ``out`` are those of ``gemm_w4a8_moe_glu`` (``wtype`` Q4_K or Q6_K), ``workspace`` that
+    of ``gemm_w4a8_moe_prefill``: ``moe_prefill_workspace_size(T, n_used, n_expert)`` bytes, allocated here when None.
+    The ids are never copied to the host: a captured graph follows the ids each replay finds."""
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: the fused gate / up prefill takes Q4_K and Q6_K")
+    _require(glu_op in (GLU_REGLU, GLU_SWIGLU), f"unsupported glu_op {glu_op}")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, gate_q, ids, T, n_used, N, K, wtype, 1, out)
+    _require(up_q.is_cuda and up_q.dtype == torch.uint8 and up_q.device == w.device and up_q.numel() == w.numel(),
+             "Up experts must be a CUDA uint8 tensor of the gate experts' size, on their device")
+    up = up_q.contiguous()
+    workspace = _moe_workspace(workspace, moe_prefill_workspace_size(T, n_used, n_expert), w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_glu_prefill(_ptr(a), _ptr(w), _ptr(up), n_expert, _ptr(ids), ids_stride,
+                                                            _ptr(out), ldc, T, n_used, N, K, wtype, glu_op, _ptr(workspace),
+                                                            workspace.numel(), _stream(w.device)),
+                   "gemm_w4a8_moe_glu_prefill")
+    return out
+
+
+def moe_glu_prefill_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_glu_prefill`` makes for this shape ("moe_glu:q4k_mmq TT=.. RG=.. KS=.. R=.. grid=XxY",
+    RG that of ``moe_prefill_config``, Y the host's upper bound on the tiles); nothing is launched. Raises where the
+    shape is not served."""
+    return _config("qg_moe_glu_prefill_config", T, n_used, n_expert, N, K, wtype)
+
+
 def gemm_w4a8_moe_glu_q8_1(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor, ids: torch.Tensor, T: int,
                            n_used: int, N: int, K: int, wtype: int = Q4_K, glu_op: int = GLU_SWIGLU,
                            out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1033,6 +1066,7 @@ __all__ = [
     "gemm_w4a8_moe_prefill", "moe_prefill_workspace_size", "moe_prefill_config", "debug_moe_prefill_plan",
     "gemm_w4a8_moe_batch", "moe_batch_workspace_size", "moe_batch_config",
     "gemm_w4a8_moe_glu_q8_1", "moe_glu_q8_1_config",
+    "gemm_w4a8_moe_glu_prefill", "moe_glu_prefill_config",
     "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
     "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
     "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",

@@ -43,6 +43,8 @@ SIGNATURES = {
     "qg_moe_batch_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_glu": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, P], I),
     "qg_moe_glu_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_glu_prefill": ([P, P, P, I, P, I64, P, I64, I, I, I, I, I, I, P, SZ, P], I),
+    "qg_moe_glu_prefill_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_glu_q8_1": ([P, P, P, I, P, I64, P, I, I, I, I, I, I, P], I),
     "qg_moe_glu_q8_1_config": ([I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_down": ([P, P, I, P, I64, P, I64, P, I64, I, I, I, I, I, P], I),
@@ -110,6 +112,7 @@ SIGNATURES = {
     "qg_mul_mat_id_from_view_ws": ([P, P, P, P, P, SZ, P], I),
     "qg_mul_mat_id_from_view_batch": ([P, P, P, P, P, SZ, P], I),
     "qg_mul_mat_id_glu_from_view": ([P, P, P, P, P, I, P], I),
+    "qg_mul_mat_id_glu_from_view_ws": ([P, P, P, P, P, I, P, SZ, P], I),
     "qg_mul_mat_id_down_from_view": ([P, P, P, P, P, P], I),
     "qg_mul_mat_id_glu_bias_from_view": ([P, P, P, P, P, P, P, I, F, F, P], I),
     "qg_mul_mat_id_down_bias_from_view": ([P, P, P, P, P, P, P], I),

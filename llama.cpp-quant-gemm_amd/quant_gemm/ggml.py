@@ -107,6 +107,20 @@ def mul_mat_id_glu_from_ggml(gate: TensorView, up: TensorView, act: TensorView, 
                "qg_mul_mat_id_glu_from_view")
 
 
+def mul_mat_id_glu_from_ggml_ws(gate: TensorView, up: TensorView, act: TensorView, ids: TensorView, out: TensorView,
+                                glu_op: int, workspace: torch.Tensor) -> None:
+    """The same views through the expert-grouped MFMA gate / up product (qg_mul_mat_id_glu_from_view_ws): the fused pair
+    at prompt sizes. ``workspace``: a CUDA uint8 tensor of quant_gemm.moe_prefill_workspace_size(T, n_used, n_expert)
+    bytes or more."""
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError("workspace must be a contiguous CUDA uint8 tensor")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().qg_mul_mat_id_glu_from_view_ws(ctypes.byref(gate), ctypes.byref(up), ctypes.byref(act),
+                                                          ctypes.byref(ids), ctypes.byref(out), glu_op,
+                                                          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), st),
+               "qg_mul_mat_id_glu_from_view_ws")
+
+
 def mul_mat_id_down_from_ggml(experts: TensorView, act: TensorView, ids: TensorView, weights: TensorView | None,
                               out: TensorView) -> None:
     """The down product of an MoE FFN block with the weighted sum over the token's experts on views
