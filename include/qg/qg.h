@@ -606,7 +606,7 @@ int qg_moe_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype
  * qg_moe_config for the same N, K and type; the op is no part of the launch's shape), launch-free; the same status
  * codes for the shape.
  * Standing against the three-kernel sequence (MI355X, uniform router): DESIGN.md 3f, profiles/moe_glu/.
- * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU, a fused form of the batch entry. (At
+ * Not built: the five 32-element types, a dense (no ids) GLU entry, GEGLU. (The fused form of the batch entry: qg_gemm_w4a8_moe_glu_batch below. At
  * prompt sizes: qg_gemm_w4a8_moe_glu_prefill below. The weighted sum over experts after down: qg_gemm_w4a8_moe_down below; the Q8_1 rows it reads, written by
  * this product's kernel: qg_gemm_w4a8_moe_glu_q8_1 below.) */
 #define QG_GLU_REGLU  0   /* numbered as ggml's enum ggml_glu_op */
@@ -751,7 +751,8 @@ int qg_moe_glu_q8_1_config(int T, int n_used, int N, int K, int wtype, char* buf
  * Q6_K once the sequence takes 64-row tiles (Mixtral T = 256: 1.15, T = 1024: 1.43; Qwen3-MoE T = 1024: 1.10), and Q4_K
  * everywhere (Mixtral 1.25, 1.29, 1.03, 1.27 at T = 16, 64, 256, 1024; Qwen3-MoE 1.03, 1.06, 1.08, 1.00): Q4_K's own
  * (1, 1) kernel fits two workgroups on a CU, the fused one (196 VGPRs) one.
- * Not built: the Q8_1-writing form, MXFP4 / bias / the clamped SwiGLU, the batch (moeb) form, the five 32-element types. */
+ * Not built: the Q8_1-writing form, MXFP4 / bias / the clamped SwiGLU, the five 32-element types (the batch form:
+ * qg_gemm_w4a8_moe_glu_batch below). */
 int qg_gemm_w4a8_moe_glu_prefill(const void* A_q8_1, const void* B_gate, const void* B_up, int n_expert, const int32_t* ids,
                                  int64_t ids_stride, float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype,
                                  int glu_op, void* workspace, size_t workspace_bytes, qg_stream_t stream);
@@ -856,7 +857,7 @@ int qg_moe_down_bias_config(int T, int n_used, int N, int K, int wtype, char* bu
  * at T = 8 and 16 (1.07, 1.02). The prefill's (TT, RG) thresholds are the K-quants' and do not suit MXFP4 everywhere: at
  * T = 256 with 32 experts the rule's (2, 1) takes 2.1 times as long as a forced (4, 4). Q4_K / Q6_K with a bias cost a
  * third launch (an add kernel behind the unbiased entries' kernels): a convenience there, not a saving.
- * Not built: a fused GLU at prefill or batch size, one plan shared by the three products of a layer, an automatic choice
+ * Not built: a fused GLU with bias or MXFP4 at prefill size (at batch size: qg_gemm_w4a8_moe_glu_batch below), one plan shared by the three products of a layer, an automatic choice
  * between the entries, the 32-element types in these entries, an MXFP4 quantizer. */
 int qg_gemm_w4a8_moe_prefill_bias(const void* A_q8_1, int a_rows, const void* B_experts, const float* bias, int64_t bias_stride,
                                   int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
@@ -866,6 +867,66 @@ int qg_gemm_w4a8_moe_batch_bias(const void* A_q8_1, int a_rows, const void* B_ex
                                 int n_expert, const int32_t* ids, int64_t ids_stride, float* C, int64_t ldc, int T, int n_used,
                                 int N, int K, int wtype, void* workspace, size_t workspace_bytes, qg_stream_t stream);
 int qg_moe_batch_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
+
+/* ---- fused gate / up with its GLU for batched decode: expert-grouped decode GEMV, one plan, no intermediate tensor ----
+ * Between qg_gemm_w4a8_moe_glu_bias (a slot per workgroup) and qg_gemm_w4a8_moe_glu_prefill (MFMA on 16-row tiles): 8 to
+ * 256 sequences of one token each, 2 to 16 slots per expert, where the expert-grouped decode GEMV is the faster product.
+ * The first half of an MoE FFN block there was qg_gemm_w4a8_moe_batch_bias on gate, on up, and the caller's op: two plans
+ * of the same ids, the gathered activation rows staged twice, 2 * slots * N floats written and read back. This entry is
+ * that sequence in two launches: the plan of qg_gemm_w4a8_moe_batch once, then one kernel in which a tile of R = 2, 4 or 8
+ * gathered rows is staged in LDS once and runs the type's decode GEMV body on expert e of B_gate and then of B_up; the
+ * lane that holds a row's reduced sums adds the biases, applies the op and makes the one store per (row, slot).
+ * The function is exactly qg_gemm_w4a8_moe_glu_bias's: slot s = t * n_used + u, e = ids[t * ids_stride + u], A one row
+ * per token, g and u the two products, each non-null bias one rounded addition, QG_GLU_REGLU / QG_GLU_SWIGLU /
+ * QG_GLU_SWIGLU_OAI in that entry's expressions, alpha and limit read for the third alone; a null bias is no add (-0.0f
+ * stays -0.0f); an id outside [0, n_expert) stores N times +0.0f and reads no weight byte and no bias. wtype:
+ * QG_TYPE_Q4_K, QG_TYPE_Q6_K or QG_TYPE_MXFP4 (every other id: QG_ERR_UNSUPPORTED); B_gate and B_up may alias.
+ * workspace and limits: those of qg_gemm_w4a8_moe_batch (qg_gemm_w4a8_moe_batch_workspace_size bytes, 16-B aligned,
+ * content arbitrary; 65535 slots, 4096 experts); R is that entry's for (slots, n_expert, K, type), and its LDS refusals
+ * (the records of two rows beyond 160 KiB) are this entry's. No type's R is capped here: every instantiation is free of
+ * scratch (profiles/moe_glu_batch/resource_usage.txt). The host never reads ids; no device allocation, no
+ * synchronisation: capture-safe, and a replayed graph follows the ids it finds in the buffer.
+ * Bits: g and u are bit-identical to qg_gemm_w4a8_moe on B_gate / B_up for the slot (LPR, WGS and ONE are the single
+ * M = 1 call's, a token's accumulation chain is its own), so to qg_gemm_w4a8_moe_batch_bias; the output is
+ * bit-identical to qg_gemm_w4a8_moe_glu_bias on the same arguments (the same expressions, the same device expf).
+ * Nothing depends on R, the tile or the sort position. Two launches give identical bits.
+ * Validation, in order: sizes; K (a positive multiple of 256, of 32 for MXFP4); type; empty (QG_OK, nothing touched);
+ * null pointers -> QG_ERR_INVALID_ARG; alignment (weights by the type's rule, a non-null bias 4 B) -> QG_ERR_ALIGN;
+ * ids_stride, n_expert, ldc, bias_stride -> QG_ERR_INVALID_ARG, and there for QG_GLU_SWIGLU_OAI an alpha that is not
+ * finite or a limit that is not finite and > 0; the workspace (null QG_ERR_INVALID_ARG, off 16 B QG_ERR_ALIGN, too small
+ * QG_ERR_INVALID_ARG); QG_ERR_UNSUPPORTED: more than 65535 slots or 4096 experts, an expert stride off the weight
+ * alignment, a shape off the type's decode GEMV, the records of two rows beyond the LDS; last, a glu_op other than the
+ * three -> QG_ERR_UNSUPPORTED. No pointer is dereferenced on any refusal.
+ * qg_moe_glu_batch_config names the launch, launch-free, with the same status codes for the shape:
+ *   "moeb_glu:q4k_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY lds=.."  (or q6k_gemv, mxfp4_gemv)
+ * every field that of qg_moe_batch_bias_config for the same shape (bias and op are no part of the launch's shape).
+ * The host twin is qg_gemm_w4a8_moe_glu_bias_cpu (qg_host.h): it computes this function.
+ * Which entry for which T (measured on an MI355X with a uniform router, captured, median of 7 interleaved rounds; eager
+ * within 0.03 of every ratio but (a) for Qwen3-MoE Q4_K at T = 8 and 16: 0.54, 0.77; DESIGN.md 3o,
+ * profiles/moe_glu_batch/ab_moe_glu_batch.txt), against (a) qg_gemm_w4a8_moe_batch_bias on gate, on up, and torch's op,
+ * and (b) qg_gemm_w4a8_moe_glu_bias, time of this entry over theirs:
+ *   Qwen3-MoE gate/up (768 x 2048, 8 of 128, SwiGLU, no bias), T = 8, 16, 32, 64, 256:
+ *     Q4_K  (a) 0.74 0.81 0.88 0.93 1.00   (b) 1.31 1.10 0.92 0.65 0.46
+ *     Q6_K  (a) 0.75 0.80 0.85 0.91 0.93   (b) 1.18 0.98 0.81 0.55 0.33
+ *   Mixtral gate/up (14336 x 4096, 2 of 8), T = 8, 16, 32, 64:
+ *     Q4_K  (a) 0.75 0.85 0.97 1.01        (b) 0.75 0.56 0.48 0.43
+ *     Q6_K  (a) 0.81 0.83 0.91 0.96        (b) 0.68 0.44 0.33 0.29
+ *   gpt-oss (2880 x 2880, MXFP4, both biases, QG_GLU_SWIGLU_OAI), T = 8, 16, 32, 64:
+ *     4 of 32   (a) 0.71 0.78 0.82 0.88    (b) 0.91 0.79 0.54 0.41
+ *     4 of 128  (a) 0.74 0.77 0.80 0.84    (b) 1.06 0.97 0.85 0.73
+ * So: this entry from about one slot per expert upward. NOT ahead of the decode entry (b) below that: Qwen3-MoE at T = 8
+ * (Q4_K 1.31, Q6_K 1.18) and Q4_K at T = 16 (1.10), gpt-oss with 128 experts at T = 8 (1.06); level with it for Qwen3-MoE
+ * Q6_K at T = 16 (0.98, ranges overlap): keep qg_gemm_w4a8_moe_glu_bias there. NOT ahead of the sequence (a) where the
+ * weight stream is the time: Q4_K at Mixtral's shape at T = 64 (1.01) and at Qwen3-MoE's at T = 256 (1.00), Q6_K at
+ * Qwen3-MoE's at T = 256 within the rounds' spread (0.93, ranges overlap); beyond T * n_used / n_expert = 16 the
+ * prefill entries are the ones to measure against.
+ * Not built: a ggml view entry, the Q8_1-writing form, the five 32-element types, Q3_K / IQ4_XS, one plan shared with
+ * the down product, an automatic choice between the entries. */
+int qg_gemm_w4a8_moe_glu_batch(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
+                               const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids, int64_t ids_stride,
+                               float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op, float alpha,
+                               float limit, void* workspace, size_t workspace_bytes, qg_stream_t stream);
+int qg_moe_glu_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len);
 
 /* ---- weight-major twins (kernels/gemm/gemm_quant_formats.cuh:343-428) ---------------------
  * out[M][N] = W[M][K/32] . A[N][K/32]^T, M = weight rows, N = tokens. */

@@ -17,6 +17,7 @@
 #include "qg_moe_batch.hpp"
 #include "qg_moe_down.hpp"
 #include "qg_moe_glu.hpp"
+#include "qg_moe_glu_batch.hpp"
 #include "qg_moe_glu_prefill.hpp"
 #include "qg_moe_prefill.hpp"
 #include "qg_mxfp4.hpp"
@@ -610,6 +611,24 @@ int run_moe_glu_bias(MoeCall& c) {
     return hip_status(launch_moe_glu_bias(a, c.wtype, c.st, c.describe, c.describe_len));
 }
 
+// qg_gemm_w4a8_moe_glu_batch, qg_moe_glu_batch_config: Q4_K / Q6_K / MXFP4 (c.biased), one activation row per token.
+// run_moe_batch_bias's refusals with B_up beside B, then its own, last: a glu_op it does not have.
+int run_moe_glu_batch(MoeCall& c) {
+    c.a_rows = 1;
+    c.biased = true;
+    const int rc = moe_front(c, IN_MOE_BIAS, MOE_BATCH_MIN_R, true);
+    if (rc != QG_GO) return rc;
+    const int R = moe_batch_rows(c.slots, c.n_expert, c.K, c.wtype);
+    if (!moe_gemv_route(c) || R == 0 || moe_max_tiles(c.slots, c.n_expert, R) > 65535) return QG_ERR_UNSUPPORTED;
+    if (c.glu_op != QG_GLU_REGLU && c.glu_op != QG_GLU_SWIGLU && c.glu_op != QG_GLU_SWIGLU_OAI) return QG_ERR_UNSUPPORTED;
+    MoeGluBatchArgs a;
+    static_cast<MoePlanArgs&>(a) = moe_kernel_args<MoePlanArgs>(c);
+    a.ws = (int32_t*)c.ws;
+    a.B_up = c.B_up; a.bias_gate = c.bias_gate; a.bias_up = c.bias_up; a.bias_stride = (long)c.bias_stride;
+    a.glu_op = c.glu_op; a.alpha = c.alpha; a.limit = c.limit;
+    return hip_status(launch_moe_glu_batch(a, c.wtype, c.st, c.describe, c.describe_len));
+}
+
 // qg_gemm_w4a8_moe_down_bias, qg_moe_down_bias_config: Q4_K / Q6_K / MXFP4 (c.biased), run_moe_down's refusals.
 int run_moe_down_bias(MoeCall& c) {
     c.a_rows = c.n_used;
@@ -981,6 +1000,21 @@ int qg_gemm_w4a8_moe_batch_bias(const void* A_q8_1, int a_rows, const void* B_ex
 
 int qg_moe_batch_bias_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
     return moe_config(run_moe_batch_bias, T, n_used, n_expert, N, K, wtype, buf, len);
+}
+
+int qg_gemm_w4a8_moe_glu_batch(const void* A_q8_1, const void* B_gate, const void* B_up, const float* bias_gate,
+                               const float* bias_up, int64_t bias_stride, int n_expert, const int32_t* ids, int64_t ids_stride,
+                               float* C, int64_t ldc, int T, int n_used, int N, int K, int wtype, int glu_op, float alpha,
+                               float limit, void* workspace, size_t workspace_bytes, qg_stream_t stream) {
+    MoeCall c{A_q8_1, 1, B_gate, n_expert, ids, ids_stride, C, ldc, T, n_used, N, K, wtype, workspace, workspace_bytes,
+              (hipStream_t)stream};
+    c.B_up = B_up; c.glu_op = glu_op;
+    c.bias_gate = bias_gate; c.bias_up = bias_up; c.bias_stride = bias_stride; c.alpha = alpha; c.limit = limit;
+    return run_moe_glu_batch(c);
+}
+
+int qg_moe_glu_batch_config(int T, int n_used, int n_expert, int N, int K, int wtype, char* buf, size_t len) {
+    return moe_config(run_moe_glu_batch, T, n_used, n_expert, N, K, wtype, buf, len);
 }
 
 // qg_mul_mat_id_bias_from_view_ws / _batch: the views of qg_mul_mat_id_from_view_ws, then the bias view, then the entry

@@ -47,7 +47,7 @@ enum : unsigned {
     IN_PRODUCT = 1,      // the products that take the routed types (qg_gemm_w4a8, _ex, _ldc, _f32, _from_view, the sumi hook)
     IN_MOE = 2,          // qg_gemm_w4a8_moe
     IN_MOE_PLAIN = 4,    // qg_gemm_w4a8_moe_prefill, _moe_batch, _moe_glu, _moe_down
-    IN_MOE_BIAS = 8,     // the four _bias entries
+    IN_MOE_BIAS = 8,     // the four _bias entries, qg_gemm_w4a8_moe_glu_batch
     IN_QUANTIZE = 16,    // qg_quantize
     IN_DEQUANTIZE = 32,  // qg_dequantize
     IN_GGUF = 64,        // the GGUF reader serves it (another known type stays listed with nbytes == 0)

@@ -668,6 +668,46 @@ def moe_batch_bias_config(T: int, n_used: int, n_expert: int, N: int, K: int, wt
     return _config("qg_moe_batch_bias_config", T, n_used, n_expert, N, K, wtype)
 
 
+def gemm_w4a8_moe_glu_batch(activation_q: torch.Tensor, gate_q: torch.Tensor, up_q: torch.Tensor, ids: torch.Tensor, T: int,
+                            n_used: int, N: int, K: int, wtype: int = Q4_K, op: int = GLU_SWIGLU,
+                            bias_gate: torch.Tensor | None = None, bias_up: torch.Tensor | None = None,
+                            alpha: float = 1.702, limit: float = 7.0, workspace: torch.Tensor | None = None,
+                            out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gemm_w4a8_moe_glu_bias`` for batched decode, 2 to 16 slots per expert (qg_gemm_w4a8_moe_glu_batch): the slots
+    are sorted by expert id once and every tile of 2, 4 or 8 of an expert's rows meets its gate and then its up matrix in
+    one decode-GEMV kernel, which adds the biases, applies ``op`` and stores C[t, u, :], float32 [T, n_used, N]. It
+    replaces two ``gemm_w4a8_moe_batch_bias`` calls and the activation kernel between them and the down product; every
+    slot is bit-identical to ``gemm_w4a8_moe_glu_bias``.
+
+    Operands, biases, ``op`` (GLU_REGLU / GLU_SWIGLU / GLU_SWIGLU_OAI), ``alpha``, ``limit`` and ``out``: as
+    ``gemm_w4a8_moe_glu_bias`` (``wtype`` Q4_K, Q6_K or MXFP4). ``workspace``: as ``gemm_w4a8_moe_batch``
+    (``moe_batch_workspace_size``), allocated here when None. The ids are never copied to the host: a captured graph
+    follows the ids each replay finds."""
+    _require(wtype in (Q4_K, Q6_K, MXFP4), f"unsupported weight type {wtype}: the batched gate / up entry takes Q4_K, Q6_K and MXFP4")
+    _require(op in (GLU_REGLU, GLU_SWIGLU, GLU_SWIGLU_OAI), f"unsupported glu_op {op}")
+    a, w, n_expert, ids_stride, out, ldc = _moe_operands(activation_q, gate_q, ids, T, n_used, N, K, wtype, 1, out)
+    _require(up_q.is_cuda and up_q.dtype == torch.uint8 and up_q.device == w.device and up_q.numel() == w.numel(),
+             "Up experts must be a CUDA uint8 tensor of the gate experts' size, on their device")
+    up = up_q.contiguous()
+    bg, sg = _moe_bias(bias_gate, n_expert, N, w.device, "bias_gate")
+    bu, su = _moe_bias(bias_up, n_expert, N, w.device, "bias_up")
+    _require(bg is None or bu is None or sg == su, "bias_gate and bias_up must have one row stride")
+    workspace = _moe_workspace(workspace, moe_batch_workspace_size(T, n_used, n_expert), w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_moe_glu_batch(_ptr(a), _ptr(w), _ptr(up), None if bg is None else _ptr(bg),
+                                                          None if bu is None else _ptr(bu), sg or su, n_expert, _ptr(ids),
+                                                          ids_stride, _ptr(out), ldc, T, n_used, N, K, wtype, op, alpha,
+                                                          limit, _ptr(workspace), workspace.numel(), _stream(w.device)),
+                   "gemm_w4a8_moe_glu_batch")
+    return out
+
+
+def moe_glu_batch_config(T: int, n_used: int, n_expert: int, N: int, K: int, wtype: int = Q4_K) -> str:
+    """The launch ``gemm_w4a8_moe_glu_batch`` makes for this shape ("moeb_glu:q4k_gemv R=.. LPR=.. WGS=.. ONE=.. grid=XxY
+    lds=..", every field that of ``moe_batch_bias_config``); nothing is launched. Raises where the shape is not served."""
+    return _config("qg_moe_glu_batch_config", T, n_used, n_expert, N, K, wtype)
+
+
 def repack_weights(weight_q: torch.Tensor, N: int, K: int, wtype: int = Q4_0) -> torch.Tensor:
     """Load-time layout for K/32 not a multiple of 8 (qg_repack_weights): [N, K'/32, bb] uint8,
     the real blocks then zero blocks (K'/32 = round_up(K/32, 8)). Feed it to gemm_w4a8_prepacked."""
@@ -1070,4 +1110,5 @@ __all__ = [
     "gemm_w4a8_moe_glu", "moe_glu_config", "GLU_REGLU", "GLU_SWIGLU", "gemm_w4a8_moe_down", "moe_down_config",
     "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
     "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",
+    "gemm_w4a8_moe_glu_batch", "moe_glu_batch_config",
 ]

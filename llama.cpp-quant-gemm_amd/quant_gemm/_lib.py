@@ -57,6 +57,8 @@ SIGNATURES = {
     "qg_moe_prefill_bias_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_moe_batch_bias": ([P, I, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, P, SZ, P], I),
     "qg_moe_batch_bias_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
+    "qg_gemm_w4a8_moe_glu_batch": ([P, P, P, P, P, I64, I, P, I64, P, I64, I, I, I, I, I, I, F, F, P, SZ, P], I),
+    "qg_moe_glu_batch_config": ([I, I, I, I, I, I, ctypes.c_char_p, SZ], I),
     "qg_gemm_w4a8_workspace_size": ([I, I, I, I], SZ),
     "qg_gemm_w4a8_ws": ([P, P, P, I, I, I, I, P, SZ, P], I),
     "qg_repack_weights_bytes": ([I, I, I], SZ),

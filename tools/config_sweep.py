@@ -22,7 +22,8 @@ KQ_K = tuple(sorted({k for k in ROW_K if k % 256 == 0} | {768}))
 MX_K = tuple(sorted(set(ROW_K) | set(KQ_K)))  # MXFP4: K a multiple of 32 and not of 256 too (a partial unit)
 # the mul_mat_id queries: (T, n_used, N, K, wtype), and with n_expert after n_used
 MOE_CONFIGS = ("qg_moe_config", "qg_moe_glu_config", "qg_moe_down_config", "qg_moe_glu_bias_config", "qg_moe_down_bias_config")
-MOE_PLAN_CONFIGS = ("qg_moe_batch_config", "qg_moe_prefill_config", "qg_moe_batch_bias_config", "qg_moe_prefill_bias_config")
+MOE_PLAN_CONFIGS = ("qg_moe_batch_config", "qg_moe_prefill_config", "qg_moe_batch_bias_config", "qg_moe_prefill_bias_config",
+                    "qg_moe_glu_batch_config")
 NS = (1, 300, 4096, 8192, 20000)
 MOE = ((1, 2, 4), (3, 2, 8), (64, 8, 128))  # (T, n_used, n_expert)
 W16_TYPES = (2, 8)
