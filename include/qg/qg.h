@@ -110,7 +110,8 @@ int qg_gemm_w4a8_ldc(const void* A_q8_1, const void* B, float* C, int M, int N, 
  * QG_ERR_ALIGN; QG_ALGO_RAGGED / QG_ALGO_GENERIC -> QG_ERR_UNSUPPORTED; qg_gemm_w4a8_f32 without a
  * workspace of qg_gemm_w4a8_f32_workspace_size(M, K) bytes -> QG_ERR_UNSUPPORTED.
  * Every other entry that takes a wtype (tiled, repacked, prepacked, padded, grouped, strided-batched, _ws,
- * qg_quantize) returns QG_ERR_UNSUPPORTED for it and launches nothing. */
+ * qg_quantize) returns QG_ERR_UNSUPPORTED for it and launches nothing. Groups of Q4_K and Q6_K decode GEMVs in one
+ * launch: qg_gemm_w4a8_grouped_kq, which takes the type per item. */
 
 /* ---- Q6_K weights (wtype == QG_TYPE_Q6_K) --------------------------------------------------
  * B: block_q6_K[N][K/256], ggml's bytes (qg/blocks.h), rows dense. Q8_1 block b (0..7) of super-block sb is
@@ -426,6 +427,50 @@ void qg_set_group_affine(int mode);
  * when there is nothing to launch. Returns what qg_gemm_w4a8_grouped would return for the same arguments
  * before launching. */
 int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtype, char* buf, size_t len);
+
+/* ---- grouped decode GEMV of Q4_K / Q6_K items: a dense K-quant layer's Q / K / V or gate / up in one launch ----
+ * Item i computes C_i[m * ldc_i + n] = A_i[M][K] . B_i[N_i][K]^T (m < M, n < N_i) with weights of ITS OWN type,
+ * QG_TYPE_Q4_K or QG_TYPE_Q6_K: a Q4_K_M / Q4_K_S file has Q4_K Q, K, gate and up projections and, in half its
+ * layers, Q6_K V and ffn_down. One M and one K for the group. qg_gemm_w4a8_grouped keeps refusing both types.
+ * Result: C_i is overwritten with the bits of qg_gemm_w4a8(A_i, B_i, C_i, M, N_i, K, wtype_i) (with ldc_i as
+ * qg_gemm_w4a8_ldc takes it): the launch runs the single call's kernel body at the single call's instantiation.
+ * Items with N_i == 0 are skipped. Items must be independent as the capture-time merge defines it at qg_gemm_w4a8 (no
+ * item's output overlaps another item's output or operands), else the result is undefined; shared A and shared B are fine.
+ * Up to 64 items are ONE launch ("gemvg:kq"): blockIdx.y the item, blockIdx.x its row tile, grid.x the largest item's
+ * tiles (workgroups past a shorter item's rows leave at once). The table of 32-B item records travels by value in the
+ * kernel arguments, sorted by type so that the kernel knows an item's type from its index: no device allocation, the
+ * host `items` array is read before return, no pointer is dereferenced on the host. Under stream capture the call is
+ * one kernel node per 64 items (the capture-time merge is not involved: K-quant single calls stay plain nodes).
+ * More than 64 items: successive launches of up to 64, in the caller's order. M > 8, or M * K beyond the LDS records of
+ * the largest record type present (Q4_K 336 B, Q6_K 304 B per token and super-block, 160 KiB in all): the items are
+ * enqueued one by one as qg_gemm_w4a8_ldc would run them (QG_ALGO_AUTO: the MFMA prefill from M = 9 on).
+ * Validation, in this order, nothing enqueued on any of them: count, M, any N_i or ldc_i negative, items null with
+ * count > 0, 0 < ldc_i < N_i or reserved != 0 -> QG_ERR_INVALID_ARG; K not a positive multiple of 256 -> QG_ERR_BAD_K;
+ * any item's wtype not Q4_K or Q6_K (an item with N_i == 0 too) -> QG_ERR_UNSUPPORTED; count == 0, M == 0 or every
+ * N_i == 0 -> QG_OK, nothing touched; a null A, B or C of an item with N_i > 0 -> QG_ERR_INVALID_ARG; A or C not 4-B
+ * aligned, a Q4_K B not 16-B aligned, a Q6_K B not 2-B aligned -> QG_ERR_ALIGN.
+ * Measured on an MI355X against one qg_gemm_w4a8 per item, 32 captured layers at K = 4096, M = 1, 2, 4, 8
+ * (profiles/group_kq/README.md): Q / K / V with N = 4096, 1024, 1024 0.72 - 0.78 x with a Q6_K V and 0.69 - 0.70 x all
+ * Q4_K (half of the grid's workgroups lie past the short items' rows and leave at once); gate / up with N = 14336 twice
+ * 0.85 - 0.89 x. Every measured row is ahead beyond the spread of the rounds; where the items run one by one (M > 8)
+ * there is nothing to gain. */
+typedef struct {
+    const void* A_q8_1;  /* block_q8_1 [M][K/32]; items may share it */
+    const void* B;       /* blocks of this item's wtype, [N][K/256], rows dense */
+    float* C;            /* [M][ldc] */
+    int N, ldc;          /* ldc in floats, 0 = N */
+    int wtype;           /* QG_TYPE_Q4_K or QG_TYPE_Q6_K, per item */
+    int reserved;        /* 0 */
+} qg_gemv_item_kq;
+int qg_gemm_w4a8_grouped_kq(const qg_gemv_item_kq* items, int count, int M, int K, qg_stream_t stream);
+
+/* The route qg_gemm_w4a8_grouped_kq(items, count, M, K) would take for its first launch, written to buf (NUL-terminated,
+ * truncated to len); nothing is enqueued and no pointer is dereferenced.
+ * "gemvg:kq T=<q4k|q6k|mix> MT= LPR= WGS= ONE= grid=XxY lds=": the grouped kernel, its type form (one type's body, or
+ * both behind a uniform branch), the single call's instantiation, the grid (row tiles x items) and the dynamic LDS;
+ * "items: ..." when the items are enqueued one by one; "none" when there is nothing to launch. Returns what
+ * qg_gemm_w4a8_grouped_kq would return for the same arguments before launching. */
+int qg_group_kq_config(const qg_gemv_item_kq* items, int count, int M, int K, char* buf, size_t len);
 
 /* ---- expert-indexed decode GEMV: ggml_mul_mat_id for a decode step, ids read on the device ----
  * Slot s = t * n_used + u (t < T, u < n_used):

@@ -11,6 +11,7 @@
 #include <initializer_list>
 
 #include "../../include/qg/qg.h"
+#include "qg_group_kq.hpp"
 #include "qg_iq4xs.hpp"
 #include "qg_q3k.hpp"
 #include "qg_kernels.hpp"
@@ -1323,6 +1324,89 @@ int qg_group_config(const qg_gemv_item* items, int count, int M, int K, int wtyp
 }
 
 void qg_set_group_affine(int mode) { set_group_affine(mode); }
+
+// qg_gemm_w4a8_grouped_kq and qg_group_kq_config: the precheck's order over all the items (by hand, as run_grouped: every
+// item's sizes, then K, then every item's type, then the empty call, then every live item's pointers), then one launch
+// per 64 live items, or the items one by one.
+static int run_grouped_kq(const qg_gemv_item_kq* items, int count, int M, int K, hipStream_t st, char* describe,
+                          size_t describe_len) {
+    if (count < 0 || M < 0 || (count > 0 && !items)) return QG_ERR_INVALID_ARG;
+    for (int i = 0; i < count; ++i) {
+        const qg_gemv_item_kq& it = items[i];
+        if (it.N < 0 || it.ldc < 0 || (it.ldc != 0 && it.ldc < it.N) || it.reserved != 0) return QG_ERR_INVALID_ARG;
+    }
+    if (K <= 0 || K % 256 != 0) return QG_ERR_BAD_K;
+    int live = 0, live_q4k = 0, maxm = 8;
+    for (int i = 0; i < count; ++i) {
+        const int t = items[i].wtype;
+        if (t != QG_TYPE_Q4_K && t != QG_TYPE_Q6_K) return QG_ERR_UNSUPPORTED;
+        if (items[i].N == 0) continue;
+        ++live;
+        live_q4k += t == QG_TYPE_Q4_K;
+        maxm = std::min(maxm, weight_type(t).gemv_maxm);
+    }
+    if (M == 0 || live == 0) {
+        describe_line(describe, describe_len, "%s", "none");
+        return QG_OK;
+    }
+    for (int i = 0; i < count; ++i)
+        if (items[i].N != 0 && (!items[i].A_q8_1 || !items[i].B || !items[i].C)) return QG_ERR_INVALID_ARG;
+    for (int i = 0; i < count; ++i) {
+        const qg_gemv_item_kq& it = items[i];
+        if (it.N == 0) continue;
+        if ((((uintptr_t)it.A_q8_1 | (uintptr_t)it.C) & 3) != 0 || ((uintptr_t)it.B & sb_weight_mask(it.wtype)) != 0)
+            return QG_ERR_ALIGN;
+    }
+    // one launch where the single call of every item takes its decode GEMV: M within the types' threshold and the
+    // records of the largest record type present within the LDS (a smaller type's then fit too)
+    if (M > maxm || group_kq_lds_bytes(M, K, live_q4k) > MAX_LDS_BYTES) {
+        if (describe) {
+            describe_line(describe, describe_len, "%s", "items: one qg_gemm_w4a8 launch per item");
+            return QG_OK;
+        }
+        for (int i = 0; i < count; ++i) {
+            const qg_gemv_item_kq& it = items[i];
+            if (it.N == 0) continue;
+            GemmArgs g = product_args(it.A_q8_1, it.B, it.C, M, it.N, K, it.wtype);
+            if (it.ldc) g.ldc_m = it.ldc;
+            const int rc = run_product(g, QG_ALGO_AUTO, st);
+            if (rc != QG_OK) return rc;
+        }
+        return QG_OK;
+    }
+    for (int i0 = 0; i0 < count;) {
+        // the next 64 live items, the device table sorted by type: Q4_K first, the caller's order within a type
+        const int first = i0;
+        int n = 0, n_q4k = 0;
+        for (; i0 < count && n < GEMV_GROUP_MAX; ++i0) {
+            if (items[i0].N == 0) continue;
+            ++n;
+            n_q4k += items[i0].wtype == QG_TYPE_Q4_K;
+        }
+        if (n == 0) break;
+        GemvGroup grp = {};
+        grp.M = M; grp.K = K; grp.count = n;
+        int at[2] = {0, n_q4k};  // where the next Q4_K / Q6_K item goes
+        for (int i = first; i < i0; ++i) {
+            const qg_gemv_item_kq& it = items[i];
+            if (it.N == 0) continue;
+            grp.it[at[it.wtype == QG_TYPE_Q6_K]++] = GemvItemDesc{it.A_q8_1, it.B, it.C, it.N, it.ldc ? it.ldc : it.N};
+        }
+        const int rc = hip_status(launch_group_kq(grp, n_q4k, st, describe, describe_len));
+        if (rc != QG_OK || describe) return rc;
+    }
+    return QG_OK;
+}
+
+int qg_gemm_w4a8_grouped_kq(const qg_gemv_item_kq* items, int count, int M, int K, qg_stream_t stream) {
+    return run_grouped_kq(items, count, M, K, (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_group_kq_config(const qg_gemv_item_kq* items, int count, int M, int K, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    return run_grouped_kq(items, count, M, K, nullptr, buf, len);
+}
 
 int qg_gemm_w4a8(const void* A, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream) {
     return qg_gemm_w4a8_ex(A, B, C, M, N, K, wtype, QG_ALGO_AUTO, stream);

@@ -223,6 +223,43 @@ def gemm_w4a8_grouped(activations_q, weights_q, Ns, M: int, K: int, wtype: int =
     return res
 
 
+class _GemvItemKq(ctypes.Structure):
+    _fields_ = [("A_q8_1", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p),
+                ("N", ctypes.c_int), ("ldc", ctypes.c_int), ("wtype", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+def gemm_w4a8_grouped_kq(activations_q, weights_q, Ns, wtypes, M: int, K: int, outs=None):
+    """Grouped decode products of Q4_K / Q6_K items, the type per item (qg_gemm_w4a8_grouped_kq): item i =
+    activations_q[i] [M, K/32, 36] (items may share one tensor) x weights_q[i] [Ns[i], K/256, 144 | 210] of type
+    wtypes[i] -> outs[i] [M, Ns[i]] (allocated unless given; a given out may be a row-strided view, e.g. a column slice
+    of a wider buffer). One launch for up to 64 items at M <= 8; each output bit-identical to gemm_w4a8 on its item."""
+    n = len(weights_q)
+    _require(len(activations_q) == n and len(Ns) == n and len(wtypes) == n, "item count mismatch")
+    _require(K % 256 == 0, f"K must be divisible by 256, got {K}")
+    items = (_GemvItemKq * max(n, 1))()
+    res, keep = [], []
+    dev = weights_q[0].device if n else torch.device("cuda")
+    for i in range(n):
+        a, w, N, t = activations_q[i], weights_q[i], int(Ns[i]), int(wtypes[i])
+        _require(t in (Q4_K, Q6_K), f"unsupported weight type {t}")
+        _check_blocks(a, "Activation", M, K, 36)
+        _check_blocks(w, "Weight", N, K, BLOCK_BYTES[t], 256)
+        a, w = a.contiguous(), w.contiguous()
+        if outs is None:
+            o = torch.empty((M, N), dtype=torch.float32, device=w.device)
+        else:
+            o = outs[i]
+            _require(o.dtype == torch.float32 and o.shape == (M, N) and (N <= 1 or o.stride(1) == 1),
+                     "out must be float32 [M, N] with unit column stride")
+        keep += [a, w]
+        ldc = o.stride(0) if M > 1 else N
+        items[i] = _GemvItemKq(a.data_ptr(), w.data_ptr(), o.data_ptr(), N, ldc, t, 0)
+        res.append(o)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().qg_gemm_w4a8_grouped_kq(items, n, M, K, _stream(dev)), "gemm_w4a8_grouped_kq")
+    return res
+
+
 def _moe_operands(activation_q, experts_q, ids, T: int, n_used: int, N: int, K: int, wtype: int, a_rows: int, out,
                   per_token: bool = False, q8_out: bool = False):
     """What the mul_mat_id wrappers check alike, after the weight type: the contiguous operands, n_expert,
@@ -1078,6 +1115,17 @@ def group_config(items, M: int, K: int, wtype: int = Q4_0) -> str:
     return buf.value.decode()
 
 
+def group_kq_config(items, M: int, K: int) -> str:
+    """The route gemm_w4a8_grouped_kq would take for items = [(A_ptr, B_ptr, C_ptr, N, ldc, wtype), ...] (device
+    addresses as ints, ldc 0 = N): "gemvg:kq T=<q4k|q6k|mix> ..." the grouped kernel, "items: ..." one launch per item,
+    "none" nothing to launch. Nothing runs and no pointer is dereferenced (qg_group_kq_config)."""
+    n = len(items)
+    arr = (_GemvItemKq * max(n, 1))(*[_GemvItemKq(*it, 0) for it in items])
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().qg_group_kq_config(arr, n, M, K, buf, len(buf)), "group_kq_config")
+    return buf.value.decode()
+
+
 def capture_fusion_stats() -> "tuple[int, int]":
     """(merged, nodes): captured GEMV calls merged into an existing graph node, and GEMV nodes started."""
     merged, nodes = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -1111,4 +1159,5 @@ __all__ = [
     "gemm_w4a8_moe_glu_bias", "moe_glu_bias_config", "gemm_w4a8_moe_down_bias", "moe_down_bias_config", "GLU_SWIGLU_OAI",
     "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",
     "gemm_w4a8_moe_glu_batch", "moe_glu_batch_config",
+    "gemm_w4a8_grouped_kq", "group_kq_config",
 ]
