@@ -472,6 +472,31 @@ int qg_gemm_w4a8_grouped_kq(const qg_gemv_item_kq* items, int count, int M, int 
  * qg_gemm_w4a8_grouped_kq would return for the same arguments before launching. */
 int qg_group_kq_config(const qg_gemv_item_kq* items, int count, int M, int K, char* buf, size_t len);
 
+/* ---- Q4_K / Q6_K decode GEMV on FP32 rows: a dense K-quant layer's o_proj, ffn_down or output.weight in one launch ----
+ * C[M][N] = quantize_q8_1(X[M][K]) . B[N][K]^T for dense FP32 rows X, dense output rows C and B in the row layout of
+ * wtype QG_TYPE_Q4_K or QG_TYPE_Q6_K, M <= 8. ONE launch, no workspace, capture-safe (one kernel node): each workgroup
+ * quantizes the M rows in its prologue, eight lanes per 32-element block, straight into the LDS records of the single
+ * call's decode GEMV, and runs that GEMV's body at the single call's instantiation. qg_gemm_w4a8_f32 keeps asking for a
+ * workspace for these types and keeps running two launches.
+ * Result: C is overwritten with the bits of qg_quantize_q8_1(X) followed by qg_gemm_w4a8(.., QG_ALGO_AUTO) on it.
+ * Validation, in this order, nothing enqueued on any of them: M or N negative -> QG_ERR_INVALID_ARG; K not a positive
+ * multiple of 256 -> QG_ERR_BAD_K; a wtype other than Q4_K / Q6_K, M > 8, or M * K beyond the LDS records (Q4_K 336 B,
+ * Q6_K 304 B per row and super-block, 160 KiB in all) -> QG_ERR_UNSUPPORTED (call qg_gemm_w4a8_f32 with its workspace);
+ * M == 0 or N == 0 -> QG_OK, nothing touched; a null pointer -> QG_ERR_INVALID_ARG; X not 16-B aligned, C not 4-B
+ * aligned, a Q4_K B not 16-B aligned, a Q6_K B not 2-B aligned -> QG_ERR_ALIGN.
+ * Every workgroup quantizes all M rows (M * K * 4 bytes of FP32 from L2 against M * K / 32 * 36 of Q8_1), so the gain
+ * shrinks as M and N grow. Measured on an MI355X against the two-call sequence, captured, N x K = 4096 x 4096, 4096 x
+ * 14336, 14336 x 4096 (profiles/kq_f32/README.md): ahead at M = 1 (0.80 - 0.95 x; Q6_K at K = 14336 level) and at M = 2
+ * for N = K = 4096 (0.92 - 0.93 x); behind from M = 2 at the two large shapes (1.03 - 1.11 x) and from M = 4 everywhere
+ * (1.06 - 1.82 x): keep qg_gemm_w4a8_f32 with its workspace there. */
+int qg_gemm_w4a8_f32_kq(const float* X, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream);
+
+/* The launch qg_gemm_w4a8_f32_kq(.., M, N, K, wtype) would make on aligned operands, written to buf (NUL-terminated,
+ * truncated to len); nothing is enqueued. "q4k_gemv_f32 MT= LPR= WGS= ONE= grid= lds=" (or "q6k_gemv_f32 ..."): the
+ * (MT, LPR, WGS, ONE), grid and dynamic LDS of qg_debug_config's line for the Q8_1 product of the same shape; "none"
+ * when M or N is 0. Returns what qg_gemm_w4a8_f32_kq would return for the same sizes and type before launching. */
+int qg_f32_kq_config(int M, int N, int K, int wtype, char* buf, size_t len);
+
 /* ---- expert-indexed decode GEMV: ggml_mul_mat_id for a decode step, ids read on the device ----
  * Slot s = t * n_used + u (t < T, u < n_used):
  *   e = ids[t * ids_stride + u]

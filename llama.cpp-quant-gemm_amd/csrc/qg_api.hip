@@ -15,6 +15,7 @@
 #include "qg_iq4xs.hpp"
 #include "qg_q3k.hpp"
 #include "qg_kernels.hpp"
+#include "qg_kq_f32.hpp"
 #include "qg_moe_batch.hpp"
 #include "qg_moe_down.hpp"
 #include "qg_moe_glu.hpp"
@@ -1406,6 +1407,30 @@ int qg_group_kq_config(const qg_gemv_item_kq* items, int count, int M, int K, ch
     if (!buf || len == 0) return QG_ERR_INVALID_ARG;
     buf[0] = 0;
     return run_grouped_kq(items, count, M, K, nullptr, buf, len);
+}
+
+// qg_gemm_w4a8_f32_kq and qg_f32_kq_config: the precheck, whose type test here is "a launch of kq_f32_kernel serves it"
+// (Q4_K or Q6_K, M within the decode GEMV, the rows' records within the LDS), then that launch.
+static int run_f32_kq(const float* X, const void* B, float* C, int M, int N, int K, int wtype, hipStream_t st, char* describe,
+                      size_t describe_len) {
+    const bool kq = wtype == QG_TYPE_Q4_K || wtype == QG_TYPE_Q6_K;
+    const bool served = kq && M <= 8 && K > 0 && kq_f32_lds_bytes(M > 0 ? M : 0, K, wtype) <= MAX_LDS_BYTES;
+    const int rc = precheck({M, N}, K, 256, served, {{X, 15}, {B, kq ? sb_weight_mask(wtype) : 0u}, {C, 3}});
+    if (rc != QG_GO) {
+        if (rc == QG_OK) describe_line(describe, describe_len, "%s", "none");
+        return rc;
+    }
+    return hip_status(launch_kq_f32(KqF32Args{X, B, C, M, N, K, wtype}, st, describe, describe_len));
+}
+
+int qg_gemm_w4a8_f32_kq(const float* X, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream) {
+    return run_f32_kq(X, B, C, M, N, K, wtype, (hipStream_t)stream, nullptr, 0);
+}
+
+int qg_f32_kq_config(int M, int N, int K, int wtype, char* buf, size_t len) {
+    if (!buf || len == 0) return QG_ERR_INVALID_ARG;
+    buf[0] = 0;
+    return run_f32_kq((const float*)256, (const void*)256, (float*)256, M, N, K, wtype, nullptr, buf, len);
 }
 
 int qg_gemm_w4a8(const void* A, const void* B, float* C, int M, int N, int K, int wtype, qg_stream_t stream) {

@@ -10,7 +10,7 @@
 //   QG_KQ_ABLK(g)       the address of activation block g = m * K/32 + b in staging: `A + (long)g * 9` for dense rows,
 //                       the gathered row of tile position m in the expert-grouped GEMV (qg_moe_batch.hip)
 //   QG_KQ_OUT(m)        the output of token m at this lane's row: `C[m * ldc + row]`, the slot's row there
-// and four the shipped includers leave undefined:
+// and these, which the shipped includers leave undefined:
 //   QG_KQ_A_STAGED      defined: the LDS records already hold the activation row (an earlier pass of the same
 //                       workgroup staged it and a barrier has passed); the body loads its first unit and goes on
 //   QG_KQ_STAGE_ONLY    defined: the inclusion is the staging prologue alone, the M activation rows into the records
@@ -19,6 +19,10 @@
 //                       workgroup whose waves share rows; tile is then not needed)
 //   QG_KQ_RECS          the first LDS record of the activation row(s) the product reads, where that is not the start
 //                       of the dynamic LDS (with QG_KQ_A_STAGED: the row of another slot)
+//   QG_KQ_ROWS_LOAD /   a pair, where the records are not copied from Q8_1 blocks (qg_kq_f32.hip quantizes FP32 rows):
+//   QG_KQ_ROWS_PUT      _LOAD issues the thread's first activation load, ahead of the lane's first unit; _PUT writes
+//                       every record of the M rows, behind it (totb, nb, nsb, tid and lds are in scope; the barrier
+//                       follows). QG_KQ_ABLK is then not needed
     constexpr int RPW = 64 / LPR;
     constexpr int RPB = (WGS / 64) * RPW;  // rows per workgroup
 #ifdef QG_KQ_RECS
@@ -58,6 +62,9 @@
 #else
     // 1) this thread's first activation block, 2) the lane's first unit, 3) the LDS records
     const int totb = M * nb;
+#ifdef QG_KQ_ROWS_LOAD
+    QG_KQ_ROWS_LOAD
+#else
     auto load_ablk = [&](int g, uint32_t (&d)[9]) {
         const uint32_t* p = QG_KQ_ABLK(g);
 #pragma unroll
@@ -74,15 +81,20 @@
     };
     uint32_t ab[9];
     if (tid < totb) load_ablk(tid, ab);
+#endif
 #ifndef QG_KQ_STAGE_ONLY
     uint32_t cur[Q4K_UNIT_DW];
     load_unit(cur, lir);
 #endif
+#ifdef QG_KQ_ROWS_LOAD
+    QG_KQ_ROWS_PUT
+#else
     if (tid < totb) put_ablk(tid, ab);
     for (int g = tid + WGS; g < totb; g += WGS) {
         load_ablk(g, ab);
         put_ablk(g, ab);
     }
+#endif
     __syncthreads();
 #endif
 

@@ -96,4 +96,54 @@ __device__ __forceinline__ void quantize_q8_1_block_fp16_fused(const float (&v)[
     for (int i = 0; i < 8; ++i) out[1 + i] = q[i];
 }
 
+// Eight lanes per block (the standalone Q8_1 quantizer, qg_quantize.hip, where the split and its byte identity with
+// quantize_q8_1_block are argued; the K-quant FP32-row GEMV's prologue, qg_kq_f32.hip).
+// One block's quantization by its 8 lanes (all 64 lanes of the wave take part in the DPP steps): lane j holds
+// elements 4j..4j+3 in v; returns qs dword j, and in lane 7 the d | s dword in hdr.
+template <int VARIANT> __device__ __forceinline__ uint32_t q8_1_lanes(const float4 v, int j, uint32_t& hdr) {
+    float m = fmaxf(fmaxf(fmaxf(fmaxf(0.0f, fabsf(v.x)), fabsf(v.y)), fabsf(v.z)), fabsf(v.w));
+    m = fmaxf(m, dpp_f<0xB1>(m));   // quad_perm [1,0,3,2]
+    m = fmaxf(m, dpp_f<0x4E>(m));   // quad_perm [2,3,0,1]
+    m = fmaxf(m, dpp_f<0x141>(m));  // row_half_mirror: the other quad of the 8 lanes
+    const float xs[4] = {v.x, v.y, v.z, v.w};
+    uint32_t qd = 0;
+    int sq = 0;
+    float d;
+    if constexpr (VARIANT == 2) {
+        d = m > 0.0f ? m / 127.0f : 1.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float r = fminf(fmaxf(rintf(xs[e] / d), -128.0f), 127.0f);
+            qd |= ((uint32_t)(int)r & 0xFFu) << (8 * e);
+        }
+    } else {
+        d = div127(m);
+        const float id = d > 0.0f ? 1.0f / d : 0.0f;
+        uint32_t t[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int q = roundf_rc(xs[e] * id);  // |q| <= 127 unless d is subnormal (inexact): clamp kept
+            const int c = VARIANT == 1 ? max(-127, min(127, q)) : max(-128, min(127, q));
+            sq += c;
+            t[e] = (uint32_t)c;
+        }
+        // low bytes of t[0..3] into one dword: two byte permutes and an or
+        qd = __builtin_amdgcn_perm(t[1], t[0], 0x0c0c0400u) | __builtin_amdgcn_perm(t[3], t[2], 0x04000c0cu);
+    }
+    float s;
+    if constexpr (VARIANT == 1) {
+        sq += __builtin_amdgcn_update_dpp(0, sq, 0xB1, 0xF, 0xF, false);
+        sq += __builtin_amdgcn_update_dpp(0, sq, 0x4E, 0xF, 0xF, false);
+        sq += __builtin_amdgcn_update_dpp(0, sq, 0x141, 0xF, 0xF, false);
+        s = (float)sq * d;
+    } else {
+        float p = (((0.0f + v.x) + v.y) + v.z) + v.w;
+#pragma unroll
+        for (int step = 1; step < 8; ++step) p = (((dpp_f<0x111>(p) + v.x) + v.y) + v.z) + v.w;  // row_shr:1
+        s = p;  // complete in lane 7
+    }
+    hdr = f2h_bits(d) | (f2h_bits(s) << 16);
+    return qd;
+}
+
 }  // namespace qg

@@ -1126,6 +1126,35 @@ def group_kq_config(items, M: int, K: int) -> str:
     return buf.value.decode()
 
 
+def gemm_w4a8_f32_kq(x: torch.Tensor, weight_q: torch.Tensor, wtype: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """C[M, N] = Q8_1(x)[M, K] . B_w[N, K]^T for FP32 x [M, K], M <= 8, and Q4_K or Q6_K weights in ONE launch without a
+    workspace: the bits of ``gemm_w4a8(quantize_q8_1(x), weight_q, ...)`` (qg_gemm_w4a8_f32_kq). out: float32, M * N
+    elements, contiguous."""
+    _require(x.is_cuda and weight_q.is_cuda, "x and weight_q must be CUDA tensors")
+    _require(x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous(), "x must be contiguous float32 [M, K]")
+    _require(wtype in (Q4_K, Q6_K), f"unsupported weight type {wtype}: Q4_K or Q6_K")
+    M, K = x.shape
+    _require(K % 256 == 0, f"K must be divisible by 256, got {K}")
+    N = weight_q.numel() // ((K // 256) * BLOCK_BYTES[wtype]) if K else 0
+    _check_blocks(weight_q, "Weight", N, K, BLOCK_BYTES[wtype], 256)
+    _require(weight_q.is_contiguous(), "weight_q must be contiguous")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    else:
+        _require(out.is_contiguous() and out.dtype == torch.float32 and out.numel() == M * N and out.device == x.device,
+                 "bad out tensor")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().qg_gemm_w4a8_f32_kq(_ptr(x), _ptr(weight_q), _ptr(out), M, N, K, wtype, _stream(x.device)),
+                   "gemm_w4a8_f32_kq")
+    return out
+
+
+def f32_kq_config(M: int, N: int, K: int, wtype: int) -> str:
+    """The launch gemm_w4a8_f32_kq makes for the shape: "q4k_gemv_f32 MT= LPR= WGS= ONE= grid= lds=" (or
+    "q6k_gemv_f32 ..."), "none" when M or N is 0. Nothing runs (qg_f32_kq_config)."""
+    return _config("qg_f32_kq_config", M, N, K, wtype)
+
+
 def capture_fusion_stats() -> "tuple[int, int]":
     """(merged, nodes): captured GEMV calls merged into an existing graph node, and GEMV nodes started."""
     merged, nodes = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -1160,4 +1189,5 @@ __all__ = [
     "gemm_w4a8_moe_prefill_bias", "moe_prefill_bias_config", "gemm_w4a8_moe_batch_bias", "moe_batch_bias_config",
     "gemm_w4a8_moe_glu_batch", "moe_glu_batch_config",
     "gemm_w4a8_grouped_kq", "group_kq_config",
+    "gemm_w4a8_f32_kq", "f32_kq_config",
 ]
